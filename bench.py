@@ -8,17 +8,27 @@ combiner folding them in order -- byte for byte the per-frame loop), then, when 
 gather of the accumulated framebuffer for its present -- hrt_read_image on a context joined to an RCCL
 communicator (hrt_comm_init: one ncclGather to rank 0 + the row un-interleave on rank 0's device,
 behind the C ABI).  --frames-per-launch 1 runs the realtime loop instead (compute_then_render: trace
-+ accumulate + gather per frame); the line also reports per_frame_dispatch_ms, a short realtime loop
-measured after the timed steps.
++ accumulate + gather per frame).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the line.  --full adds what takes runs of its own: cpu_baseline and parity_sample (the CPU
+oracle on a sample of the last timed frame, --cpu-seconds), per_frame_dispatch_ms (a short realtime
+loop after the timed steps, --realtime-frames) and, for N > 1, the gather's own wall time and
+gather_check (--verify, on by default there: rank 0 re-renders the frames on one full-frame context
+and says whether the gathered framebuffer is byte-identical to it).
+
+--dump-outputs DIR writes what the last timed step left for its caller as DIR/<name>.npy (rank 0):
+accum (the accumulated framebuffer, H x W x 4, the RGBA8 bytes as float32), trace (N = 1: the last
+frame's trace image, likewise) and stats (float64: segments and triangle tests of the timed steps).
+At most 64 MB in all: an array that does not fit whole is written as a fixed, seeded sample of its
+pixels.  The inputs depend on the arguments only (scene preset, rng_offset = frame index).
 
 Without a launcher (WORLD_SIZE unset) and --gpus N > 1, this process starts the N rank processes itself
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, 127.0.0.1) before anything in it touches a GPU, and
-exits with the first failing rank's status; under a launcher --gpus must equal WORLD_SIZE.  For N > 1
---verify is on by default: rank 0 re-renders the frames on one full-frame context and the line's
-gather_check says whether the gathered framebuffer is byte-identical to it.
+exits with the first failing rank's status; under a launcher --gpus must equal WORLD_SIZE.
 
 A "ray" is one segment = one world_hit call (assets/raytracing.glsl:317), counted exactly on the
 device.  value = segments of all ranks / max-over-ranks wall time of the K timed steps.
@@ -61,16 +71,23 @@ def parse():
     ap.add_argument("--frames-per-launch", type=int, default=64,
                     help="> 1: steps run as hrt_compute_n (compute_n_then_render) with up to this many frames per "
                          "trace launch; 1: one trace + accumulate (+ gather) dispatch per step (compute_then_render)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline and its parity sample, "
+                         "the realtime loop (per_frame_dispatch_ms) and, for N>1, the gather's own time and --verify")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left for its caller as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--verify", action=argparse.BooleanOptionalAction, default=None,
-                    help="N>1 (default on): rank 0 re-renders all frames on one full-frame context and compares "
-                         "the gathered frame byte for byte (gather_check)")
+                    help="with --full, N>1 (default on): rank 0 re-renders all frames on one full-frame context and "
+                         "compares the gathered frame byte for byte (gather_check)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = the library's RCCL gather over xGMI (default); gloo = torch all-gather of the "
                          "local blocks through the host (rehearsal with several ranks on one GPU)")
     ap.add_argument("--realtime-frames", type=int, default=32,
-                    help="after the timed steps: frames of the per-frame dispatch loop (compute_then_render) "
-                         "reported as per_frame_dispatch_ms (0 = skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample length (0 = skip)")
+                    help="with --full, after the timed steps: frames of the per-frame dispatch loop "
+                         "(compute_then_render) reported as per_frame_dispatch_ms (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="with --full: target CPU-baseline sample length (0 = skip)")
     ap.add_argument("--comm-timeout-ms", type=int, default=60000,
                     help="HRT_OPT_COMM_TIMEOUT_MS: a collective (hrt_comm_init, the gather) whose peers do not "
                          "arrive within this fails on every rank instead of hanging")
@@ -78,6 +95,8 @@ def parse():
                     help="rocprofv3 PMC record of this build and workload (tools/pmc.sh); default "
                          "profiles/pmc_traffic.json for island, profiles/pmc_traffic_<scene>.json otherwise")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.pmc_json is None:
         a.pmc_json = os.path.join(ROOT, "profiles", "pmc_traffic.json" if a.scene == "island"
                                   else f"pmc_traffic_{a.scene}.json")
@@ -183,6 +202,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.verify is None:
         args.verify = world > 1
+    args.verify = args.verify and args.full
 
     import torch
     import torch.distributed as dist
@@ -288,22 +308,28 @@ def main():
 
     st = ctx.stats()
     segs, tests = st.segments, st.tri_tests
-    # the gather's own wall time (one more present after the timed region: the library's status
+    # --full: the gather's own wall time (one more present after the timed region: the library's status
     # all-reduce + ncclGather + row assembly, or the gloo all-gather)
     gather_ms = None
-    if dist_on:
+    if dist_on and args.full:
         dist.barrier()
         tg = time.perf_counter()
         present()
         ctx.synchronize()
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - tg) * 1e3
-    last_trace = ctx.read(_lib.IMG_TRACE, _lib.FMT_RGBA8) if world == 1 else None
-    gathered = full.cpu().numpy() if (dist_on and rank == 0 and full is not None) else None
-    # the realtime loop (compute_then_render per frame, src/main.rs:41-57): consecutive traces overlap
+    cpu_base = world == 1 and args.full and args.cpu_seconds > 0
+    last_trace = ctx.read(_lib.IMG_TRACE, _lib.FMT_RGBA8) if world == 1 and (cpu_base or args.dump_outputs) else None
+    gathered = (full.cpu().numpy() if (dist_on and rank == 0 and full is not None
+                                       and (args.verify or args.dump_outputs)) else None)
+    # --dump-outputs: the accumulated framebuffer as the last timed step left it (gathered when N > 1)
+    accum = None
+    if args.dump_outputs and rank == 0:
+        accum = gathered if dist_on else ctx.read(_lib.IMG_ACCUM, _lib.FMT_RGBA8)
+    # --full: the realtime loop (compute_then_render per frame, src/main.rs:41-57): consecutive traces overlap
     # on the context's trace lanes (three by default); measured after the timed steps, separately reported
     rt_ms = None
-    if args.realtime_frames > 0 and fpl > 1:
+    if args.full and args.realtime_frames > 0 and fpl > 1:
         saved = fpl
         fpl = 1
         steps(6)  # untimed: every trace lane's first (probe-planned) trace
@@ -336,6 +362,14 @@ def main():
         segs_all, tests_all = int(c[0]), int(c[1])
     else:
         kern_ms_max, segs_all, tests_all = kern_ms, segs, tests
+
+    if accum is not None:
+        # what the last timed step left for its caller: the framebuffer, the last frame's trace image
+        # (N = 1) and the exact counters of the timed steps (all ranks')
+        outs = {"stats": np.array([segs_all, tests_all], np.float64), "accum": accum}
+        if last_trace is not None:
+            outs["trace"] = last_trace
+        dump_outputs(args.dump_outputs, outs)
 
     if rank == 0:
         ms_per_step = elapsed * 1e3 / args.steps
@@ -409,7 +443,7 @@ def main():
                              "traffic_over_algorithmic": (round(roof["traffic"] / algo_bytes, 2)
                                                           if roof["traffic"] else None)},
         }
-        if world == 1 and args.cpu_seconds > 0:
+        if cpu_base:
             line["cpu_baseline"], line["parity_sample"] = cpu_baseline(args, raytrace, camera, last_frame,
                                                                        last_trace)
         if ranks is not None:
@@ -423,6 +457,26 @@ def main():
     ctx.close()
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # (of array data: the files stay under 64 MB with their headers)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each array as path/<name>.npy: float64 stays, everything else as float32.  An array that
+    does not fit into what is left of the budget is written as a sample of its pixels (rows of its last
+    axis), chosen by a fixed seed from its shape alone -- the same pixels in every run and build."""
+    os.makedirs(path, exist_ok=True)
+    left = budget
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.nbytes > left:
+            px = a.reshape(-1, a.shape[-1])
+            keep = left // (px.shape[1] * a.itemsize)
+            a = px[np.sort(np.random.default_rng(0).choice(len(px), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def pmc_roofline(args, world, kernel_sym, kern_ms, tests_per_frame, row_frac, launch_frames):

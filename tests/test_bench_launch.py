@@ -70,6 +70,38 @@ def test_bench_refuses_more_rccl_ranks_than_gpus():
     assert "metric" not in r.stdout
 
 
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: float64 stays, the rest becomes float32; what fits is written whole, what does
+    not as the same seeded sample of its pixels in every run, and the arrays stay within the budget."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    accum = rng.integers(0, 256, (9, 7, 4), dtype=np.uint8)
+    trace = rng.integers(0, 256, (9, 7, 4), dtype=np.uint8)
+    outs = {"stats": np.array([2.0 ** 40 + 1, 3.0]), "accum": accum, "trace": trace}
+    budget = 16 + accum.size * 4 + 10 * 16 + 5  # stats and accum whole, 10 pixels of trace
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs, budget=budget)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in outs}
+    assert got["stats"].dtype == np.float64 and list(got["stats"]) == [2.0 ** 40 + 1, 3.0]
+    assert got["accum"].dtype == np.float32 and np.array_equal(got["accum"], accum)
+    assert got["trace"].dtype == np.float32 and got["trace"].shape == (10, 4)
+    assert sum(a.nbytes for a in got.values()) <= budget
+    px = {tuple(p) for p in trace.reshape(-1, 4)}
+    assert all(tuple(p) in px for p in got["trace"].astype(np.uint8))
+    for n in outs:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))
+    assert bench.DUMP_BUDGET_BYTES < 64_000_000
+
+
+def test_plain_run_options():
+    """--full and --dump-outputs exist and are off by default; --steps 0 is refused."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
 def test_assemble_ranks_says_whether_rccl_saw_every_rank():
     """The N > 1 line's "ranks" object: the communicator's world as each rank's
     library reports it (hrt_comm_info), the rank ids, and each rank's kernel and gather times."""

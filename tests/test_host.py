@@ -11,7 +11,8 @@ import pyoracle as O
 import epq_raytracer_amd as E
 from epq_raytracer_amd import _lib
 
-REF_ASSETS = "/root/reference/assets"
+# the reference's four .obj scenes, stored with the suite (tests/golden/assets)
+REF_ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assets")
 CAMERAS = [(name, *E.PRESETS[name]()) for name in E.PRESETS]
 
 
@@ -127,7 +128,6 @@ def _parse_obj_py(path):
     return [(n, V[np.array(f, np.int64)].reshape(-1, 3, 3)) for n, f in objs]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference checkout not mounted")
 @pytest.mark.parametrize("name", ["Cube", "box", "island", "Cave"])
 def test_obj_loader_and_bundled_asset(name):
     path = os.path.join(REF_ASSETS, f"{name}.obj")

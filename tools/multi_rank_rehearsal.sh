@@ -4,6 +4,6 @@
 set -o pipefail
 OUT=gpurun_out/${1:-rehearsal}; mkdir -p $OUT
 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --dist-backend gloo --verify --spp 16 \
+  --master-port 29517 bench.py --full --gpus 2 --steps 2 --warmup 1 --dist-backend gloo --verify --spp 16 \
   > $OUT/n2.json 2> $OUT/n2.err || { echo "rehearsal failed"; tail -30 $OUT/n2.err; exit 1; }
 cat $OUT/n2.json

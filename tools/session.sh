@@ -26,6 +26,6 @@ if [ -n "$DIAG" ]; then
   grep -h primary_iters $OUT/diag_island.jsonl $OUT/diag_cave.jsonl | python3 -c "import sys,json; [print({k: d.get(k) for k in ('primary_iters','sky_items','sky_cycles','primary_cycles','bounce_cycles','shade_cycles','primary_lane_use','live_lane_use','loop_iters','bounce_lanes_per_iter')}) for d in map(json.loads, sys.stdin)]"
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 600 python3 bench.py --cpu-seconds 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
+  timeout -k 10 600 python3 bench.py --full --cpu-seconds 5 > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -30 $OUT/bench.err; exit 1; }
   cat $OUT/bench.json
 fi
