@@ -67,6 +67,15 @@ class Stats(ctypes.Structure):
                 ("reserved", c_uint32)]
 
 
+class PresentInfo(ctypes.Structure):
+    """hrt_present_info: the target of one present pass (24 bytes)."""
+
+    _fields_ = [("image_id", c_uint32), ("format", c_uint32), ("width", c_uint32), ("height", c_uint32),
+                ("pitch", c_uint32), ("flags", c_uint32)]
+
+
+assert ctypes.sizeof(PresentInfo) == 24
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 HRT_OK = 0
 STATUS_NAMES = {0: "HRT_OK", 1: "HRT_ERR_INVALID_ARGUMENT", 2: "HRT_ERR_NO_DEVICE", 3: "HRT_ERR_OUT_OF_MEMORY",
@@ -76,6 +85,8 @@ MODE_RGBA8, MODE_RGBA32F = 0, 1
 IMG_TRACE, IMG_ACCUM = 0, 1
 IMG_LOCAL = 0x100  # flag: this context's local rows, never the collective gather
 FMT_RGBA8, FMT_RGBA32F = 0, 1
+PRESENT_B8G8R8A8, PRESENT_R8G8B8A8 = 0, 1  # hrt_present_format
+PRESENT_RING = 8  # present tickets in flight per context
 OPT_KERNEL_VARIANT, OPT_COUNTERS, OPT_SECONDARY_BATCH, OPT_BVH_LEAF_SIZE = 1, 2, 3, 4
 OPT_SPLIT, OPT_SPLIT_FACTOR, OPT_PRIORITY, OPT_GRID_CUS, OPT_COOP, OPT_WQ_NODE_CAP, OPT_PROBE = 5, 6, 7, 8, 9, 10, 11
 OPT_FRAMES_PER_LAUNCH, OPT_OVERLAP, OPT_BUSY_SPLIT, OPT_BVH_WIDTH, OPT_WQ_NODE_RADIUS = 12, 13, 14, 15, 16
@@ -128,7 +139,8 @@ EXPORTED_SYMBOLS = (
     "hrt_abi_version", "hrt_build_id", "hrt_debug_build", "hrt_debug_check_guards", "hrt_create", "hrt_destroy", "hrt_set_scene", "hrt_trace", "hrt_accumulate", "hrt_compute_n",
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
-    "hrt_import_external_memory", "hrt_release_external_memory", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
+    "hrt_import_external_memory", "hrt_release_external_memory",
+    "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs",
     "hrt_stream", "hrt_release_caches", "hrt_last_error", "hrt_comm_unique_id", "hrt_comm_init", "hrt_comm_init_all", "hrt_comm_info",
     "hrt_host_create_rays", "hrt_host_ray_grid", "hrt_host_view_matrix", "hrt_host_transform_meshes",
@@ -193,6 +205,10 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_read_rays": (c_int32, [P, P, c_uint32]),
         "hrt_import_external_memory": (c_int32, [P, c_int32, c_uint64, c_uint64, c_uint64, POINTER(c_void_p)]),
         "hrt_release_external_memory": (c_int32, [P, P]),
+        "hrt_present": (c_int32, [P, POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
+        "hrt_accumulate_present": (c_int32, [P, c_uint32, POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
+        "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
+        "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),
                                               POINTER(c_uint64)]),
         "hrt_debug_unmap_memory": (c_int32, [P, c_uint64]),

@@ -2,9 +2,11 @@
 
 The reference's frame counter is both the accumulator weight and the RNG ``rng_offset``:
 ``open`` clears the trace image and the accumulator with frame 0 (:128-129) and leaves frame = 1,
-so the first traced frame uses rng_offset = 1 (:139, :181, :193).  Presentation
-(RenderPassOverFrame, src/texture_draw_pipeline.rs) is out of scope: ``render`` hooks receive the
-accumulated Image and may read it back.
+so the first traced frame uses rng_offset = 1 (:139, :181, :193).  ``render`` hooks receive the
+accumulated Image: they may read it back, or present it without a host wait through
+``pipeline.RenderPassOverFrame(ctx, fmt).render(image, PresentTarget(...))`` (hrt_present: the
+reference's src/texture_draw_pipeline.rs pass into caller memory, returning a completion ticket).
+The window and swapchain themselves stay outside this package.
 """
 from __future__ import annotations
 

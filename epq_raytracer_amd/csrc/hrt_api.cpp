@@ -430,6 +430,8 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->frame_stack);
   free_dev(ctx, ctx->ring);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
+  for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
+    if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) {
     if (ctx->staging.buf[i]) (void)hipHostFree(ctx->staging.buf[i]);
     if (ctx->staging.ev[i]) (void)hipEventDestroy(ctx->staging.ev[i]);
@@ -1122,6 +1124,167 @@ hrt_status copy_frame_out(hrt_context* ctx, const void* src, size_t npix, uint32
 }
 }  // namespace hrt
 
+// ---- the present pass (RenderPassOverFrame::render, src/texture_draw_pipeline.rs:96-157) ------------
+namespace {
+
+constexpr uint32_t kPresentMaxDim = 16384;
+
+// Whether a kernel of this context may write [dst, dst + bytes): the range lies inside one of the
+// context's imports, or its first and last byte are device memory of the context's device, managed
+// memory or registered (pinned) host memory.  Pageable host memory is not: with XNACK off a kernel's
+// store to it is a GPU fault, not an error code, so it has to be refused here.
+bool present_writable(hrt_context* ctx, const void* dst, uint64_t bytes) {
+  const uintptr_t a = (uintptr_t)dst;
+  if (bytes == 0 || bytes - 1 > UINTPTR_MAX - a) return false;
+  for (const auto& im : ctx->imports) {
+    const uintptr_t b = (uintptr_t)im.ptr;
+    if (a >= b && bytes <= im.bytes && a - b <= im.bytes - bytes) return true;
+  }
+  for (const uint64_t off : {(uint64_t)0, bytes - 1}) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, static_cast<const char*>(dst) + off) != hipSuccess) {
+      (void)hipGetLastError();  // (an unknown pointer is not a sticky error)
+      return false;
+    }
+    const bool ok = (at.type == hipMemoryTypeDevice && at.device == ctx->device) || at.type == hipMemoryTypeManaged ||
+                    at.type == hipMemoryTypeHost;
+    if (!ok) return false;
+  }
+  return true;
+}
+
+// Every argument check of hrt_present / hrt_accumulate_present, on the host, before anything is enqueued.
+hrt_status check_present(hrt_context* ctx, const hrt_present_info* info, const void* dst, uint64_t dst_bytes,
+                         const uint64_t* ticket, bool accum_only, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!info || !dst || !ticket) return bad("null info, destination or ticket");
+  if (ctx->part_count > 1 || ctx->comm)
+    return bad("a partitioned or communicator-joined context cannot present (the gathered present is not implemented)");
+  if (info->image_id != HRT_IMG_ACCUM && (accum_only || info->image_id != HRT_IMG_TRACE))
+    return bad(accum_only ? "image_id must be HRT_IMG_ACCUM" : "unknown image id");
+  if (info->format != HRT_PRESENT_B8G8R8A8 && info->format != HRT_PRESENT_R8G8B8A8) return bad("unknown present format");
+  if (info->flags != 0) return bad("flags must be 0");
+  if (info->width == 0 || info->height == 0 || info->width > kPresentMaxDim || info->height > kPresentMaxDim)
+    return bad("target width / height must be 1..16384");
+  if (info->pitch % 4 != 0 || (uint64_t)info->pitch < (uint64_t)info->width * 4)
+    return bad("pitch must be a multiple of 4 and at least width * 4");
+  if ((uintptr_t)dst % 4 != 0) return bad("destination must be 4-byte aligned");
+  const uint64_t need = (uint64_t)(info->height - 1) * info->pitch + (uint64_t)info->width * 4;
+  if (dst_bytes < need) return bad("destination smaller than (height - 1) * pitch + width * 4");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if (!present_writable(ctx, dst, need))
+    return bad("destination is not an import of this context nor device, managed or registered host memory");
+  return HRT_OK;
+}
+
+// The event of the next ticket: created on first use; when all kPresentRing tickets before it may still
+// be in flight, the oldest (whose event this is) is waited for first.
+hrt_status ticket_begin(hrt_context* ctx, hipEvent_t* ev) {
+  hipEvent_t& e = ctx->present_ev[ctx->present_issued % hrt_context::kPresentRing];
+  if (!e)
+    HRT_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  else
+    HRT_HIP(ctx, hipEventSynchronize(e));
+  *ev = e;
+  return HRT_OK;
+}
+
+hrt_status ticket_end(hrt_context* ctx, hipEvent_t ev, uint64_t* ticket) {
+  HRT_HIP(ctx, hipEventRecord(ev, ctx->stream));
+  *ticket = ++ctx->present_issued;
+  return HRT_OK;
+}
+
+hrt::PresentTarget present_target(const hrt_present_info* info, void* dst) {
+  return {static_cast<unsigned char*>(dst), info->width, info->height, info->pitch,
+          info->format == HRT_PRESENT_B8G8R8A8 ? 1u : 0u};
+}
+
+// The pass itself on ctx->stream, after everything that wrote the image (arguments already checked).
+hrt_status enqueue_present(hrt_context* ctx, const hrt_present_info* info, void* dst) {
+  const void* src = hrt::local_image(ctx, info->image_id);
+  if (!src) return fail(ctx, HRT_ERR_HIP, "hrt_present: lane wait failed");
+  const bool f32 = ctx->mode != HRT_MODE_RGBA8;
+  HRT_HIP(ctx, hrt::launch_present(f32 ? nullptr : static_cast<const uint32_t*>(src),
+                                   f32 ? static_cast<const float4*>(src) : nullptr, ctx->width, ctx->local_rows,
+                                   present_target(info, dst), ctx->stream));
+  if (info->image_id != HRT_IMG_TRACE) return HRT_OK;
+  // the trace image's next writer follows the pass: its lane's next trace, and -- when the image is a
+  // slot of the deferred combiner's ring -- the slot's next trace, which waits for fold_done
+  if (ctx->cur_slot >= 0) {
+    HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+    ctx->fold_set = true;
+  }
+  return hrt::release_lane(ctx, ctx->cur_lane);
+}
+
+}  // namespace
+
+extern "C" hrt_status hrt_present(hrt_context* ctx, const hrt_present_info* info, void* dst, uint64_t dst_bytes,
+                                  uint64_t* ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = check_present(ctx, info, dst, dst_bytes, ticket, false, "hrt_present");
+  if (st != HRT_OK) return st;
+  hipEvent_t ev = nullptr;
+  if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  if ((st = enqueue_present(ctx, info, dst)) != HRT_OK) return st;
+  return ticket_end(ctx, ev, ticket);
+}
+
+extern "C" hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, const hrt_present_info* info, void* dst,
+                                             uint64_t dst_bytes, uint64_t* ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = check_present(ctx, info, dst, dst_bytes, ticket, true, "hrt_accumulate_present");
+  if (st != HRT_OK) return st;
+  hipEvent_t ev = nullptr;
+  if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  if (ctx->defer || info->width != ctx->width || info->height != ctx->local_rows) {
+    // the two passes: a deferred combine is folded by the present, a scaled target samples the new accumulator
+    if ((st = hrt_accumulate(ctx, frame)) != HRT_OK) return st;
+    if ((st = enqueue_present(ctx, info, dst)) != HRT_OK) return st;
+    return ticket_end(ctx, ev, ticket);
+  }
+  // hrt_accumulate's immediate combine with the target's pixel written by the same kernel
+  const int l = ctx->cur_lane;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
+  void* img = hrt::trace_image(ctx);
+  HRT_HIP(ctx, hrt::launch_accumulate_present(ctx->accum8, ctx->accum8 ? static_cast<uint32_t*>(img) : nullptr,
+                                              ctx->accum32, ctx->accum32 ? static_cast<float4*>(img) : nullptr,
+                                              ctx->width, ctx->local_rows, frame, present_target(info, dst), ctx->stream));
+  ctx->accumulates++;
+  if ((st = hrt::release_lane(ctx, l)) != HRT_OK) return st;
+  return ticket_end(ctx, ev, ticket);
+}
+
+extern "C" hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done) {
+  if (!ctx || !done) return HRT_ERR_INVALID_ARGUMENT;
+  if (ticket == 0 || ticket > ctx->present_issued)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_present_done: no such ticket");
+  *done = 1;  // a ticket older than the ring was waited for when its event was reused
+  if (ctx->present_issued - ticket >= hrt_context::kPresentRing) return HRT_OK;
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  const hipError_t e = hipEventQuery(ctx->present_ev[(ticket - 1) % hrt_context::kPresentRing]);
+  if (e == hipErrorNotReady)
+    *done = 0;
+  else if (e != hipSuccess)
+    return hip_fail(ctx, e, "hipEventQuery");
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_present_wait(hrt_context* ctx, uint64_t ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (ticket == 0 || ticket > ctx->present_issued)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_present_wait: no such ticket");
+  if (ctx->present_issued - ticket >= hrt_context::kPresentRing) return HRT_OK;
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  HRT_HIP(ctx, hipEventSynchronize(ctx->present_ev[(ticket - 1) % hrt_context::kPresentRing]));
+  return HRT_OK;
+}
+
 extern "C" hrt_status hrt_get_layout(const hrt_context* ctx, hrt_layout* out) {
   if (!ctx || !out) return HRT_ERR_INVALID_ARGUMENT;
   out->width = ctx->width;
@@ -1139,7 +1302,7 @@ extern "C" hrt_status hrt_synchronize(hrt_context* ctx) {
   hrt_status st = bind(ctx);
   if (st != HRT_OK) return st;
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // every accumulate has run after a sync
-  return sync_all(ctx);
+  return sync_all(ctx);  // (and every present ticket is done: their events were recorded on ctx->stream)
 }
 
 extern "C" hrt_status hrt_get_stats(hrt_context* ctx, hrt_stats* out) {
@@ -1215,7 +1378,7 @@ extern "C" hrt_status hrt_import_external_memory(hrt_context* ctx, int fd, uint6
     (void)hipDestroyExternalMemory(mem);
     return hip_fail(ctx, e, "hipExternalMemoryGetMappedBuffer");
   }
-  ctx->imports.push_back({mem, ptr});
+  ctx->imports.push_back({mem, ptr, bytes});
   *dev_ptr = ptr;
   return HRT_OK;
 }

@@ -161,8 +161,14 @@ struct hrt_context {
   struct Import {
     hipExternalMemory_t mem;
     void* ptr;
+    uint64_t bytes;  // mapped size (hrt_present accepts a target inside [ptr, ptr + bytes))
   };
   std::vector<Import> imports;           // hrt_import_external_memory (released by hrt_destroy)
+  // Present tickets (hrt_present): ticket t's event is present_ev[(t - 1) % kPresentRing], recorded on
+  // `stream` after the pass; present_issued = the newest ticket.  Events are created on first use.
+  static constexpr uint32_t kPresentRing = 8;
+  hipEvent_t present_ev[kPresentRing] = {};
+  uint64_t present_issued = 0;
   std::vector<hrt::EventPair> event_pool;  // reusable
   std::vector<hrt::EventPair> pending;     // recorded, not yet harvested (a ring of kMaxPending)
   uint64_t traces = 0, accumulates = 0;

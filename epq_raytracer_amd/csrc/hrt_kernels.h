@@ -113,6 +113,19 @@ hipError_t launch_band_records(const uint32_t* off, const uint32_t* band16, uint
                                hipStream_t stream);
 hipError_t launch_accumulate(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32, size_t npix,
                              uint32_t frame, hipStream_t stream);
+// The present pass (hrt_present): the target of width x height pixels of 4 bytes, rows pitch bytes apart
+// (dst 4-byte aligned, pitch a multiple of 4); bgra: bytes 0 and 2 of each pixel swapped.
+struct PresentTarget {
+  unsigned char* dst;
+  uint32_t width, height, pitch, bgra;
+};
+// target(x, y) = the ws x hs image's texel (((2x+1) ws) div (2 width), hs - 1 - ((2y+1) hs) div (2 height)):
+// present_rows at the image's own size, else present_nearest (src8 or src32 set)
+hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws, uint32_t hs, const PresentTarget& t,
+                          hipStream_t stream);
+// launch_accumulate on a w x h image (t of the same size) whose kernel also writes the folded pixel to t
+hipError_t launch_accumulate_present(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32,
+                                     uint32_t w, uint32_t h, uint32_t frame, const PresentTarget& t, hipStream_t stream);
 // Row-tile framebuffer assembly: gathered = parts x local_rows rows (rank-major), frame = height rows of
 // row_words 4-byte words; global row y comes from part (y / row_tile) % parts (hip_raytrace.h partition).
 hipError_t launch_assemble_rows(const uint32_t* gathered, uint32_t* frame, uint32_t row_words, uint32_t height,

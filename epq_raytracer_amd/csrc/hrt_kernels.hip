@@ -3185,6 +3185,90 @@ __global__ __launch_bounds__(256) void f32_to_rgba8(const float4* src, uint32_t*
   dst[i] = unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
 }
 
+// ---- the present pass (RenderPassOverFrame::render, src/texture_draw_pipeline.rs:96-157) ------------
+// The image as the reference's full-target quad draws it: nearest filter, flipped vertically.  One
+// target row per grid.y, so the source row is wave-uniform and the stores of a row stream coalesced.
+// A target pixel is the source's RGBA8 word (an RGBA32F texel converted as f32_to_rgba8 converts it),
+// with bytes 0 and 2 swapped for a B8G8R8A8 target: one v_perm_b32 per word.
+__device__ __forceinline__ uint32_t present_word(uint32_t v, uint32_t bgra) {
+  return bgra ? __builtin_amdgcn_perm(v, v, 0x03000102u) : v;
+}
+__device__ __forceinline__ uint32_t present_load(const uint32_t* s, size_t i) { return s[i]; }
+__device__ __forceinline__ uint32_t present_load(const float4* s, size_t i) {
+  const float4 v = s[i];
+  return unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
+}
+// Target of the image's own size: dst(x, y) = src(x, h - 1 - y).  Four pixels per lane -- one 128-bit
+// load (four float4 loads of an RGBA32F source) and one 128-bit store -- over the row's whole quads
+// while the row of the target and of an RGBA8 source both start on a 16 B boundary (an odd width, pitch
+// or base leaves only some rows there); the row's last w % 4 pixels, and every pixel of a row that
+// does not, go one word per lane.
+template <typename T>
+__global__ __launch_bounds__(256) void present_rows(const T* __restrict__ src, unsigned char* __restrict__ dst, uint32_t w,
+                                                    uint32_t h, uint32_t pitch, uint32_t bgra) {
+  const uint32_t y = blockIdx.y;
+  const T* s = src + (size_t)(h - 1u - y) * w;
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
+  const bool vec = (((uintptr_t)d | (sizeof(T) == 4 ? (uintptr_t)s : (uintptr_t)0)) & 15u) == 0;
+  const uint32_t quads = vec ? w / 4u : 0u;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+  for (uint32_t q = t; q < quads; q += stride) {
+    uint4 v;
+    if constexpr (sizeof(T) == 4) {
+      v = reinterpret_cast<const uint4*>(s)[q];
+    } else {
+      v = make_uint4(present_load(s, 4u * q), present_load(s, 4u * q + 1u), present_load(s, 4u * q + 2u),
+                     present_load(s, 4u * q + 3u));
+    }
+    reinterpret_cast<uint4*>(d)[q] =
+        make_uint4(present_word(v.x, bgra), present_word(v.y, bgra), present_word(v.z, bgra), present_word(v.w, bgra));
+  }
+  for (uint32_t i = quads * 4u + t; i < w; i += stride) d[i] = present_word(present_load(s, i), bgra);
+}
+// Target of another size: sample points at the target's pixel centres, texel = floor of the centre's
+// source coordinate -- the pinned integer rule, 64-bit so that no size overflows:
+//   sx = ((2x+1) ws) div (2 wt),  sy = hs - 1 - ((2y+1) hs) div (2 ht).
+// sy once per row (wave-uniform), sx per lane: coalesced stores, loads gathered along one source row.
+template <typename T>
+__global__ __launch_bounds__(256) void present_nearest(const T* __restrict__ src, uint32_t ws, uint32_t hs,
+                                                       unsigned char* __restrict__ dst, uint32_t wt, uint32_t ht,
+                                                       uint32_t pitch, uint32_t bgra) {
+  const uint32_t y = blockIdx.y;
+  const uint32_t sy = hs - 1u - (uint32_t)(((2ull * y + 1ull) * hs) / (2ull * ht));
+  const T* s = src + (size_t)sy * ws;
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
+  for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < wt; x += gridDim.x * 256u) {
+    const uint32_t sx = (uint32_t)(((2ull * x + 1ull) * ws) / (2ull * wt));
+    d[x] = present_word(present_load(s, sx), bgra);
+  }
+}
+// hrt_accumulate_present at the image's own size: accumulate_rgba8 / accumulate_rgba32f (the same
+// combine_* arithmetic, 256 threads, the UNORM8 table in LDS) whose thread also writes the folded pixel
+// to the flipped target row -- the accumulator is not read again by a present pass (w * h <= 2^28).
+__global__ __launch_bounds__(256) void accumulate_present_rgba8(uint32_t* cur, const uint32_t* nw, uint32_t w, uint32_t h,
+                                                                uint32_t frame, unsigned char* __restrict__ dst,
+                                                                uint32_t pitch, uint32_t bgra) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  __shared__ float tab[256];
+  unorm8_table(tab);
+  if (i >= w * h) return;
+  const uint32_t v = combine_rgba8_fast(frame == 0 ? 0u : cur[i], nw[i], frame, tab);
+  cur[i] = v;
+  const uint32_t y = i / w, x = i - y * w;
+  reinterpret_cast<uint32_t*>(dst + (size_t)(h - 1u - y) * pitch)[x] = present_word(v, bgra);
+}
+__global__ __launch_bounds__(256) void accumulate_present_rgba32f(float4* cur, const float4* nw, uint32_t w, uint32_t h,
+                                                                  uint32_t frame, unsigned char* __restrict__ dst,
+                                                                  uint32_t pitch, uint32_t bgra) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= w * h) return;
+  const float4 v = combine_rgba32f(frame == 0 ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : cur[i], nw[i], frame);
+  cur[i] = v;
+  const uint32_t y = i / w, x = i - y * w;
+  const uint32_t px = unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
+  reinterpret_cast<uint32_t*>(dst + (size_t)(h - 1u - y) * pitch)[x] = present_word(px, bgra);
+}
+
 // Row-tile framebuffer assembly after the gather: global row y lives in part
 // (y / row_tile) % parts at local row (y / row_tile / parts) * row_tile + y % row_tile.  One 4-byte word
 // per lane; grid.y = rows, so the row arithmetic is wave-uniform and both sides stream coalesced.
@@ -3628,6 +3712,42 @@ hipError_t launch_accumulate(uint32_t* cur8, const uint32_t* new8, float4* cur32
     accumulate_rgba8<<<blocks_for(npix), 256, 0, stream>>>(cur8, new8, npix, frame);
   else
     accumulate_rgba32f<<<blocks_for(npix), 256, 0, stream>>>(cur32, new32, npix, frame);
+  return hipGetLastError();
+}
+
+template <typename T>
+static void present_launch(const T* src, uint32_t ws, uint32_t hs, const PresentTarget& t, hipStream_t stream) {
+  if (t.width == ws && t.height == hs) {  // a lane moves four pixels; rows off the 16 B grid loop
+    const dim3 g(((t.width + 3) / 4 + 255) / 256, t.height, 1);
+    present_rows<T><<<g, 256, 0, stream>>>(src, t.dst, ws, hs, t.pitch, t.bgra);
+  } else {
+    const dim3 g((t.width + 255) / 256, t.height, 1);
+    present_nearest<T><<<g, 256, 0, stream>>>(src, ws, hs, t.dst, t.width, t.height, t.pitch, t.bgra);
+  }
+}
+
+hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws, uint32_t hs, const PresentTarget& t,
+                          hipStream_t stream) {
+  // (grid.y = target rows; the checks of hrt_present, repeated where the launch is shaped)
+  if (ws == 0 || hs == 0 || t.width == 0 || t.height == 0 || t.height > 65535u || t.pitch / 4 < t.width || !t.dst)
+    return hipErrorInvalidValue;
+  if (src8)
+    present_launch(src8, ws, hs, t, stream);
+  else
+    present_launch(src32, ws, hs, t, stream);
+  return hipGetLastError();
+}
+
+hipError_t launch_accumulate_present(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32,
+                                     uint32_t w, uint32_t h, uint32_t frame, const PresentTarget& t, hipStream_t stream) {
+  if (w == 0 || h == 0 || t.width != w || t.height != h || (uint64_t)w * h > (1ull << 28) || t.pitch / 4 < w || !t.dst)
+    return hipErrorInvalidValue;
+  if (cur8)
+    accumulate_present_rgba8<<<blocks_for((size_t)w * h), 256, 0, stream>>>(cur8, new8, w, h, frame, t.dst, t.pitch,
+                                                                           t.bgra);
+  else
+    accumulate_present_rgba32f<<<blocks_for((size_t)w * h), 256, 0, stream>>>(cur32, new32, w, h, frame, t.dst, t.pitch,
+                                                                             t.bgra);
   return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@ Mapping to the reference:
   RayTracePipeline.init     src/raytrace_pipeline.rs:190-213 (-> hrt_trace, init = 1)
   RayTracePipeline.push_constants  dispatch :216-266 (124-byte block :243-257)
   DiffusePipeline.next_frame       src/diffuse.rs:73-101 (-> hrt_accumulate)
+  RenderPassOverFrame.render       src/texture_draw_pipeline.rs:96-157 (-> hrt_present)
 """
 from __future__ import annotations
 
@@ -224,6 +225,42 @@ class HrtContext:
         self._check(self.lib.hrt_read_image(self.handle, image_id, fmt, ctypes.c_void_p(dst_ptr), nbytes),
                     "hrt_read_image")
 
+    # ---- the present pass (hrt_present) ----
+
+    def _present_info(self, image_id, width, height, pitch, fmt) -> _lib.PresentInfo:
+        width, height = int(width), int(height)
+        return _lib.PresentInfo(int(image_id), int(fmt), width, height, width * 4 if pitch is None else int(pitch), 0)
+
+    def present(self, image_id: int, dst_ptr: int, nbytes: int, width: int, height: int, pitch: Optional[int] = None,
+                fmt: int = _lib.PRESENT_B8G8R8A8) -> int:
+        """hrt_present: enqueue the image as the reference's flipped, nearest-sampled quad over the
+        width x height target at device pointer dst_ptr (rows pitch bytes apart, default width * 4) and
+        return its ticket without waiting (at most 8 in flight)."""
+        info, t = self._present_info(image_id, width, height, pitch, fmt), ctypes.c_uint64()
+        self._check(self.lib.hrt_present(self.handle, ctypes.byref(info), ctypes.c_void_p(dst_ptr), int(nbytes),
+                                         ctypes.byref(t)), "hrt_present")
+        return t.value
+
+    def accumulate_present(self, frame: int, dst_ptr: int, nbytes: int, width: int, height: int,
+                           pitch: Optional[int] = None, fmt: int = _lib.PRESENT_B8G8R8A8) -> int:
+        """hrt_accumulate_present: accumulate(frame) and present(IMG_ACCUM, ...) in one call (one kernel
+        when the target has the image's size and combines are not deferred); returns the ticket."""
+        info, t = self._present_info(_lib.IMG_ACCUM, width, height, pitch, fmt), ctypes.c_uint64()
+        self._check(self.lib.hrt_accumulate_present(self.handle, int(frame) & 0xFFFFFFFF, ctypes.byref(info),
+                                                    ctypes.c_void_p(dst_ptr), int(nbytes), ctypes.byref(t)),
+                    "hrt_accumulate_present")
+        return t.value
+
+    def present_done(self, ticket: int) -> bool:
+        """Whether the present pass of `ticket` has finished (a poll)."""
+        done = ctypes.c_uint32()
+        self._check(self.lib.hrt_present_done(self.handle, int(ticket), ctypes.byref(done)), "hrt_present_done")
+        return bool(done.value)
+
+    def present_wait(self, ticket: int):
+        """Block until the present pass of `ticket` has finished."""
+        self._check(self.lib.hrt_present_wait(self.handle, int(ticket)), "hrt_present_wait")
+
     def check_guards(self):
         """libhip_raytrace_debug.so: (guarded device buffers, buffers whose guard bands were overwritten)."""
         n, bad = ctypes.c_uint32(), ctypes.c_uint32()
@@ -294,6 +331,37 @@ class Image:
         if transport == _lib.COMM_NONE:
             return self.ctx.read(self.image_id, fmt)
         return self.ctx.read_frame(self.image_id, fmt, root=transport != _lib.COMM_RCCL or rank == 0)
+
+
+@dataclass
+class PresentTarget:
+    """The memory a frame is presented into (the reference's swapchain image view): ``ptr`` is a device
+    pointer a kernel may write (an import of the context, device, managed or registered host memory),
+    ``nbytes`` the bytes that may be written from it."""
+    ptr: int
+    nbytes: int
+    width: int
+    height: int
+    pitch: Optional[int] = None  # bytes per row; None = width * 4
+    format: int = _lib.PRESENT_B8G8R8A8
+
+
+class RenderPassOverFrame:
+    """src/texture_draw_pipeline.rs:96-157 on the HIP context: the image drawn as a nearest-sampled,
+    vertically flipped quad over the whole target (hrt_present)."""
+
+    def __init__(self, ctx: HrtContext, output_format: int = _lib.PRESENT_B8G8R8A8):
+        self.ctx, self.output_format = ctx, int(output_format)
+
+    def render(self, view: Image, target: PresentTarget) -> int:
+        """Enqueues the pass after the work issued so far (the reference's before_future) and returns
+        its ticket (the after_future): wait with ctx.present_wait, poll with ctx.present_done."""
+        if view.ctx is not self.ctx:
+            raise ValueError("view must be an image of the render pass's context")
+        if target.format != self.output_format:
+            raise ValueError("the target's format differs from the render pass's output format")
+        return self.ctx.present(view.image_id, target.ptr, target.nbytes, target.width, target.height, target.pitch,
+                                target.format)
 
 
 # ---- pipelines ---------------------------------------------------------------------------------

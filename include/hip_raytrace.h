@@ -14,6 +14,8 @@
  *   hrt_accumulate   DiffusePipeline::next_frame src/diffuse.rs:73-101 (-> dispatch :103-136)
  *   hrt_read_image   RayTracePipeline::image / DiffusePipeline::image  src/raytrace_pipeline.rs:156, src/diffuse.rs:69
  *                    (on a row-tile partition with a communicator: the RCCL framebuffer gather, hrt_comm_*)
+ *   hrt_present      RenderPassOverFrame::render src/texture_draw_pipeline.rs:96-157 (the accumulated image as a
+ *                    nearest-sampled, vertically flipped quad over the B8G8R8A8_UNORM target, src/raytracing_app.rs:104-109)
  *   hrt_synchronize  then_signal_fence_and_flush().unwrap() + fence wait  src/raytrace_pipeline.rs:179-183
  *   hrt_last_error   the .unwrap() panics (every Vulkan call in src/raytrace_pipeline.rs / src/diffuse.rs)
  *
@@ -39,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6 (r06): hrt_release_caches; HRT_DEBUG_OPT_STACK_LIMIT.
+/* 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
+ * hrt_present_info, hrt_present, hrt_accumulate_present, hrt_present_done, hrt_present_wait.
+ * 6 (r06): hrt_release_caches; HRT_DEBUG_OPT_STACK_LIMIT.
  * 5 (r05): HRT_DIAG_WQ_STEPS_* / WQ_MEMBERS (HRT_NUM_DIAG 29), HRT_DEBUG_OPT_TIMELINE + hrt_debug_timeline.
  * 4 (r04): hrt_debug_wq_protocol; hrt_stats.last_frames; HRT_DIAG_SKY_* / PRIMARY_LANES / LOOP_ITERS /
  * LIVE_LANES (HRT_NUM_DIAG 24).
@@ -173,6 +177,21 @@ typedef struct hrt_stats {
   uint32_t reserved;
 } hrt_stats;
 
+/* The present pass (hrt_present): the byte order of a target pixel. */
+typedef enum hrt_present_format {
+  HRT_PRESENT_B8G8R8A8 = 0, /* the reference's swapchain format (src/raytracing_app.rs:104-109) */
+  HRT_PRESENT_R8G8B8A8 = 1  /* the image's own byte order */
+} hrt_present_format;
+
+/* The target of one present pass: width x height pixels of 4 bytes, rows pitch bytes apart. */
+typedef struct hrt_present_info {
+  uint32_t image_id;      /* HRT_IMG_ACCUM or HRT_IMG_TRACE */
+  uint32_t format;        /* hrt_present_format */
+  uint32_t width, height; /* target size in pixels, each 1..16384 */
+  uint32_t pitch;         /* bytes per target row: >= width*4, a multiple of 4 */
+  uint32_t flags;         /* must be 0 */
+} hrt_present_info;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -196,6 +215,9 @@ HRT_STATIC_ASSERT(sizeof(hrt_stats) == 64 && offsetof(hrt_stats, last_trace_ms) 
                       offsetof(hrt_stats, wave_steps) == 40 && offsetof(hrt_stats, last_kernel) == 48 &&
                       offsetof(hrt_stats, last_frames) == 56,
                   "hrt_stats: 64 bytes since ABI 4");
+HRT_STATIC_ASSERT(sizeof(hrt_present_info) == 24 && offsetof(hrt_present_info, pitch) == 16 &&
+                      offsetof(hrt_present_info, flags) == 20,
+                  "hrt_present_info");
 
 typedef struct hrt_context hrt_context;
 
@@ -484,6 +506,46 @@ hrt_status hrt_read_rays(hrt_context* ctx, hrt_ray* out, uint32_t n);
 hrt_status hrt_import_external_memory(hrt_context* ctx, int fd, uint64_t size, uint64_t offset, uint64_t bytes,
                                       void** dev_ptr);
 hrt_status hrt_release_external_memory(hrt_context* ctx, void* dev_ptr);
+
+/* ---- the present pass (RenderPassOverFrame::render, src/texture_draw_pipeline.rs:96-157) -------------
+ * Writes image info->image_id of the context (Ws x Hs) into the caller's target (info->width x
+ * info->height pixels, rows info->pitch bytes apart) as the reference's full-target quad does: nearest
+ * filter, flipped vertically (its NDC (-1,-1), the target's top-left, maps to tex (0,1); :28-50), not
+ * horizontally.  Target pixel (x, y) takes source texel
+ *     sx = ((2x+1) Ws) div (2 Wt),   sy = Hs - 1 - ((2y+1) Hs) div (2 Ht)        (64-bit intermediates)
+ * which is dst(x, y) = src(x, Hs-1-y) at equal sizes (DESIGN.md §2 pins the rule, texel edges included).
+ * HRT_PRESENT_B8G8R8A8 swaps bytes 0 and 2 of each RGBA8 pixel, HRT_PRESENT_R8G8B8A8 copies it; an
+ * HRT_MODE_RGBA32F image is converted channel by channel as hrt_read_image(HRT_FMT_RGBA8) converts it.
+ * Bytes of a target row beyond width*4 (pitch padding) are not written.
+ *
+ * Non-blocking: the pass is enqueued on the context's stream after the work issued so far (deferred
+ * combines are folded first; HRT_IMG_TRACE joins and releases the current trace lane like hrt_read_image)
+ * and the call returns.  Work issued afterwards is ordered after it, so the target holds the image as
+ * of the call whatever is queued behind.  *ticket receives the pass's completion ticket: tickets count
+ * up from 1 per context, each a HIP event recorded after the pass.  At most 8 are in flight: a call
+ * that finds all 8 unfinished first waits for the oldest.  hrt_synchronize completes every ticket.
+ *
+ * dst must be memory a kernel may write: inside an import of this context
+ * (hrt_import_external_memory), or device, managed or registered (pinned) host memory as
+ * hipPointerGetAttributes reports it; dst 4-byte aligned; dst_bytes >= (height-1)*pitch + width*4.
+ * Anything else -- pageable host memory included -- is HRT_ERR_INVALID_ARGUMENT, decided on the host
+ * before anything is enqueued.
+ *
+ * A context of a row-tile partition (part_count > 1) or joined to a communicator is rejected: the
+ * gathered present is a follow-up. */
+hrt_status hrt_present(hrt_context* ctx, const hrt_present_info* info, void* dst, uint64_t dst_bytes,
+                       uint64_t* ticket);
+/* hrt_accumulate(ctx, frame) followed by hrt_present(ctx, info, ...) with info->image_id ==
+ * HRT_IMG_ACCUM (any other id is rejected), byte for byte; hrt_stats.accumulates counts it once.  When
+ * the target has the image's size and HRT_OPT_DEFER_COMBINE is off, both run as one kernel that folds
+ * the pixel, writes the accumulator and writes the target; otherwise as the two passes. */
+hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, const hrt_present_info* info, void* dst,
+                                  uint64_t dst_bytes, uint64_t* ticket);
+/* *done = 1 when the pass of `ticket` has finished, else 0 (a poll).  Ticket 0 or one never issued:
+ * HRT_ERR_INVALID_ARGUMENT.  A ticket more than 8 behind the newest is done. */
+hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done);
+/* Blocks until the pass of `ticket` has finished. */
+hrt_status hrt_present_wait(hrt_context* ctx, uint64_t ticket);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

@@ -13,6 +13,7 @@
  *   RayTracerSettings                      src/raytracing_app.rs:17-29
  *   RayTracePipeline                       src/raytrace_pipeline.rs:31-266 (new / image / compute / init)
  *   DiffusePipeline                        src/diffuse.rs:22-136 (new / image / next_frame)
+ *   RenderPassOverFrame, PresentTarget     src/texture_draw_pipeline.rs:96-157 (render into caller memory)
  *   RayTracingApp, compute_then_render,    src/raytracing_app.rs:32-227 (without the window: a render
  *   compute_n_then_render                  callback receives the accumulated image)
  *   load_obj                               graphics::load_obj (one mesh per `o` record)
@@ -217,6 +218,23 @@ class Context {
     return out;
   }
   std::vector<uint8_t> read_rgba8(hrt_image_id image) const { return read(image, HRT_FMT_RGBA8); }
+  // the present pass into caller memory (hrt_present): enqueued, not waited for; returns the ticket
+  uint64_t present(const hrt_present_info& info, void* dst, uint64_t dst_bytes) {
+    uint64_t ticket = 0;
+    check(hrt_present(get(), &info, dst, dst_bytes, &ticket), "hrt_present", get());
+    return ticket;
+  }
+  uint64_t accumulate_present(uint32_t frame, const hrt_present_info& info, void* dst, uint64_t dst_bytes) {
+    uint64_t ticket = 0;
+    check(hrt_accumulate_present(get(), frame, &info, dst, dst_bytes, &ticket), "hrt_accumulate_present", get());
+    return ticket;
+  }
+  bool present_done(uint64_t ticket) const {
+    uint32_t done = 0;
+    check(hrt_present_done(get(), ticket, &done), "hrt_present_done", get());
+    return done != 0;
+  }
+  void present_wait(uint64_t ticket) { check(hrt_present_wait(get(), ticket), "hrt_present_wait", get()); }
 
  private:
   struct Del {
@@ -231,6 +249,37 @@ struct Image {
   Context* ctx;
   hrt_image_id id;
   std::vector<uint8_t> read_rgba8() const { return ctx->read_rgba8(id); }
+};
+
+// The memory a frame is presented into (the reference's swapchain image view): ptr is memory a kernel
+// may write (an import of the context, device, managed or registered host memory).
+struct PresentTarget {
+  void* ptr;
+  uint64_t nbytes;
+  uint32_t width, height;
+  uint32_t pitch = 0;  // bytes per row; 0 = width * 4
+  hrt_present_format format = HRT_PRESENT_B8G8R8A8;
+};
+
+// src/texture_draw_pipeline.rs:96-157: the image as a nearest-sampled, vertically flipped quad over the
+// whole target.  render() enqueues the pass after the work issued so far (the before_future) and
+// returns its ticket (the after_future): Context::present_wait / present_done.
+class RenderPassOverFrame {
+ public:
+  RenderPassOverFrame(Context& ctx, hrt_present_format output_format = HRT_PRESENT_B8G8R8A8)
+      : ctx_(&ctx), format_(output_format) {}
+  uint64_t render(const Image& view, const PresentTarget& target) {
+    if (view.ctx != ctx_) throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: view must be an image of the pass's context");
+    if (target.format != format_)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: the target's format differs from the pass's output format");
+    const hrt_present_info info{(uint32_t)view.id, (uint32_t)target.format, target.width, target.height,
+                                target.pitch ? target.pitch : target.width * 4u, 0u};
+    return ctx_->present(info, target.ptr, target.nbytes);
+  }
+
+ private:
+  Context* ctx_;
+  hrt_present_format format_;
 };
 
 // ---- pipelines ---------------------------------------------------------------------------------

@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""What presenting costs the realtime loop (compute_then_render per frame, src/main.rs:41-57): island
+1920x1080, 64 spp, 8 bounces, 5 warm-up frames then 32 timed frames, per-frame wall time of four variants
+
+  a  trace + accumulate only                          (bench.py's per_frame_dispatch_ms shape)
+  b  ... + a blocking hrt_read_image of the accumulator into device memory every frame
+         (what a presenting user paid before hrt_present: the host waits once per frame)
+  c  ... + hrt_present into device memory, waiting only for the ticket of three frames back
+  d  hrt_accumulate_present (the combine and the present in one kernel), waiting as c
+
+each in a fresh process, three times.  Usage:
+    python tools/present_loop.py [--out profiles/present_loop.jsonl] [--repeats 3]
+Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
+child, then a summary line (median and spread per variant, c / b and d / c).
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VARIANTS = ("a", "b", "c", "d")
+SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
+
+
+def child(variant: str) -> dict:
+    import torch
+
+    import epq_raytracer_amd as E
+    from epq_raytracer_amd import _lib
+
+    W, H = SIZE
+    camera, settings = E.preset(SCENE)
+    settings.num_samples, settings.max_bounces = SPP, BOUNCES
+    ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
+    raytrace = E.RayTracePipeline(ctx, SIZE, settings)
+    diffuse = E.DiffusePipeline(ctx, SIZE)
+    targets = [torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0") for _ in range(LAG + 1)]
+    nbytes = W * H * 4
+    raytrace.init()
+    diffuse.next_frame(0, raytrace.image())
+    frame, tickets = 1, []
+
+    def step():
+        nonlocal frame
+        dst = targets[frame % len(targets)].data_ptr()
+        raytrace.compute(camera, frame)
+        if variant == "d":
+            tickets.append(ctx.accumulate_present(frame, dst, nbytes, W, H))
+        else:
+            diffuse.next_frame(frame, raytrace.image())
+            if variant == "b":
+                ctx.read_into(_lib.IMG_ACCUM, _lib.FMT_RGBA8, dst, nbytes)
+            elif variant == "c":
+                tickets.append(ctx.present(_lib.IMG_ACCUM, dst, nbytes, W, H))
+        if len(tickets) > LAG:  # the frame of three back is on screen before its target is reused
+            ctx.present_wait(tickets[-1 - LAG])
+        frame += 1
+
+    for _ in range(WARMUP):
+        step()
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(FRAMES):
+        step()
+    ctx.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3 / FRAMES
+    st = ctx.stats()
+    out = {"variant": variant, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
+           "width": W, "height": H, "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
+           "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
+    ctx.close()
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--variant", choices=VARIANTS, help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "present_loop.jsonl"))
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--timeout", type=int, default=150, help="seconds per child process")
+    a = ap.parse_args()
+    if a.variant:
+        print(json.dumps(child(a.variant)), flush=True)
+        return 0
+    runs = {v: [] for v in VARIANTS}
+    lines = []
+    for rep in range(a.repeats):
+        for v in VARIANTS:
+            try:
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--variant", v], capture_output=True,
+                                   text=True, timeout=a.timeout)
+            except subprocess.TimeoutExpired:
+                print(f"variant {v} repeat {rep}: no result within {a.timeout} s; stopping", file=sys.stderr)
+                return 1
+            rec = next((ln for ln in p.stdout.splitlines() if ln.startswith("{")), None)
+            if p.returncode != 0 or rec is None:
+                print(f"variant {v} repeat {rep} failed ({p.returncode}); stopping\n{p.stderr[-2000:]}", file=sys.stderr)
+                return 1
+            d = dict(json.loads(rec), repeat=rep)
+            runs[v].append(d["ms_per_frame"])
+            lines.append(json.dumps(d))
+            print(lines[-1], flush=True)
+    med = {v: statistics.median(runs[v]) for v in VARIANTS}
+    summary = {"summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
+                               "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in VARIANTS},
+               "c_over_b": round(med["c"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
+               "d_minus_c_ms": round(med["d"] - med["c"], 4)}
+    lines.append(json.dumps(summary))
+    print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
