@@ -1158,8 +1158,13 @@ hrt_status check_present(hrt_context* ctx, const hrt_present_info* info, const v
                          const uint64_t* ticket, bool accum_only, const char* who) {
   auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
   if (!info || !dst || !ticket) return bad("null info, destination or ticket");
-  if (ctx->part_count > 1 || ctx->comm)
-    return bad("a partitioned or communicator-joined context cannot present (the gathered present is not implemented)");
+  // a communicator: only the root of an intact hrt_comm_init_all group presents (the gathered frame)
+  if (ctx->comm) {
+    if (hrt_status st = hrt::comm_present_check(ctx, who); st != HRT_OK) return st;
+  } else if (ctx->part_count > 1) {
+    return bad("a partitioned context with no communicator cannot present (its rows are not a frame: join an "
+               "hrt_comm_init_all group and present on its root)");
+  }
   if (info->image_id != HRT_IMG_ACCUM && (accum_only || info->image_id != HRT_IMG_TRACE))
     return bad(accum_only ? "image_id must be HRT_IMG_ACCUM" : "unknown image id");
   if (info->format != HRT_PRESENT_B8G8R8A8 && info->format != HRT_PRESENT_R8G8B8A8) return bad("unknown present format");
@@ -1203,6 +1208,8 @@ hrt::PresentTarget present_target(const hrt_present_info* info, void* dst) {
 
 // The pass itself on ctx->stream, after everything that wrote the image (arguments already checked).
 hrt_status enqueue_present(hrt_context* ctx, const hrt_present_info* info, void* dst) {
+  // the root of a group (check_present let no other communicator through): the gathered frame
+  if (ctx->comm) return hrt::comm_present(ctx, info->image_id, present_target(info, dst));
   const void* src = hrt::local_image(ctx, info->image_id);
   if (!src) return fail(ctx, HRT_ERR_HIP, "hrt_present: lane wait failed");
   const bool f32 = ctx->mode != HRT_MODE_RGBA8;
@@ -1239,6 +1246,19 @@ extern "C" hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, c
   if (st != HRT_OK) return st;
   hipEvent_t ev = nullptr;
   if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  if (const std::vector<hrt_context*>* members = hrt::comm_group_members(ctx)) {
+    // the root of a group: every part folds its own rows on its own device and stream, in part order,
+    // then the gathered present of the accumulator (no fused kernel: the fold and the target are on
+    // different contexts)
+    for (hrt_context* m : *members)
+      if ((st = hrt_accumulate(m, frame)) != HRT_OK) {
+        if (m != ctx) ctx->err = m->err;
+        (void)bind(ctx);
+        return st;
+      }
+    if ((st = enqueue_present(ctx, info, dst)) != HRT_OK) return st;
+    return ticket_end(ctx, ev, ticket);
+  }
   if (ctx->defer || info->width != ctx->width || info->height != ctx->local_rows) {
     // the two passes: a deferred combine is folded by the present, a scaled target samples the new accumulator
     if ((st = hrt_accumulate(ctx, frame)) != HRT_OK) return st;

@@ -16,6 +16,11 @@
 //                            device-to-device copies instead, through the same assembly.
 // RCCL is loaded with dlopen on the first hrt_comm_* call, so single-GPU users never load it.
 //
+// The root of an hrt_comm_init_all group also presents the gathered frame (hrt_present,
+// hrt_accumulate_present): the same gather, but stream-ordered and without a host wait, and one kernel
+// that reads the blocks where the partition put each row and writes the caller's target
+// (present_group below).
+//
 // Errors on the process path (hrt_comm_init, read_process) follow hrt_comm_protocol.h: every rank
 // agrees on the call's status (a 4-byte ncclAllReduce) before any data moves, so an error on one rank
 // is an error on every rank instead of peers blocked forever in the collective; waits are bounded by
@@ -328,7 +333,109 @@ hrt_status read_group(hrt_context* ctx, Comm* c, uint32_t image_id, uint32_t fmt
   return bind(ctx);
 }
 
+// hrt_present on the root of an hrt_comm_init_all group: read_group's gather without its host waits, then
+// one kernel that reads the gathered blocks where the partition put each row and writes the caller's
+// target (launch_present_gathered; frame_buf and conv_buf are not touched).  Everything is ordered by
+// streams and events on the device:
+//   * a member's block is sent (RCCL) or copied (device copies, after an event recorded on the member's
+//     stream) behind everything that wrote its image -- local_image folds the deferred combines and
+//     joins the trace lane on the member's stream first;
+//   * the kernel follows the gather on the root's stream;
+//   * a member's later work follows the read of its image: the RCCL send is on its own stream, the
+//     copies are followed by the root's comm event, which every other member's stream waits for;
+//   * gather_buf is written again only by a later present or hrt_read_image of the group, whose copies
+//     run on the root's stream and whose RCCL gather receives on the root's rank, i.e. also on the
+//     root's stream: stream order puts them behind this kernel.
+// `at` names the context whose error text a failure left (copied to the root by comm_present).
+hrt_status present_group(hrt_context* root, Comm* rc, uint32_t image_id, const PresentTarget& target,
+                         hrt_context*& at) {
+  Group& g = *rc->group;
+  const size_t count = root->npix() * root->px_bytes(), n = g.members.size();
+  std::vector<const void*> src(n);
+  hrt_status st;
+  for (size_t i = 0; i < n; ++i) {
+    hrt_context* m = at = g.members[i];
+    if ((st = bind(m)) != HRT_OK) return st;
+    if (!(src[i] = local_image(m, image_id))) return fail(m, HRT_ERR_HIP, "hrt_present: lane wait failed");
+  }
+  at = root;
+  if (rc->transport == HRT_COMM_RCCL_GROUP) {
+    ncclResult_t r = rccl()->group_start();
+    for (size_t i = 0; r == ncclSuccess && i < n; ++i) {
+      hrt_context* m = g.members[i];
+      (void)hipSetDevice(m->device);
+      r = rccl()->gather(src[i], i == 0 ? rc->gather_buf : nullptr, count, ncclUint8, 0, m->comm->nccl, m->stream);
+    }
+    const ncclResult_t r2 = rccl()->group_end();
+    if (r != ncclSuccess || r2 != ncclSuccess) return fail(root, HRT_ERR_HIP, nccl_msg("ncclGather", r ? r : r2));
+    if ((st = bind(root)) != HRT_OK) return st;
+  } else {  // contexts sharing a device: copies into the root's gather buffer, ordered by events
+    if ((st = bind(root)) != HRT_OK) return st;
+    for (size_t i = 0; i < n; ++i) {
+      hrt_context* m = g.members[i];
+      if (i) {
+        HRT_HIP(root, hipEventRecord(m->comm->ev, m->stream));
+        HRT_HIP(root, hipStreamWaitEvent(root->stream, m->comm->ev, 0));
+      }
+      HRT_HIP(root, hipMemcpyAsync(static_cast<char*>(rc->gather_buf) + i * count, src[i], count, hipMemcpyDefault,
+                                   root->stream));
+    }
+    // the members' next writes of these images follow the copies (not the kernel: it reads gather_buf only)
+    HRT_HIP(root, hipEventRecord(rc->ev, root->stream));
+    for (size_t i = 1; i < n; ++i) HRT_HIP(root, hipStreamWaitEvent(g.members[i]->stream, rc->ev, 0));
+  }
+  const bool f32 = root->mode != HRT_MODE_RGBA8;
+  const GatheredImage img{f32 ? nullptr : static_cast<const uint32_t*>(rc->gather_buf),
+                          f32 ? static_cast<const float4*>(rc->gather_buf) : nullptr,
+                          root->width,
+                          root->height,
+                          rc->world == 1 ? root->height : root->row_tile,
+                          rc->world,
+                          root->local_rows};
+  HRT_HIP(root, launch_present_gathered(img, target, root->stream));
+  if (image_id != HRT_IMG_TRACE) return HRT_OK;
+  // each member's trace image may be written again after the read of it enqueued above: its lane's next
+  // trace, and the ring slot's next trace when the image is a slot of the deferred combiner's ring
+  for (size_t i = 0; i < n; ++i) {
+    hrt_context* m = at = g.members[i];
+    if ((st = bind(m)) != HRT_OK) return st;
+    if (m->cur_slot >= 0) {
+      HRT_HIP(m, hipEventRecord(m->fold_done, m->stream));
+      m->fold_set = true;
+    }
+    if ((st = release_lane(m, m->cur_lane)) != HRT_OK) return st;
+  }
+  at = root;
+  return bind(root);
+}
+
 }  // namespace
+
+hrt_status comm_present_check(hrt_context* ctx, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  const Comm* c = ctx->comm;
+  if (!c || !c->group)
+    return bad("a context joined with hrt_comm_init cannot present (the gathered present needs an hrt_comm_init_all group)");
+  if (c->group->broken) return bad("a context of the group was destroyed");
+  if (c->rank != 0 || c->group->members.empty() || c->group->members[0] != ctx)
+    return bad("present on the group's root, part 0");
+  if (!c->gather_buf) return bad("the group's root has no gather buffer");
+  return HRT_OK;
+}
+
+const std::vector<hrt_context*>* comm_group_members(const hrt_context* ctx) {
+  return ctx->comm && ctx->comm->group ? &ctx->comm->group->members : nullptr;
+}
+
+hrt_status comm_present(hrt_context* root, uint32_t image_id, const PresentTarget& target) {
+  hrt_context* at = root;
+  const hrt_status st = present_group(root, root->comm, image_id, target, at);
+  if (st != HRT_OK) {
+    if (at != root) root->err = at->err;
+    (void)hipSetDevice(root->device);
+  }
+  return st;
+}
 
 hrt_status comm_read_image(hrt_context* ctx, uint32_t image_id, uint32_t fmt, void* dst, size_t bytes,
                            hrt_status arg) {

@@ -227,6 +227,17 @@ hrt_status copy_frame_out(hrt_context* ctx, const void* src, size_t npix, uint32
 // check, agreed on by every rank of a process communicator before any of them gathers.
 hrt_status comm_read_image(hrt_context* ctx, uint32_t image_id, uint32_t fmt, void* dst, size_t bytes,
                            hrt_status arg);
+// The gathered present (hrt_present / hrt_accumulate_present on a context with a communicator, hrt_comm.cpp).
+struct PresentTarget;
+// HRT_OK when ctx is member 0 of an intact hrt_comm_init_all group; else HRT_ERR_INVALID_ARGUMENT with
+// the reason (`who` prefixes the message).  Host only: nothing is enqueued.
+hrt_status comm_present_check(hrt_context* ctx, const char* who);
+// The members of ctx's hrt_comm_init_all group in part order (nullptr: no such group).
+const std::vector<hrt_context*>* comm_group_members(const hrt_context* ctx);
+// Enqueues the gather of image_id to the root and the fused present kernel on the root's stream, with no
+// host wait (the caller has run comm_present_check and issues the ticket on root->stream afterwards).
+// image_id: HRT_IMG_TRACE or HRT_IMG_ACCUM.  Leaves the root's device current.
+hrt_status comm_present(hrt_context* root, uint32_t image_id, const PresentTarget& target);
 
 }  // namespace hrt
 

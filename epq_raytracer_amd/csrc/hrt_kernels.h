@@ -123,6 +123,16 @@ struct PresentTarget {
 // present_rows at the image's own size, else present_nearest (src8 or src32 set)
 hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws, uint32_t hs, const PresentTarget& t,
                           hipStream_t stream);
+// The gathered present: the full width x height image as the root of a row-tile group holds it after the
+// gather -- parts blocks of local_rows x width pixels in part order (src8 or src32 set), global row y in
+// block (y / row_tile) % parts (hrt_present_map.h).  launch_present's rule over the full image, read
+// straight from the blocks: present_gathered_rows at the image's own size, else present_gathered_nearest.
+struct GatheredImage {
+  const uint32_t* src8;
+  const float4* src32;
+  uint32_t width, height, row_tile, parts, local_rows;
+};
+hipError_t launch_present_gathered(const GatheredImage& g, const PresentTarget& t, hipStream_t stream);
 // launch_accumulate on a w x h image (t of the same size) whose kernel also writes the folded pixel to t
 hipError_t launch_accumulate_present(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32,
                                      uint32_t w, uint32_t h, uint32_t frame, const PresentTarget& t, hipStream_t stream);

@@ -27,6 +27,7 @@
 #include "hrt_bvh.h"
 #include "hrt_kernels.h"
 #include "hrt_math.h"
+#include "hrt_present_map.h"
 
 namespace hrt {
 
@@ -3242,6 +3243,49 @@ __global__ __launch_bounds__(256) void present_nearest(const T* __restrict__ src
     d[x] = present_word(present_load(s, sx), bgra);
   }
 }
+// The gathered present (hrt_present on the root of an hrt_comm_init_all group): the source is the root's
+// gather buffer -- the parts' blocks of local_rows x w pixels in part order -- read where the row-tile
+// partition put each global row (hrt_present_map.h gathered_row), so the un-interleave, the conversion
+// and the copy of the read path are one read and one write.  The shape is present_rows' / present_nearest's:
+// the target row is grid.y, so the source row, its part and its local row are wave-uniform; the row
+// offset is 64-bit (parts x local_rows x w x 16 B may pass 2^32).  At equal size the 128-bit body runs
+// on the rows whose target row and (RGBA8) gathered source row both start on a 16 B boundary: with an
+// odd width consecutive global rows of one tile alternate, and a tile's first row depends on its block.
+template <typename T>
+__global__ __launch_bounds__(256) void present_gathered_rows(const T* __restrict__ src, unsigned char* __restrict__ dst,
+                                                             uint32_t w, uint32_t h, uint32_t pitch, uint32_t bgra,
+                                                             uint32_t row_tile, uint32_t parts, uint32_t local_rows) {
+  const uint32_t y = blockIdx.y;
+  const T* s = src + gathered_row(present_sy(y, h, h), row_tile, parts, local_rows) * w;
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
+  const bool vec = (((uintptr_t)d | (sizeof(T) == 4 ? (uintptr_t)s : (uintptr_t)0)) & 15u) == 0;
+  const uint32_t quads = vec ? w / 4u : 0u;
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
+  for (uint32_t q = t; q < quads; q += stride) {
+    uint4 v;
+    if constexpr (sizeof(T) == 4) {
+      v = reinterpret_cast<const uint4*>(s)[q];
+    } else {
+      v = make_uint4(present_load(s, 4u * q), present_load(s, 4u * q + 1u), present_load(s, 4u * q + 2u),
+                     present_load(s, 4u * q + 3u));
+    }
+    reinterpret_cast<uint4*>(d)[q] =
+        make_uint4(present_word(v.x, bgra), present_word(v.y, bgra), present_word(v.z, bgra), present_word(v.w, bgra));
+  }
+  for (uint32_t i = quads * 4u + t; i < w; i += stride) d[i] = present_word(present_load(s, i), bgra);
+}
+// ... into a target of another size: sy of the FULL ws x hs image once per row, then its gathered row.
+template <typename T>
+__global__ __launch_bounds__(256) void present_gathered_nearest(const T* __restrict__ src, uint32_t ws, uint32_t hs,
+                                                                unsigned char* __restrict__ dst, uint32_t wt, uint32_t ht,
+                                                                uint32_t pitch, uint32_t bgra, uint32_t row_tile,
+                                                                uint32_t parts, uint32_t local_rows) {
+  const uint32_t y = blockIdx.y;
+  const T* s = src + gathered_row(present_sy(y, hs, ht), row_tile, parts, local_rows) * ws;
+  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
+  for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < wt; x += gridDim.x * 256u)
+    d[x] = present_word(present_load(s, present_sx(x, ws, wt)), bgra);
+}
 // hrt_accumulate_present at the image's own size: accumulate_rgba8 / accumulate_rgba32f (the same
 // combine_* arithmetic, 256 threads, the UNORM8 table in LDS) whose thread also writes the folded pixel
 // to the flipped target row -- the accumulator is not read again by a present pass (w * h <= 2^28).
@@ -3735,6 +3779,34 @@ hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws
     present_launch(src8, ws, hs, t, stream);
   else
     present_launch(src32, ws, hs, t, stream);
+  return hipGetLastError();
+}
+
+template <typename T>
+static void present_gathered_launch(const T* src, const GatheredImage& g, const PresentTarget& t, hipStream_t stream) {
+  if (t.width == g.width && t.height == g.height) {
+    const dim3 grid(((t.width + 3) / 4 + 255) / 256, t.height, 1);
+    present_gathered_rows<T><<<grid, 256, 0, stream>>>(src, t.dst, g.width, g.height, t.pitch, t.bgra, g.row_tile,
+                                                        g.parts, g.local_rows);
+  } else {
+    const dim3 grid((t.width + 255) / 256, t.height, 1);
+    present_gathered_nearest<T><<<grid, 256, 0, stream>>>(src, g.width, g.height, t.dst, t.width, t.height, t.pitch,
+                                                           t.bgra, g.row_tile, g.parts, g.local_rows);
+  }
+}
+
+hipError_t launch_present_gathered(const GatheredImage& g, const PresentTarget& t, hipStream_t stream) {
+  if (g.width == 0 || g.height == 0 || t.width == 0 || t.height == 0 || t.height > 65535u || t.pitch / 4 < t.width ||
+      !t.dst || (!g.src8 && !g.src32))
+    return hipErrorInvalidValue;
+  // (launch_assemble_rows' bound: every global row below height lies inside its part's local rows)
+  if (g.parts == 0 || g.row_tile == 0 ||
+      (uint64_t)((g.height - 1) / g.row_tile / g.parts + 1) * g.row_tile > g.local_rows)
+    return hipErrorInvalidValue;
+  if (g.src8)
+    present_gathered_launch(g.src8, g, t, stream);
+  else
+    present_gathered_launch(g.src32, g, t, stream);
   return hipGetLastError();
 }
 

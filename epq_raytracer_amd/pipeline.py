@@ -235,7 +235,9 @@ class HrtContext:
                 fmt: int = _lib.PRESENT_B8G8R8A8) -> int:
         """hrt_present: enqueue the image as the reference's flipped, nearest-sampled quad over the
         width x height target at device pointer dst_ptr (rows pitch bytes apart, default width * 4) and
-        return its ticket without waiting (at most 8 in flight)."""
+        return its ticket without waiting (at most 8 in flight).  On the root (part 0) of a comm_init_all
+        group the image is the group's gathered full frame (width x height, not local_rows); the other
+        members, a comm_init-joined context and a partitioned context with no communicator are rejected."""
         info, t = self._present_info(image_id, width, height, pitch, fmt), ctypes.c_uint64()
         self._check(self.lib.hrt_present(self.handle, ctypes.byref(info), ctypes.c_void_p(dst_ptr), int(nbytes),
                                          ctypes.byref(t)), "hrt_present")
@@ -244,7 +246,9 @@ class HrtContext:
     def accumulate_present(self, frame: int, dst_ptr: int, nbytes: int, width: int, height: int,
                            pitch: Optional[int] = None, fmt: int = _lib.PRESENT_B8G8R8A8) -> int:
         """hrt_accumulate_present: accumulate(frame) and present(IMG_ACCUM, ...) in one call (one kernel
-        when the target has the image's size and combines are not deferred); returns the ticket."""
+        when the target has the image's size and combines are not deferred); returns the ticket.  On the
+        root of a comm_init_all group: accumulate(frame) on every member in part order, then the gathered
+        present."""
         info, t = self._present_info(_lib.IMG_ACCUM, width, height, pitch, fmt), ctypes.c_uint64()
         self._check(self.lib.hrt_accumulate_present(self.handle, int(frame) & 0xFFFFFFFF, ctypes.byref(info),
                                                     ctypes.c_void_p(dst_ptr), int(nbytes), ctypes.byref(t)),
@@ -326,7 +330,8 @@ class Image:
     def read(self, fmt: int = _lib.FMT_RGBA8) -> Optional[np.ndarray]:
         """What the presenter gets.  Without a communicator: the context's rows.  On a context joined to
         one (hrt_comm_init): the gathered FULL frame -- a collective every rank must call; ranks other
-        than 0 get None.  On a group (hrt_comm_init_all): the full frame."""
+        than 0 get None.  On a group (hrt_comm_init_all): the full frame (a blocking read; the root's
+        HrtContext.present / RenderPassOverFrame.render shows the same frame without a host wait)."""
         rank, _, transport = self.ctx.comm_info()
         if transport == _lib.COMM_NONE:
             return self.ctx.read(self.image_id, fmt)
@@ -348,7 +353,8 @@ class PresentTarget:
 
 class RenderPassOverFrame:
     """src/texture_draw_pipeline.rs:96-157 on the HIP context: the image drawn as a nearest-sampled,
-    vertically flipped quad over the whole target (hrt_present)."""
+    vertically flipped quad over the whole target (hrt_present).  With ctx the root of a comm_init_all
+    group, the view is the group's full frame (the gathered present)."""
 
     def __init__(self, ctx: HrtContext, output_format: int = _lib.PRESENT_B8G8R8A8):
         self.ctx, self.output_format = ctx, int(output_format)

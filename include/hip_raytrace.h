@@ -531,14 +531,32 @@ hrt_status hrt_release_external_memory(hrt_context* ctx, void* dev_ptr);
  * Anything else -- pageable host memory included -- is HRT_ERR_INVALID_ARGUMENT, decided on the host
  * before anything is enqueued.
  *
- * A context of a row-tile partition (part_count > 1) or joined to a communicator is rejected: the
- * gathered present is a follow-up. */
+ * The gathered present.  On member 0 (the root, part 0) of an intact hrt_comm_init_all group -- either
+ * transport, any world >= 1 -- the source is the group's full width x height image: global row y lives
+ * in part (y / row_tile) % parts at local row (y / row_tile / parts) * row_tile + y % row_tile, and the
+ * rule above runs with Ws = width and Hs = height (the full height, not local_rows; the parts' padded
+ * local rows are never sampled).  The target holds, byte for byte, what hrt_present writes on an
+ * unpartitioned context holding the same frame.  The call still only enqueues: every member's block is
+ * gathered to the root behind the work issued so far on that member (deferred combines folded first on
+ * every member; HRT_IMG_TRACE joins and then releases each member's current trace lane), one kernel on
+ * the root's stream reads the gathered blocks and writes the target, and work issued afterwards on any
+ * member is ordered after the part of the pass that reads that member's image -- all by streams and
+ * events on the device, with no host wait.  Tickets come from the root's sequence; hrt_present_done,
+ * hrt_present_wait and hrt_synchronize on the root behave as above, and dst is checked against the
+ * root's device and imports.
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued on any member (the message names
+ * the reason): a member other than the root, a group with a destroyed member, a context joined with
+ * hrt_comm_init (one process per GPU: a present there would be a collective), and a context of a
+ * row-tile partition (part_count > 1) with no communicator. */
 hrt_status hrt_present(hrt_context* ctx, const hrt_present_info* info, void* dst, uint64_t dst_bytes,
                        uint64_t* ticket);
 /* hrt_accumulate(ctx, frame) followed by hrt_present(ctx, info, ...) with info->image_id ==
  * HRT_IMG_ACCUM (any other id is rejected), byte for byte; hrt_stats.accumulates counts it once.  When
  * the target has the image's size and HRT_OPT_DEFER_COMBINE is off, both run as one kernel that folds
- * the pixel, writes the accumulator and writes the target; otherwise as the two passes. */
+ * the pixel, writes the accumulator and writes the target; otherwise as the two passes.
+ * On the root of an hrt_comm_init_all group: hrt_accumulate(member, frame) on every member in part order,
+ * each on its own stream (every member's hrt_stats.accumulates counts once), then the gathered present of
+ * HRT_IMG_ACCUM -- the fold runs on each member's device, the present on the root's. */
 hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, const hrt_present_info* info, void* dst,
                                   uint64_t dst_bytes, uint64_t* ticket);
 /* *done = 1 when the pass of `ticket` has finished, else 0 (a poll).  Ticket 0 or one never issued:

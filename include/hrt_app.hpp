@@ -218,7 +218,9 @@ class Context {
     return out;
   }
   std::vector<uint8_t> read_rgba8(hrt_image_id image) const { return read(image, HRT_FMT_RGBA8); }
-  // the present pass into caller memory (hrt_present): enqueued, not waited for; returns the ticket
+  // the present pass into caller memory (hrt_present): enqueued, not waited for; returns the ticket.
+  // On the root (part 0) of an hrt_comm_init_all group the image is the group's gathered full frame,
+  // and accumulate_present accumulates on every member first; other members of a group are rejected.
   uint64_t present(const hrt_present_info& info, void* dst, uint64_t dst_bytes) {
     uint64_t ticket = 0;
     check(hrt_present(get(), &info, dst, dst_bytes, &ticket), "hrt_present", get());
@@ -263,7 +265,8 @@ struct PresentTarget {
 
 // src/texture_draw_pipeline.rs:96-157: the image as a nearest-sampled, vertically flipped quad over the
 // whole target.  render() enqueues the pass after the work issued so far (the before_future) and
-// returns its ticket (the after_future): Context::present_wait / present_done.
+// returns its ticket (the after_future): Context::present_wait / present_done.  With the context the
+// root of an hrt_comm_init_all group, the view is the group's full frame (the gathered present).
 class RenderPassOverFrame {
  public:
   RenderPassOverFrame(Context& ctx, hrt_present_format output_format = HRT_PRESENT_B8G8R8A8)

@@ -9,7 +9,13 @@
   d  hrt_accumulate_present (the combine and the present in one kernel), waiting as c
 
 each in a fresh process, three times.  Usage:
-    python tools/present_loop.py [--out profiles/present_loop.jsonl] [--repeats 3]
+    python tools/present_loop.py [--out profiles/present_loop.jsonl] [--repeats 3] [--parts N]
+With --parts N > 1 the frame is rendered by N contexts of interleaved 8-row tiles, all on device 0, joined
+with hrt_comm_init_all (the single-process multi-GPU layout rehearsed on one GPU: ordering and host cost,
+not scaling).  Every frame traces and accumulates on every part; b reads the gathered frame with a blocking
+read_frame into device memory, c presents on the group's root, d is hrt_accumulate_present on the root.
+--baseline-lib PATH adds, to every repeat, variant b on another build of the library (what that build
+offers a group), alternating with this build's variants.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -28,7 +34,10 @@ VARIANTS = ("a", "b", "c", "d")
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
 
-def child(variant: str) -> dict:
+ROW_TILE = 8
+
+
+def child(variant: str, parts: int = 1) -> dict:
     import torch
 
     import epq_raytracer_amd as E
@@ -37,23 +46,33 @@ def child(variant: str) -> dict:
     W, H = SIZE
     camera, settings = E.preset(SCENE)
     settings.num_samples, settings.max_bounces = SPP, BOUNCES
-    ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
-    raytrace = E.RayTracePipeline(ctx, SIZE, settings)
-    diffuse = E.DiffusePipeline(ctx, SIZE)
+    if parts > 1:
+        ctxs = [E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8, partition=(ROW_TILE, p, parts))
+                for p in range(parts)]
+    else:
+        ctxs = [E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)]
+    ctx = ctxs[0]  # the root: presents, reads and holds the tickets
+    raytraces = [E.RayTracePipeline(c, SIZE, settings) for c in ctxs]
+    diffuses = [E.DiffusePipeline(c, SIZE) for c in ctxs]
+    if parts > 1:
+        E.HrtContext.comm_init_all(ctxs)
     targets = [torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0") for _ in range(LAG + 1)]
     nbytes = W * H * 4
-    raytrace.init()
-    diffuse.next_frame(0, raytrace.image())
+    for raytrace, diffuse in zip(raytraces, diffuses):
+        raytrace.init()
+        diffuse.next_frame(0, raytrace.image())
     frame, tickets = 1, []
 
     def step():
         nonlocal frame
         dst = targets[frame % len(targets)].data_ptr()
-        raytrace.compute(camera, frame)
-        if variant == "d":
+        for raytrace in raytraces:
+            raytrace.compute(camera, frame)
+        if variant == "d":  # (on a group's root: accumulates on every part, then the gathered present)
             tickets.append(ctx.accumulate_present(frame, dst, nbytes, W, H))
         else:
-            diffuse.next_frame(frame, raytrace.image())
+            for raytrace, diffuse in zip(raytraces, diffuses):
+                diffuse.next_frame(frame, raytrace.image())
             if variant == "b":
                 ctx.read_into(_lib.IMG_ACCUM, _lib.FMT_RGBA8, dst, nbytes)
             elif variant == "c":
@@ -64,37 +83,52 @@ def child(variant: str) -> dict:
 
     for _ in range(WARMUP):
         step()
-    ctx.synchronize()
+    for c in ctxs:
+        c.synchronize()
     t0 = time.perf_counter()
     for _ in range(FRAMES):
         step()
-    ctx.synchronize()
+    for c in reversed(ctxs):  # (the root last: its tickets follow every part's copy)
+        c.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / FRAMES
     st = ctx.stats()
-    out = {"variant": variant, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
+    assert all(c.stats().accumulates == st.accumulates for c in ctxs)
+    out = {"variant": variant, "parts": parts, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
            "width": W, "height": H, "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
            "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
-    ctx.close()
+    for c in ctxs:
+        c.close()
     return out
 
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--variant", choices=VARIANTS, help="run one variant in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "present_loop.jsonl"))
+    ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
+    ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
+                                                "with --parts above 1, appended to)")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--baseline-lib", default=None,
+                    help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
+                         "(HRT_LIB), alternating with this build's variants, recorded as b_baseline")
     ap.add_argument("--timeout", type=int, default=150, help="seconds per child process")
     a = ap.parse_args()
+    if a.parts < 1:
+        ap.error("--parts must be at least 1")
     if a.variant:
-        print(json.dumps(child(a.variant)), flush=True)
+        print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    runs = {v: [] for v in VARIANTS}
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl")
+    order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in VARIANTS]
+    runs = {name: [] for name, _, _ in order}
     lines = []
     for rep in range(a.repeats):
-        for v in VARIANTS:
+        for name, v, lib in order:
+            env = dict(os.environ, HRT_LIB=os.path.abspath(lib)) if lib else None
             try:
-                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--variant", v], capture_output=True,
-                                   text=True, timeout=a.timeout)
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--variant", v, "--parts", str(a.parts)],
+                                   capture_output=True, text=True, timeout=a.timeout, env=env)
             except subprocess.TimeoutExpired:
                 print(f"variant {v} repeat {rep}: no result within {a.timeout} s; stopping", file=sys.stderr)
                 return 1
@@ -102,19 +136,22 @@ def main() -> int:
             if p.returncode != 0 or rec is None:
                 print(f"variant {v} repeat {rep} failed ({p.returncode}); stopping\n{p.stderr[-2000:]}", file=sys.stderr)
                 return 1
-            d = dict(json.loads(rec), repeat=rep)
-            runs[v].append(d["ms_per_frame"])
+            d = dict(json.loads(rec), repeat=rep, run=name)
+            runs[name].append(d["ms_per_frame"])
             lines.append(json.dumps(d))
             print(lines[-1], flush=True)
-    med = {v: statistics.median(runs[v]) for v in VARIANTS}
-    summary = {"summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
-                               "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in VARIANTS},
+    med = {v: statistics.median(runs[v]) for v in runs}
+    summary = {"parts": a.parts,
+               "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
+                               "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs},
                "c_over_b": round(med["c"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
                "d_minus_c_ms": round(med["d"] - med["c"], 4)}
+    if a.baseline_lib:
+        summary["b_over_b_baseline"] = round(med["b"] / med["b_baseline"], 4)
     lines.append(json.dumps(summary))
     print(lines[-1], flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
+    with open(a.out, "a" if a.parts > 1 else "w") as f:  # (the group file holds one run per --parts)
         f.write("\n".join(lines) + "\n")
     return 0
 
