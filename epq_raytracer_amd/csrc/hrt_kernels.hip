@@ -39,12 +39,6 @@ namespace hrt {
 #endif
 
 
-#ifndef HRT_SHADE_KARGS
-#define HRT_SHADE_KARGS 1  // shading reads the scene pointers from the kernel arguments (kargs)
-#endif
-#ifndef HRT_RAYGEN_KARGS
-#define HRT_RAYGEN_KARGS 1  // the camera read per sample from the kernel arguments (kargs)
-#endif
 
 // Read-only views of the uploaded std430 records.
 struct Scene {
@@ -90,6 +84,12 @@ __device__ __forceinline__ unsigned long long mask_read(unsigned long long m, ui
 }
 __device__ __forceinline__ uint32_t lanes_below(unsigned long long b) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+}
+// n + lanes_below(b), the same integer (mod 2^32): n goes in as the lane count's own addend (v_mbcnt_lo
+// adds its second operand), which hipcc does not do by itself -- it counted from 0, shifted n on the
+// scalar side and added both (one VALU and one SALU more per stack push)
+__device__ __forceinline__ uint32_t lanes_below_from(unsigned long long b, uint32_t n) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, n));
 }
 
 // Exclusive prefix sum of x over the wave's 64 lanes in lane order, and the total (every lane active):
@@ -989,17 +989,14 @@ __device__ __forceinline__ uint32_t world_hit_tile(const Scene& sc, const TraceP
     }
   }
   float best_k = c.t * kOnePlus;
-  const kfloat* ct = to_const(HRT_SHADE_KARGS ? kargs()->cam_tris : P.cam_tris);
+  const kfloat* ct = to_const(kargs()->cam_tris);
   auto entry = [&](uint32_t i) {
     return tl.lds ? __builtin_amdgcn_readfirstlane(lds_get(&tl.lds[i])) : (uint32_t)__builtin_amdgcn_readlane((int)tl.v, (int)i);
   };
   // (r03: requesting the next entry's record before this one's test was slower, island 2.259 -> 2.338)
-#ifndef HRT_LIST_UNIFORM
-#define HRT_LIST_UNIFORM 1
-#endif
   // (the list length through readfirstlane: hipcc had lost its uniformity through build_tile_list's
   // early returns and ran the entry loop as a divergent loop with a VGPR trip count)
-  const uint32_t n = HRT_LIST_UNIFORM ? __builtin_amdgcn_readfirstlane(tl.n) : tl.n;
+  const uint32_t n = __builtin_amdgcn_readfirstlane(tl.n);
   uint32_t tested = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t e = entry(i);
@@ -1480,48 +1477,16 @@ __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const Trac
 // hold key 0 and win ties, as they are scanned first).  A child is dropped only by BUNDLE_BVH's exact
 // node test (wq_node_visit) against the slot's current t, which only ever exceeds the final one.
 // When the node stack could overflow, the popped groups' subtrees are walked stacklessly instead.
-#ifndef HRT_WQ_CONE
-#define HRT_WQ_CONE 1    // the nodes' back-face (normal cone) test
-#endif
-#ifndef HRT_WQ_BRANCHLESS
-#define HRT_WQ_BRANCHLESS 1  // member test without the back-face early-out branch (r03s: island -0.6%, cave -0.3% with ALL4)
-#endif
-#ifndef HRT_WQ_ALL4
-#define HRT_WQ_ALL4 1  // all four member slots tested, masked past the group's count (r03s, with BRANCHLESS)
-#endif
-#ifndef HRT_WQ_SELECT
-#define HRT_WQ_SELECT 1  // a member's outcome as selects instead of a branch (r03t)
-#endif
-#ifndef HRT_WQ_CONE_SQ
-#define HRT_WQ_CONE_SQ 1  // the members' back-face test squared, no square root (r03t)
-#endif
-#ifndef HRT_WQ_FMA_SLACK
-#define HRT_WQ_FMA_SLACK 1  // member test: slack compare and the cone's first product as fmas (r03t)
-#endif
-#ifndef HRT_WQ_LEAF_FLAT
-#define HRT_WQ_LEAF_FLAT 1  // kept leaves' triangle pairs pushed by one loop over the lane's count (r03u: island -1.3%, cave -1.7%)
-#endif
-#ifndef HRT_WQ_TRI_SELECT
-#define HRT_WQ_TRI_SELECT 1  // the triangle pre-test's rejections as one predicate (r03y: cave -0.4%)
-#endif
-#ifndef HRT_WQ_PUSH_DUMP
-#define HRT_WQ_PUSH_DUMP 0  // (A/B) inner-member pushes without a branch (non-pushing lanes store to a dump word)
-#endif
-#ifndef HRT_WQ_BAND_PLANE
-#define HRT_WQ_BAND_PLANE 1  // band entries whose plane the ray starts behind are dropped (r03aa: band tests per cave lane 3.9 -> 0.8; island -0.9%, cave -1.6%)
-#endif
-#ifndef HRT_WQ_MIXED
-#define HRT_WQ_MIXED 1   // short node and triangle stacks share one step
-#endif
-#ifndef HRT_WQ_EARLY_REC
-#define HRT_WQ_EARLY_REC 1  // a node step's first member pair read before the slot read (r04)
-#endif
-#ifndef HRT_WQ_BAND_EARLY
-#define HRT_WQ_BAND_EARLY 0  // (r05b: neutral, island 1.786 / 1.787, cave 5.405 / 5.400 ms) a bounce lane's direction-cell offsets requested at the batch's start (r05)
-#endif
-#ifndef HRT_WQ_BAND_AHEAD
-#define HRT_WQ_BAND_AHEAD 1  // band-list rounds whose entry loads are in flight at once (1: one round ahead)
-#endif
+//
+// Settled A/B arms, folded into the code (their switches are gone; the ISA is unchanged by the folding,
+// DESIGN.md 15): the nodes' back-face (normal cone) test; the member test without an early-out branch,
+// all four slots tested and masked past the group's count (r03s: island -0.6%, cave -0.3%); a member's
+// outcome as selects, the cone test squared, the slack compares as fmas (r03t); kept leaves' triangles
+// pushed by one loop over the lane's count (r03u: island -1.3%, cave -1.7%); the triangle pre-test's
+// rejections as one predicate (r03y: cave -0.4%); pushes by branch, not to a dump word; the band's
+// plane-side filter (r03aa: island -0.9%, cave -1.6%); mixed steps; a node step's first member pair read
+// before the slot read (r04); band cells read at the band's start, not the batch's (r05b: neutral); band
+// rounds one ahead.
 #ifndef HRT_WQ_TRI_MIN
 #define HRT_WQ_TRI_MIN 64u  // a triangle step runs once this many triangle pairs wait (or no node pair is left)
 #endif
@@ -1578,7 +1543,7 @@ __device__ __forceinline__ bool wq_node_visit_r(const float4& N0, const float4& 
   const float x = half_lo(w8) * d.x + half_hi(w8) * d.y + half_lo(w9) * d.z;
   const float xa = fmaxf(fabsf(x) - (2e-6f + kWqAxisErr), 0.0f);
   const float s_up = __builtin_amdgcn_sqrtf(fmaxf(1.0f - xa * xa, 0.0f)) + 1.2e-6f;
-  if (HRT_WQ_CONE && (x - kWqAxisErr) * half_hi(w9) - s_up * wq_sin_up(w10) - 1e-6f > 1e-5f) return false;  // back
+  if ((x - kWqAxisErr) * half_hi(w9) - s_up * wq_sin_up(w10) - 1e-6f > 1e-5f) return false;  // back
   const float mg = N0.w + N1.w * R;
   const float tx0 = ((N0.x - mg) - o.x) * inv.x, tx1 = ((N1.x + mg) - o.x) * inv.x;
   const float ty0 = ((N0.y - mg) - o.y) * inv.y, ty1 = ((N1.y + mg) - o.y) * inv.y;
@@ -1622,15 +1587,10 @@ __device__ __forceinline__ bool wq_member_visit(const float4& N0, const float4& 
                  w10 = __builtin_bit_cast(uint32_t, N2.z);
   // (fused: each rounding here is far inside the 2e-6 / 1e-6 slacks, and the host's margins carry 1e-6
   // relative headroom over one rounding of a + b R)
-#if HRT_WQ_FMA_SLACK
   // the first product as an fma with +0 (v_fma_mix_f32 reads the binary16 operand directly)
   const float x = __builtin_fmaf(half_lo(w9), q.d.z, __builtin_fmaf(half_hi(w8), q.d.y, __builtin_fmaf(half_lo(w8), q.d.x, 0.0f)));
-#else
-  const float x = __builtin_fmaf(half_lo(w9), q.d.z, __builtin_fmaf(half_hi(w8), q.d.y, half_lo(w8) * q.d.x));
-#endif
   const float xa = fmaxf(fabsf(x) - (2e-6f + kWqAxisErr), 0.0f);
   // (the cone test pays on cave too with per-node radii: without it 7.25 -> 7.43 ms, r03c)
-#if HRT_WQ_CONE_SQ
   // The test below squared, without the square root and only ever stricter.  It is back <=> L > s_up sin
   // with L = (x - E) cos - 1.1e-5 and s_up = sqrt(q) + 1.2e-6 (q = max(1 - xa^2, 0); the hardware root is
   // within 1.2e-7 of sqrt(q) on [0, 1]).  Here: L' = (x - E) cos - 1.2e-5 (its two roundings < 2.4e-7
@@ -1641,14 +1601,7 @@ __device__ __forceinline__ bool wq_member_visit(const float4& N0, const float4& 
   // NaN -> not back.
   const float q2 = fmaxf(__builtin_fmaf(-xa, xa, 1.0f), 0.0f);
   const float L = __builtin_fmaf(x - kWqAxisErr, half_hi(w9), -1.2e-5f);
-  const bool back = HRT_WQ_CONE && L > 0.0f && L * L > __builtin_fmaf(q2 + 3e-6f, half_lo(w10), 0.0f);
-#else
-  const float s_up = __builtin_amdgcn_sqrtf(fmaxf(__builtin_fmaf(-xa, xa, 1.0f), 0.0f)) + 1.2e-6f;
-  const bool back = HRT_WQ_CONE && (x - kWqAxisErr) * half_hi(w9) - s_up * wq_sin_up(w10) - 1e-6f > 1e-5f;
-#endif
-#if !HRT_WQ_BRANCHLESS
-  if (back) return false;
-#endif
+  const bool back = L > 0.0f && L * L > __builtin_fmaf(q2 + 3e-6f, half_lo(w10), 0.0f);
   float Rm = q.R;
   if constexpr (NodeR) {  // trace_bundle_wq_nr (HRT_OPT_WQ_NODE_RADIUS)
     // R for this member: the ray origin's distance to the farthest corner of its box (every vertex
@@ -1666,15 +1619,9 @@ __device__ __forceinline__ bool wq_member_visit(const float4& N0, const float4& 
   const float tn = fmaxf(fmaxf(-q.abs_t, fminf(tx0, tx1)), fmaxf(fminf(ty0, ty1), fminf(tz0, tz1)));
   const float tf = fminf(fminf(t_hi, fmaxf(tx0, tx1)), fminf(fmaxf(ty0, ty1), fmaxf(tz0, tz1)));
   t_near = tn;
-#if HRT_WQ_BRANCHLESS && HRT_WQ_FMA_SLACK
   // the 1e-6 relative slacks as fmas (one rounding fewer each; the products' roundings were far inside
   // the slacks either way)
   return !back & !(__builtin_fmaf(-fabsf(tn), 1e-6f, tn) > __builtin_fmaf(fabsf(tf), 1e-6f, tf) + 2.0f * q.sig);
-#elif HRT_WQ_BRANCHLESS
-  return !back & !((tn - fabsf(tn) * 1e-6f) > (tf + fabsf(tf) * 1e-6f) + 2.0f * q.sig);  // NaN -> visit
-#else
-  return !((tn - fabsf(tn) * 1e-6f) > (tf + fabsf(tf) * 1e-6f) + 2.0f * q.sig);  // NaN -> visit
-#endif
 }
 
 // Exact reference test (raytracing.glsl:213-241) of BVH leaf prim record (a, -) (e1, -) (e2, -) (n, -):
@@ -1686,7 +1633,6 @@ __device__ __forceinline__ bool wq_tri_accept(const float4& A, const float4& B, 
   const f3 ao = o - mk(A.x, A.y, A.z);
   TriPre q;
   q.num_t = dot(ao, n);
-#if HRT_WQ_TRI_SELECT
   // the three rejections as one predicate (no early-out branches: in a step of 64 different pairs they
   // almost never skip the whole wave)
   const float dn = dot(d, n);
@@ -1695,16 +1641,6 @@ __device__ __forceinline__ bool wq_tri_accept(const float4& A, const float4& B, 
   q.num_v = dot(mk(B.x, B.y, B.z), dao);
   q.det = -dn;
   if (!(q.num_t > 0.0f) | !(dn < 0.0f) | pre_reject(q, best_k)) return false;
-#else
-  if (!(q.num_t > 0.0f)) return false;
-  const float dn = dot(d, n);
-  if (!(dn < 0.0f)) return false;
-  const f3 dao = cross(ao, d);
-  q.num_u = dot(mk(C.x, C.y, C.z), dao);
-  q.num_v = dot(mk(B.x, B.y, B.z), dao);
-  q.det = -dn;
-  if (pre_reject(q, best_k)) return false;
-#endif
   const float inv_det = 1.0f / q.det;
   dist = q.num_t * inv_det;
   const float u = q.num_u * inv_det;
@@ -1727,8 +1663,20 @@ __device__ __forceinline__ float wq_slot_t(const WqLds& wq, uint32_t r) {
 // pair stacks: the lanes with `push` append v in lane order at the wave-uniform top n
 __device__ __forceinline__ void wq_push(uint32_t* st, uint32_t& n, bool push, uint32_t v) {
   const unsigned long long b = __ballot(push);
-  if (push) lds_put(&st[n + lanes_below(b)], v);
+  if (push) lds_put(&st[lanes_below_from(b, n)], v);
   n += (uint32_t)__popcll(b);
+}
+// One step's pops (world_hit_bounce_wq): lanes [0, nn) read the node stack's entries nc .. nc + nn - 1,
+// lanes [nn, nn + tn) the triangle stack's tc .. tc + tn - 1 (nc, tc: the tops after the pops; nn + tn
+// <= 64), every other lane gets `idle`.  One load at a selected address and one select: the same words
+// as a load per kind under its own branch (three exec splits per step), and a lane of neither kind
+// reads the triangle stack's word 0 (always allocated: its capacity is at least 128) and drops it.
+__device__ __forceinline__ uint32_t wq_pop(const uint32_t* ns, uint32_t nc, uint32_t nn, const uint32_t* ts,
+                                           uint32_t tc, uint32_t tn, uint32_t lane, uint32_t idle) {
+  const bool is_node = lane < nn, is_tri = lane - nn < tn;  // (lane - nn wraps past 2^31 for a node lane)
+  const uint32_t* p = is_node ? ns + (nc + lane) : ts + (is_tri ? tc + lane - nn : 0u);
+  const uint32_t v = lds_get(p);
+  return (is_node | is_tri) ? v : idle;
 }
 
 // Leaf prim k for ray r (origin o, direction d, mesh filter mask): test and lower the ray's slot.
@@ -1820,13 +1768,6 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   const float4* prims = K->bvh_prims;
   const float rel_t = K->bvh_rel_t, abs_coef = K->bvh_abs_coef;
   const uint32_t tcap = K->wq_tcap;
-#if HRT_WQ_BAND_EARLY
-  // the lane's direction-cell offsets requested first: the band rounds' first dependent global read (a
-  // random line of a structure far larger than an XCD's L2) then overlaps the spheres, the reciprocals,
-  // the meshes' AABB tests and the irregular list instead of starting after them
-  uint32_t cb0 = 0, cb1 = 0;
-  if (sec) band_cell(K, d, cb0, cb1);
-#endif
   spheres_first(sc, pc, sec, o, d, c);
   const f3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);  // the meshes' AABB tests and the traversal
   unsigned long long mask = 0ull;
@@ -1884,23 +1825,14 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   // no faster).
   if (__any(sec && mask)) {
     const BandCheck bc(d, -K->bvh_band_tau - 2e-5f, 3e-5f);  // see world_hit_bounce_bvh
-#if HRT_WQ_BAND_PLANE
     // Plane-side filter: an entry whose plane the ray starts behind, s = n^.o - n^.a < -ptol, cannot be
     // accepted.  The reference's num_t = dot(o - a, n) is within 4 eps (|o|_1 + |a|_1) |n| of |n| times
     // the exact n^.(o - a), and s within 6 eps (|o|_1 + |a|_1) of it (n^ within 2^-24 per component, the
     // fma chain, the host's rounding of n^.a, the subtraction), so s < -1e-5 (|o|_1 + max |a|_1) means
     // num_t < 0: dist <= 0, rejected (raytracing.glsl:233-238).  NaN -> kept.
     const float ptol = 1e-5f * (fabsf(o.x) + fabsf(o.y) + fabsf(o.z) + K->bvh_band_a1);
-#endif
     uint32_t b0 = 0, n = 0;
-#if HRT_WQ_BAND_EARLY
-    if (sec && mask) {
-      b0 = cb0;
-      n = cb1;
-    }
-#else
     if (sec && mask) band_cell(K, d, b0, n);
-#endif
     if (D && P.diag) {
       dg.band_len += n;
       band_lmax = n;
@@ -1931,31 +1863,6 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
     // round's normal load and before its check, so a round waits for the (cache-resident) normal
     // alone while the next round's (mostly L2-missing) entry load is in flight.  (The last round
     // fetches a round past the end too: a conditional load would make the normal's wait a full drain.)
-#if HRT_WQ_BAND_AHEAD > 1
-    // (A/B) the entry loads of the first HRT_WQ_BAND_AHEAD rounds issued together, then each round
-    // fetches the round that far ahead: the lists' random lines (a 74 MB structure no L2 holds) wait
-    // in parallel instead of one round at a time
-    uint32_t own_r[HRT_WQ_BAND_AHEAD], q_r[HRT_WQ_BAND_AHEAD];
-#pragma unroll
-    for (int i = 0; i < HRT_WQ_BAND_AHEAD; ++i) {
-      own_r[i] = 0u;
-      q_r[i] = 0u;
-      if (total > 64u * (uint32_t)i) fetch(64u * (uint32_t)i, own_r[i], q_r[i]);
-    }
-    for (uint32_t base = 0; base < total; base += 64u) {
-      if (tc + 64u > tcap) tri_step64();  // room for this round's pairs
-      const uint32_t own = own_r[0], q = q_r[0];
-      const float4 nh = nhat[q];
-#pragma unroll
-      for (int i = 0; i + 1 < HRT_WQ_BAND_AHEAD; ++i) {
-        own_r[i] = own_r[i + 1];
-        q_r[i] = q_r[i + 1];
-      }
-      uint32_t own_n, q_n;
-      fetch(base + 64u * HRT_WQ_BAND_AHEAD, own_n, q_n);
-      own_r[HRT_WQ_BAND_AHEAD - 1] = own_n;
-      q_r[HRT_WQ_BAND_AHEAD - 1] = q_n;
-#else
     uint32_t own = 0, q = 0;
     if (total) fetch(0u, own, q);
     for (uint32_t base = 0; base < total; base += 64u) {
@@ -1963,30 +1870,18 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
       const float4 nh = nhat[q];
       uint32_t own_n, q_n;
       fetch(base + 64u, own_n, q_n);
-#endif
       BandCheck oc = bc;
       oc.d = shfl3(bc.d, own);
-#if HRT_WQ_BAND_PLANE
       const f3 oo = shfl3(o, own);
       const float ot = lane_read(ptol, own);
       const float sp = __builtin_fmaf(oo.z, nh.z, __builtin_fmaf(oo.y, nh.y, oo.x * nh.x)) - nh.w;
       const bool push = base + lane < total && oc.in(nh) && !(sp < -ot);
-#else
-      const bool push = base + lane < total && oc.in(nh);
-#endif
       const unsigned long long pb = __ballot(push);
-#if HRT_WQ_PUSH_DUMP
-      // (non-pushing lanes store into the node stack's last word: empty during the band rounds)
-      lds_put(push ? &wq.ts[tc + lanes_below(pb)] : &wq.ns[wq.ncap - 1u], (q << 6) | own);
-#else
-      if (push) lds_put(&wq.ts[tc + lanes_below(pb)], (q << 6) | own);
-#endif
+      if (push) lds_put(&wq.ts[lanes_below_from(pb, tc)], (q << 6) | own);
       tc += (uint32_t)__popcll(pb);
       band_tests += push ? 1u : 0u;
-#if HRT_WQ_BAND_AHEAD <= 1
       own = own_n;
       q = q_n;
-#endif
     }
   }
   // pair traversal: the root is tested per lane, then (ray, node group) / (ray, triangle) pairs
@@ -2002,7 +1897,7 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   wave_handoff();  // the band rounds' marks (in the node stack's words) before the root pushes
   if (rvis && rcnt == 0u) lds_put(&wq.ns[lanes_below(rb)], (rinfo << 6) | lane);  // inner root: its children's group
   uint32_t nc = (uint32_t)__popcll(rb);
-  {  // leaf root (a scene of at most leaf-size triangles): its triangles, after any band pairs
+  if (__any(rcnt != 0u)) {  // leaf root (a scene of at most leaf-size triangles): its triangles, after any band pairs
     uint32_t tot;
     const uint32_t pre = tc + wave_scan_excl(rcnt, tot, 5u);
     for (uint32_t j = 0; j < rcnt; ++j) lds_put(&wq.ts[pre + j], (((rinfo & 0x07FFFFFFu) + j) << 6) | lane);
@@ -2017,18 +1912,18 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
     // (Measured, r02: filling a short node step's idle lanes with triangle pairs, or running triangle
     // steps from 32 waiting pairs, was no faster: 3.699 / 3.722 vs 3.692 ms, profiles/r02g_ab.txt.)
     const bool tri_step = tc >= HRT_WQ_TRI_MIN || nc == 0u;
-    const bool mixed = HRT_WQ_MIXED && !tri_step && tc > 0u && nc + tc <= 64u;
+    const bool mixed = !tri_step && tc > 0u && nc + tc <= 64u;
     const uint32_t tn = tri_step ? min(64u, tc) : (mixed ? tc : 0u);
     const uint32_t nn = tri_step ? 0u : min(64u, nc);
     tc -= tn;
     nc -= nn;
     node_pairs += nn;
     tri_pairs += tn;
-    const bool overflow = nc + width * nn > wq.ncap - (HRT_WQ_PUSH_DUMP ? 1u : 0u);  // wave-uniform
-    const bool is_node = lane < nn, is_tri = lane >= nn && lane < nn + tn;
+    const bool overflow = nc + width * nn > wq.ncap;  // wave-uniform
+    const bool is_node = lane < nn, is_tri = lane - nn < tn;  // (lane - nn wraps past 2^31 for a node lane)
     if (D && P.diag && nn) ++dg.wq_fill[(nn - 1u) >> 4];
     wave_handoff();  // the last step's pushes and slot lowerings before this step's pops and reads
-    const uint32_t e = is_node ? lds_get(&wq.ns[nc + lane]) : is_tri ? lds_get(&wq.ts[tc + lane - nn]) : lane;
+    const uint32_t e = wq_pop(wq.ns, nc, nn, wq.ts, tc, tn, lane, lane);
     const uint32_t r = e & 63u;
     const f3 ro = shfl3(o, r), rd = shfl3(d, r);
     const unsigned long long rm = mask_read(mask, r, K->pc.num_meshes);
@@ -2054,7 +1949,6 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
       const uint32_t g = e >> 6, fc = g & 0xFFFFu, gcnt = (g >> 16) + 1u;
       if (D && P.diag) dg.wq_members += gcnt;
       if (!overflow) {
-#if HRT_WQ_EARLY_REC
         // the first member pair's records are requested before the slot read: that read is an atomic
         // (lds_get), which the scheduler keeps every other memory access on its side of, so requested
         // after it they waited for the ray shuffles and the slot before being issued
@@ -2062,12 +1956,10 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
         const float4* nb0 = wq.nodes + 3 * (fc + min(1u, gcnt - 1u));
         const float4 A00 = na0[0], A01 = na0[1], A02 = na0[2], B00 = nb0[0], B01 = nb0[1], B02 = nb0[2];
         // (both pairs up front: 24 more live VGPRs, scratch 92 -> 160 B with spills in the fused loop)
-#endif
         const float t_hi = wq_slot_t(wq, r) * (1.0f + rel_t) + rabs;
         auto member = [&](const float4& N0, const float4& N1, const float4& N2, int k, bool valid = true) {
           float tnear;
           const uint32_t inf = __builtin_bit_cast(uint32_t, N2.w);
-#if HRT_WQ_SELECT
           // the outcome as selects: no branch, and the info word arrives with the record (a branch let
           // hipcc sink its LDS read into the kept path: one more dependent round trip per member)
           const bool vis = wq_member_visit<NodeR>(N0, N1, N2, rq, t_hi, tnear) & valid;
@@ -2075,48 +1967,23 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
           li[k] = (vis & leaf) ? inf : 0u;
           pe[k] = (vis & !leaf) ? ((inf << 6) | r) : ~0u;
           pk[k] = (vis & !leaf) ? -tnear : -kFltMax;
-#else
-          if (wq_member_visit<NodeR>(N0, N1, N2, rq, t_hi, tnear) & valid) {
-            if (inf >> 27) {
-              li[k] = inf;
-            } else {
-              pe[k] = (inf << 6) | r;
-              pk[k] = -tnear;
-            }
-          }
-#endif
         };
         // members two at a time, both records read up front (six LDS reads in flight); every group
         // has >= 2 members, and an odd count reads its last member twice and keeps one
-#if HRT_WQ_ALL4
-        // (A/B) every slot tested, the ones past the group's count masked (no per-pair branch)
+        // every slot is tested, the ones past the group's count masked (no per-pair branch)
 #pragma unroll
         for (int h = 0; h < (int)kWqSlots / 2; ++h) {
-#if HRT_WQ_EARLY_REC
           if (h == 0) {
             member(A00, A01, A02, 0);
             member(B00, B01, B02, 1);
             continue;
           }
-#endif
           const float4* na = wq.nodes + 3 * (fc + min(2u * h, gcnt - 1u));
           const float4* nb = wq.nodes + 3 * (fc + min(2u * h + 1u, gcnt - 1u));
           const float4 A0 = na[0], A1 = na[1], A2 = na[2], B0 = nb[0], B1 = nb[1], B2 = nb[2];
           member(A0, A1, A2, 2 * h, h == 0 || 2u * h < gcnt);
           member(B0, B1, B2, 2 * h + 1, h == 0 || 2u * h + 1u < gcnt);
         }
-#else
-#pragma unroll
-        for (int h = 0; h < (int)kWqSlots / 2; ++h) {
-          if (h == 0 || 2u * h < gcnt) {
-            const float4* na = wq.nodes + 3 * (fc + 2u * h);
-            const float4* nb = wq.nodes + 3 * (fc + min(2u * h + 1u, gcnt - 1u));
-            const float4 A0 = na[0], A1 = na[1], A2 = na[2], B0 = nb[0], B1 = nb[1], B2 = nb[2];
-            member(A0, A1, A2, 2 * h);
-            if (h == 0 || 2u * h + 1u < gcnt) member(B0, B1, B2, 2 * h + 1);
-          }
-        }
-#endif
         // the nearest member in the last slot (pushed last = popped first)
 #pragma unroll
         for (int st = 1; st < (int)kWqSlots; st *= 2)
@@ -2145,42 +2012,32 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
     for (int k = 0; k < (int)kWqSlots; ++k) {
       const bool push = pe[k] != ~0u;
       const unsigned long long bk = __ballot(push);
-#if HRT_WQ_PUSH_DUMP
-      // every lane stores (no branch): the others into the stack's last word, which no entry reaches
-      // (the overflow test keeps nc + width nn below ncap)
-      lds_put(&wq.ns[push ? nc + lanes_below(bk) : wq.ncap - 1u], pe[k]);
-#else
-      if (push) lds_put(&wq.ns[nc + lanes_below(bk)], pe[k]);
-#endif
+      if (push) lds_put(&wq.ns[lanes_below_from(bk, nc)], pe[k]);
       nc += (uint32_t)__popcll(bk);
     }
     // kept leaves' triangles: exclusive prefix of the per-lane counts (0..16)
     uint32_t cnt = 0;
 #pragma unroll
     for (int k = 0; k < (int)kWqSlots; ++k) cnt += li[k] >> 27;
+    // (a step that kept no leaf -- the upper levels of every batch -- skips the scan and the pushes: the
+    // scan of all-zero counts gives tot = 0 and no lane has an entry, so the stacks are left the same)
+    if (!__any(cnt != 0u)) continue;
     uint32_t tot;
     const uint32_t pre = wave_scan_excl(cnt, tot, 5u);
     if (tc + tot <= tcap) {  // wave-uniform
       uint32_t at = tc + pre;
-#if HRT_WQ_LEAF_FLAT
       // one loop over the lane's kept triangles (slot of entry j by its running start, selects),
       // instead of a loop per slot
       const uint32_t c0 = li[0] >> 27, c1 = li[1] >> 27, c2 = li[2] >> 27;
       const uint32_t s1 = c0, s2 = s1 + c1, s3 = s2 + c2;
       const uint32_t f0 = li[0] & 0x07FFFFFFu, f1 = (li[1] & 0x07FFFFFFu) - s1, f2 = (li[2] & 0x07FFFFFFu) - s2,
                      f3 = (li[3] & 0x07FFFFFFu) - s3;
+      // (the slot picked by a two-level select -- s1 <= s2 <= s3: j >= s2 leaves f2 / f3 by s3, j < s2
+      // leaves f0 / f1 by s1 -- whose two inner selects do not wait for each other)
       for (uint32_t j = 0; j < cnt; ++j) {
-        const uint32_t f = j >= s3 ? f3 : j >= s2 ? f2 : j >= s1 ? f1 : f0;
+        const uint32_t f = j >= s2 ? (j >= s3 ? f3 : f2) : (j >= s1 ? f1 : f0);
         lds_put(&wq.ts[at + j], ((f + j) << 6) | r);
       }
-#else
-#pragma unroll
-      for (int k = 0; k < (int)kWqSlots; ++k) {
-        const uint32_t c = li[k] >> 27, first = li[k] & 0x07FFFFFFu;
-        for (uint32_t j = 0; j < c; ++j) lds_put(&wq.ts[at + j], ((first + j) << 6) | r);
-        at += c;
-      }
-#endif
       tc += tot;
     } else {  // a burst of kept leaves beyond the triangle stack: each lane tests its own in place
 #pragma unroll
@@ -2319,9 +2176,6 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     const float4 rc = kargs()->rays[id];
     centre = mk(rc.x, rc.y, rc.z);
   }
-#if !HRT_RAYGEN_KARGS
-  const f3 root = mk(pc.cam_pos[0], pc.cam_pos[1], pc.cam_pos[2]);
-#endif
 #if HRT_TL_PREPASS
   // a whole tile's item: the list the launch's tile_lists kernel built for the tile (the same function of
   // the same inputs -- camera, the tile's ray centres, the camera lists -- as building it here, which the
@@ -2432,17 +2286,12 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
         done = true;
       } else {
         ++sample;
-#if HRT_RAYGEN_KARGS
         // the camera (matrix, jitter, position) read at the sample's start (kargs): 13 values not held
         // in SGPRs across the loop
         const KArgs K = kargs();
         const f3 dir = get_ray_dir(K->pc, centre, state);
         p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), mk(K->pc.cam_pos[0], K->pc.cam_pos[1], K->pc.cam_pos[2]),
                  normalize_fl(dir), 0, true};
-#else
-        const f3 dir = get_ray_dir(pc, centre, state);
-        p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), root, normalize_fl(dir), 0, true};
-#endif
       }
     }
     const bool ready = !done && p.bounce == 0;  // a primary segment to run
@@ -2468,7 +2317,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (co.w == 0) co.work += 2u + (any_prim ? 1u + (tl.ok ? tl.n : 64u) : 0u);  // shading, primary list
     if (any_prim) {
       if (tl.ok) {
-        const uint32_t tested = world_hit_tile(HRT_SHADE_KARGS ? kscene() : sc, P, tl, prim, p.pos, p.dir, tests, c);
+        const uint32_t tested = world_hit_tile(kscene(), P, tl, prim, p.pos, p.dir, tests, c);
         if (D && P.diag) {
           dg.prim_considered += tl.n;
           dg.prim_survivors += tested;
@@ -2481,7 +2330,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (run_sec) {
       if (HRT_BOUNCE_PRIO && !co.hot) __builtin_amdgcn_s_setprio(HRT_BOUNCE_PRIO);
       if constexpr (is_wq(Bounce)) {
-        world_hit_bounce_wq<D, Bounce == kBounceWqR>(HRT_SHADE_KARGS ? kscene() : sc, P, bsrc, sec, p.pos, p.dir, tests,
+        world_hit_bounce_wq<D, Bounce == kBounceWqR>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
                                                      c, dg);
       } else if constexpr (Bounce == kBounceBvh) {
         world_hit_bounce_bvh<D>(sc, P, bsrc, sec, p.pos, p.dir, tests, c, dg);
@@ -2495,7 +2344,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (D && P.diag) t2 = __builtin_readcyclecounter();
     if (prim || sec) {
       ++segs;
-      const bool ended = shade_step(HRT_SHADE_KARGS ? kscene() : sc, pc, p, c, state);
+      const bool ended = shade_step(kscene(), pc, p, c, state);
       ++p.bounce;
       if (ended || p.bounce > pc.max_bounces) {
         colour = colour + p.light * p.colour;
@@ -3399,7 +3248,8 @@ __global__ __launch_bounds__(64) void band_flatten_check(const uint32_t* n_in, c
 }
 
 // hrt_debug_wq_protocol: the pair traversal's LDS handoffs on a scripted run of one wave -- per round,
-// the top take[r] entries popped (lane l < take reads entry n - take + l), each lane's slot read and
+// the top take[r] entries popped (lane l < take reads entry n - take + l; with take = nn | tn << 8 the
+// step's mixed pop, wq_pop: nn node-kind lanes, then tn triangle-kind lanes), each lane's slot read and
 // lowering of slot tgt (tgt >= 64: none), then the lanes' pushes (lane l pushes cnt[r][l] <= 4 entries
 // (r << 16 | l << 8 | k), slot-major as the node steps push) -- in the product kernel's order, with
 // its helpers (wq_push, lds_get, wq_slot_*, wave_handoff).
@@ -3416,10 +3266,13 @@ __global__ __launch_bounds__(64) void wq_protocol_check(uint32_t rounds, const u
   wave_handoff();
   uint32_t n = 0;
   for (uint32_t r = 0; r < rounds; ++r) {
-    const uint32_t tk = min(take[r], n);
-    n -= tk;
+    // take[r] = nn | tn << 8: the top nn entries to lanes [0, nn) as a step's node pairs, the tn below
+    // them to lanes [nn, nn + tn) as its triangle pairs (one stack standing for both: wq_pop's two ranges)
+    const uint32_t nn = min(take[r] & 0xFFu, min(n, 64u));
+    const uint32_t tn = min(take[r] >> 8, min(n - nn, 64u - nn));
+    n -= nn + tn;
     wave_handoff();
-    popped[r * 64u + lane] = lane < tk ? lds_get(&st[n + lane]) : ~0u;
+    popped[r * 64u + lane] = wq_pop(st, n + tn, nn, st, n, tn, lane, ~0u);
     const uint32_t t = tgt[r * 64u + lane];
     if (t < 64u) {
       seen[r * 64u + lane] = lds_get(&slot[t]);

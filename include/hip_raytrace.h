@@ -587,7 +587,9 @@ hrt_status hrt_debug_band_flatten(int device, const uint32_t n[64], const uint32
 /* Test support: the pair traversal's cross-lane LDS handoffs (BUNDLE_WQ's stacks and closest-hit slots) on
  * a scripted run of one wave of 64 lanes over `rounds` <= 1024 rounds.  Slot l starts at seed[l].  Round r:
  * the top min(take[r], depth) stack entries are popped (popped[r * 64 + l] = the entry lane l < take
- * read, else 0xFFFFFFFF); lane l with tgt[r * 64 + l] < 64 reads that slot (seen[r * 64 + l]) and lowers it
+ * read, else 0xFFFFFFFF; take[r] = nn | tn << 8 pops as a mixed step does: the top nn <= 64 entries go to
+ * lanes [0, nn) in stack order, the tn <= 64 - nn entries below them to lanes [nn, nn + tn), each count
+ * clamped to what the stack holds); lane l with tgt[r * 64 + l] < 64 reads that slot (seen[r * 64 + l]) and lowers it
  * to val[r * 64 + l] (u64 minimum); then lane l pushes cnt[r * 64 + l] <= 4 entries (r << 16 | l << 8 | k),
  * k-major over the lanes in lane order (while the stack holds at most 8192 - 256).  slots[l] = the final
  * slots, *depth = the final stack depth. */

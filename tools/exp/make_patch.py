@@ -50,34 +50,34 @@ __device__ __forceinline__ void exp_use(float v) { asm volatile("; use %0" ::"v"
         }
 #endif
 '''),
-    ("        world_hit_tile(HRT_SHADE_KARGS ? kscene() : sc, P, tl, prim, p.pos, p.dir, tests, c);\n",
-     '''        world_hit_tile(HRT_SHADE_KARGS ? kscene() : sc, P, tl, prim, p.pos, p.dir, tests, c);
+    ("        world_hit_tile(kscene(), P, tl, prim, p.pos, p.dir, tests, c);\n",
+     '''        world_hit_tile(kscene(), P, tl, prim, p.pos, p.dir, tests, c);
 #if defined(HRT_EXP_TWICE) && HRT_EXP_TWICE == 1
         {
           const float z = exp_zero();
           Closest c2{kFltMax, 0, 0u, 0u};
           uint32_t t2 = 0;
-          world_hit_tile(HRT_SHADE_KARGS ? kscene() : sc, P, tl, prim, p.pos, mk(p.dir.x + z, p.dir.y + z, p.dir.z + z),
+          world_hit_tile(kscene(), P, tl, prim, p.pos, mk(p.dir.x + z, p.dir.y + z, p.dir.z + z),
                          t2, c2);
           exp_use(c2.t + (float)t2 + (float)c2.idx);
         }
 #endif
 '''),
     ('''      if constexpr (is_wq(Bounce)) {
-        world_hit_bounce_wq<D, Bounce == kBounceWqR>(HRT_SHADE_KARGS ? kscene() : sc, P, bsrc, sec, p.pos, p.dir, tests,
+        world_hit_bounce_wq<D, Bounce == kBounceWqR>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
                                                      c, dg);
 ''', '''      if constexpr (is_wq(Bounce)) {
 #if defined(HRT_EXP_TWICE) && HRT_EXP_TWICE == 5
         const Closest c_in = c;
 #endif
-        world_hit_bounce_wq<D, Bounce == kBounceWqR>(HRT_SHADE_KARGS ? kscene() : sc, P, bsrc, sec, p.pos, p.dir, tests,
+        world_hit_bounce_wq<D, Bounce == kBounceWqR>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
                                                      c, dg);
 #if defined(HRT_EXP_TWICE) && HRT_EXP_TWICE == 5
         {
           const float z = exp_zero();
           Closest c2 = c_in;
           uint32_t t2 = 0;
-          world_hit_bounce_wq<D, Bounce == kBounceWqR>(HRT_SHADE_KARGS ? kscene() : sc, P, bsrc, sec, p.pos,
+          world_hit_bounce_wq<D, Bounce == kBounceWqR>(kscene(), P, bsrc, sec, p.pos,
                                                        mk(p.dir.x + z, p.dir.y + z, p.dir.z + z), t2, c2, dg);
           exp_use(c2.t + (float)t2 + (float)c2.idx);
         }
@@ -96,7 +96,7 @@ __device__ __forceinline__ void exp_use(float v) { asm volatile("; use %0" ::"v"
         Path p2 = p;
         p2.dir.x = p2.dir.x + exp_zero();
         uint32_t s2 = state + (uint32_t)exp_zero();
-        exp_use((shade_step(HRT_SHADE_KARGS ? kscene() : sc, pc, p2, c, s2) ? 1.0f : 0.0f) + p2.dir.x + p2.dir.y +
+        exp_use((shade_step(kscene(), pc, p2, c, s2) ? 1.0f : 0.0f) + p2.dir.x + p2.dir.y +
                 p2.dir.z + p2.light.x + p2.colour.y);
       }
 #endif
