@@ -5,7 +5,7 @@ accumulator (assets/image_combiner.glsl), plus the present pass into caller memo
 (include/hip_raytrace.h).  See DESIGN.md.
 """
 from . import _lib
-from .app import RayTracingApp, compute_n_then_render, compute_then_render
+from .app import RayTracingApp, compute_n_then_render, compute_then_render, compute_until_then_render
 from .pipeline import (DiffusePipeline, HrtContext, Image, PresentTarget, RayTracePipeline, RayTracerSettings,
                        RenderPassOverFrame, create_rays, sphere_records, transform_meshes, view_matrix)
 from .scene import (Camera, CustomMaterial, InvisLightMaterial, LambertianMaterial, LightMaterial, Mesh,
@@ -14,7 +14,7 @@ from .scenes import PRESETS, load_box_scene, load_cave_scene, load_cube_scene, l
     load_spheres_scene, make_app, preset, scaled_preset
 
 __all__ = [
-    "RayTracingApp", "compute_then_render", "compute_n_then_render", "DiffusePipeline", "HrtContext", "Image",
+    "RayTracingApp", "compute_then_render", "compute_n_then_render", "compute_until_then_render", "DiffusePipeline", "HrtContext", "Image",
     "RayTracePipeline", "RayTracerSettings", "create_rays", "sphere_records", "transform_meshes", "view_matrix",
     "Camera", "CustomMaterial", "InvisLightMaterial", "LambertianMaterial", "LightMaterial", "Mesh", "MetalMaterial",
     "RayTracingMesh", "Sphere", "get_null_mesh", "get_null_sphere", "load_asset", "load_obj", "PRESETS",

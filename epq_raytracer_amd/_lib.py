@@ -76,6 +76,29 @@ class PresentInfo(ctypes.Structure):
 
 assert ctypes.sizeof(PresentInfo) == 24
 
+
+class FoldRecord(ctypes.Structure):
+    """hrt_fold_record: what one fold did to the displayed image (24 bytes)."""
+
+    _fields_ = [("frame", c_uint32), ("changed_pixels", c_uint32), ("max_delta", c_uint32), ("reserved", c_uint32),
+                ("abs_delta_sum", c_uint64)]
+
+
+class SettleRule(ctypes.Structure):
+    """hrt_settle_rule: when hrt_compute_until stops (16 bytes)."""
+
+    _fields_ = [("max_changed_pixels", c_uint32), ("max_delta", c_uint32), ("quiet_frames", c_uint32),
+                ("flags", c_uint32)]
+
+
+assert ctypes.sizeof(FoldRecord) == 24 and ctypes.sizeof(SettleRule) == 16
+FOLD_RECORD_DTYPE = np.dtype([("frame", "<u4"), ("changed_pixels", "<u4"), ("max_delta", "<u4"), ("reserved", "<u4"),
+                              ("abs_delta_sum", "<u8")])
+assert FOLD_RECORD_DTYPE.itemsize == 24
+FOLD_RECORD_RING = 1024      # HRT_FOLD_RECORD_RING
+RGBA8_FREEZE_FRAME = 510     # HRT_RGBA8_FREEZE_FRAME
+RULE_ANY = 0xFFFFFFFF        # a settle-rule bound that is disabled
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 HRT_OK = 0
 STATUS_NAMES = {0: "HRT_OK", 1: "HRT_ERR_INVALID_ARGUMENT", 2: "HRT_ERR_NO_DEVICE", 3: "HRT_ERR_OUT_OF_MEMORY",
@@ -90,7 +113,7 @@ PRESENT_RING = 8  # present tickets in flight per context
 OPT_KERNEL_VARIANT, OPT_COUNTERS, OPT_SECONDARY_BATCH, OPT_BVH_LEAF_SIZE = 1, 2, 3, 4
 OPT_SPLIT, OPT_SPLIT_FACTOR, OPT_PRIORITY, OPT_GRID_CUS, OPT_COOP, OPT_WQ_NODE_CAP, OPT_PROBE = 5, 6, 7, 8, 9, 10, 11
 OPT_FRAMES_PER_LAUNCH, OPT_OVERLAP, OPT_BUSY_SPLIT, OPT_BVH_WIDTH, OPT_WQ_NODE_RADIUS = 12, 13, 14, 15, 16
-OPT_COMM_TIMEOUT_MS, OPT_DEFER_COMBINE = 17, 18
+OPT_COMM_TIMEOUT_MS, OPT_DEFER_COMBINE, OPT_FOLD_RECORDS = 17, 18, 19
 DEBUG_OPT_FAIL_ALLOC = 1001  # libhip_raytrace_debug.so only
 DEBUG_OPT_WQ_TRI_CAP = 1002  # libhip_raytrace_debug.so only
 DEBUG_OPT_GRAB_RUNS = 1003  # libhip_raytrace_debug.so only
@@ -137,6 +160,7 @@ SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh
 # Every symbol include/*.h declares (tests/test_abi.py checks the export table against this).
 EXPORTED_SYMBOLS = (
     "hrt_abi_version", "hrt_build_id", "hrt_debug_build", "hrt_debug_check_guards", "hrt_create", "hrt_destroy", "hrt_set_scene", "hrt_trace", "hrt_accumulate", "hrt_compute_n",
+    "hrt_compute_until", "hrt_get_fold_records",
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
@@ -192,6 +216,9 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_trace": (c_int32, [P, POINTER(PushConstants)]),
         "hrt_accumulate": (c_int32, [P, c_uint32]),
         "hrt_compute_n": (c_int32, [P, POINTER(PushConstants), c_uint32]),
+        "hrt_compute_until": (c_int32, [P, POINTER(PushConstants), c_uint32, POINTER(SettleRule), POINTER(c_uint32),
+                                        POINTER(c_uint32)]),
+        "hrt_get_fold_records": (c_int32, [P, P, c_uint32, POINTER(c_uint32), POINTER(c_uint64)]),
         "hrt_read_image": (c_int32, [P, c_uint32, c_uint32, P, c_size_t]),
         "hrt_load_accumulator": (c_int32, [P, c_uint32, P, c_size_t]),
         "hrt_get_layout": (c_int32, [P, POINTER(Layout)]),

@@ -95,3 +95,18 @@ def compute_n_then_render(app: RayTracingApp, num_renders: int) -> None:
         app.frame += num_renders
     if render is not None:
         render(diffuse.image())
+
+
+def compute_until_then_render(app: RayTracingApp, max_renders: int, **rule):
+    """compute_n_then_render that stops when the image settles: one hrt_compute_until call of at most
+    max_renders frames under the rule (max_changed_pixels, max_delta, quiet_frames: HrtContext.compute_until),
+    then one present.  ``app.frame`` advances by the frames folded.  Returns (frames_done, settled)."""
+    raytrace, diffuse, render = app.pipeline
+    if diffuse.ctx is not raytrace.ctx:
+        raise ValueError("the trace and the accumulator must share one context")
+    done, settled = raytrace.ctx.compute_until(raytrace.push_constants(app.camera, app.frame, False), max_renders,
+                                               **rule)
+    app.frame += done
+    if render is not None:
+        render(diffuse.image())
+    return done, settled

@@ -172,6 +172,30 @@ const void* local_image(hrt_context* ctx, uint32_t image_id) {
   return trace_image(ctx);
 }
 
+// HRT_OPT_FOLD_RECORDS = 1: the fold of nf frames (image f of the stack = frame frame0 + f) into the
+// accumulator by the recording kernel, appending nf records to the ring -- the slots zeroed on the stream
+// first, their frame numbers kept on the host.  A fold may wrap the ring's end.
+hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0) {
+  const size_t np = ctx->npix(), fb = np * ctx->px_bytes();
+  const uint32_t ring = HRT_FOLD_RECORD_RING;
+  for (uint32_t done = 0; done < nf;) {  // (a launch's frames have a slot each)
+    const uint32_t n = std::min(nf - done, ring), slot0 = (uint32_t)(ctx->fold_total % ring);
+    const uint32_t head = std::min(n, ring - slot0);
+    HRT_HIP(ctx, hipMemsetAsync(ctx->fold_ring + slot0, 0, (size_t)head * sizeof(hrt_fold_record), ctx->stream));
+    if (n > head)
+      HRT_HIP(ctx, hipMemsetAsync(ctx->fold_ring, 0, (size_t)(n - head) * sizeof(hrt_fold_record), ctx->stream));
+    for (uint32_t f = 0; f < n; ++f) ctx->fold_frame[(slot0 + f) % ring] = frame0 + done + f;
+    const char* base = static_cast<const char*>(stack) + (size_t)done * fb;
+    HRT_HIP(ctx, launch_fold_records(ctx->accum8, ctx->accum8 ? reinterpret_cast<const uint32_t*>(base) : nullptr,
+                                     ctx->accum32, ctx->accum32 ? reinterpret_cast<const float4*>(base) : nullptr, np,
+                                     ctx->real_pix(), n, frame0 + done, true, ctx->fold_ring, slot0, ctx->num_cus,
+                                     ctx->stream));
+    ctx->fold_total += n;
+    done += n;
+  }
+  return HRT_OK;
+}
+
 hrt_status flush_combines(hrt_context* ctx) {
   if (ctx->pend.empty()) return HRT_OK;
   // the folds read slots that traces on every lane wrote: after each lane's latest trace
@@ -184,9 +208,13 @@ hrt_status flush_combines(hrt_context* ctx) {
            ctx->pend[j + 1].frame == ctx->pend[j].frame + 1)
       ++j;
     char* base = static_cast<char*>(ctx->ring) + (size_t)ctx->pend[i].slot * fb;
-    HRT_HIP(ctx, launch_accumulate_frames(ctx->accum8, ctx->accum8 ? reinterpret_cast<const uint32_t*>(base) : nullptr,
-                                          ctx->accum32, ctx->accum32 ? reinterpret_cast<const float4*>(base) : nullptr,
-                                          np, (uint32_t)(j - i + 1), ctx->pend[i].frame, ctx->stream));
+    if (ctx->fold_on) {
+      if ((st = fold_recorded(ctx, base, (uint32_t)(j - i + 1), ctx->pend[i].frame)) != HRT_OK) return st;
+    } else {
+      HRT_HIP(ctx, launch_accumulate_frames(ctx->accum8, ctx->accum8 ? reinterpret_cast<const uint32_t*>(base) : nullptr,
+                                            ctx->accum32, ctx->accum32 ? reinterpret_cast<const float4*>(base) : nullptr,
+                                            np, (uint32_t)(j - i + 1), ctx->pend[i].frame, ctx->stream));
+    }
     i = j + 1;
   }
   ctx->pend.clear();
@@ -429,6 +457,8 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->timeline_count);
   free_dev(ctx, ctx->frame_stack);
   free_dev(ctx, ctx->ring);
+  free_dev(ctx, ctx->fold_ring);
+  free_dev(ctx, ctx->fold_scratch);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -945,6 +975,34 @@ static hipError_t stack_alloc(hrt_context* ctx, void** p, size_t bytes) {
   return hrt::dev_alloc(ctx, p, bytes);
 }
 
+// hrt_compute_n / hrt_compute_until: grows the frame stack towards a whole launch of cap frames for a call of
+// n frames (the policy is described in hrt_compute_n).  Never an error for a stack that does not fit.
+static hrt_status grow_frame_stack(hrt_context* ctx, uint32_t cap, uint32_t n, size_t np, size_t px_bytes) {
+  if (ctx->frame_stack_frames < cap) {
+    const uint32_t need = std::min(cap, n);
+    void* fresh = nullptr;
+    uint32_t fresh_frames = 0;
+    auto try_alloc = [&](uint32_t frames) {
+      if (stack_alloc(ctx, &fresh, (size_t)frames * np * px_bytes) == hipSuccess) {
+        fresh_frames = frames;
+        return true;
+      }
+      (void)hipGetLastError();  // (a failed allocation is not a sticky error)
+      fresh = nullptr;
+      return false;
+    };
+    if (ctx->frame_stack_failed != cap && !try_alloc(cap)) ctx->frame_stack_failed = cap;
+    if (!fresh && ctx->frame_stack_frames < need) (void)try_alloc(need);
+    if (fresh) {
+      HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      free_dev(ctx, ctx->frame_stack);
+      ctx->frame_stack = fresh;
+      ctx->frame_stack_frames = fresh_frames;
+    }
+  }
+  return HRT_OK;
+}
+
 extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* pc, uint32_t n) {
   if (!ctx || !pc) return HRT_ERR_INVALID_ARGUMENT;
   if (pc->init) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_n: init dispatches go through hrt_trace");
@@ -969,28 +1027,7 @@ extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* 
   // device, little free memory) the call's own min(cap, n) frames are allocated instead; where even those
   // do not fit, the call runs with the stack it has (more, shorter launches) or one launch per frame.
   // Never an error: the frames are the same bytes whatever the launches hold.
-  if (batch && ctx->frame_stack_frames < cap) {
-    const uint32_t need = std::min(cap, n);
-    void* fresh = nullptr;
-    uint32_t fresh_frames = 0;
-    auto try_alloc = [&](uint32_t frames) {
-      if (stack_alloc(ctx, &fresh, (size_t)frames * np * px_bytes) == hipSuccess) {
-        fresh_frames = frames;
-        return true;
-      }
-      (void)hipGetLastError();  // (a failed allocation is not a sticky error)
-      fresh = nullptr;
-      return false;
-    };
-    if (ctx->frame_stack_failed != cap && !try_alloc(cap)) ctx->frame_stack_failed = cap;
-    if (!fresh && ctx->frame_stack_frames < need) (void)try_alloc(need);
-    if (fresh) {
-      HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      free_dev(ctx, ctx->frame_stack);
-      ctx->frame_stack = fresh;
-      ctx->frame_stack_frames = fresh_frames;
-    }
-  }
+  if (batch && (st = grow_frame_stack(ctx, cap, n, np, px_bytes)) != HRT_OK) return st;
   const uint32_t lcap = batch ? std::min(cap, ctx->frame_stack_frames) : 1;  // frames per launch this call
   batch = batch && lcap > 1;
   for (uint32_t done = 0; done < n;) {
@@ -1007,7 +1044,10 @@ extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* 
     }
     if ((st = launch_frames(ctx, q, ctx->stream, 0)) != HRT_OK) return st;
     // DiffusePipeline::next_frame(frame) for each frame, in frame order: one pass over the stack
-    if (nf > 1)
+    if (ctx->fold_on) {
+      if ((st = hrt::fold_recorded(ctx, nf > 1 ? ctx->frame_stack : lane.image(), nf, q.pc.rng_offset)) != HRT_OK)
+        return st;
+    } else if (nf > 1)
       HRT_HIP(ctx, hrt::launch_accumulate_frames(ctx->accum8, q.img8, ctx->accum32, q.img32, np, nf, q.pc.rng_offset,
                                                  ctx->stream));
     else
@@ -1023,6 +1063,122 @@ extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* 
   ctx->cur_slot = -1;  // the trace image is lane 0's
   ctx->lane_used = true;
   return hrt::release_lane(ctx, 0);  // lane 0's next trace follows this loop
+}
+
+// hrt_compute_n's loop with a count pass between a launch's trace and its fold: the count pass runs the fold
+// chain over the launch's frames in registers and writes one record per frame into the scratch ring; the
+// host reads them (the call blocks here), extends the quiet run and folds only the frames up to the stop.
+extern "C" hrt_status hrt_compute_until(hrt_context* ctx, const hrt_push_constants* pc, uint32_t max_frames,
+                                        const hrt_settle_rule* rule, uint32_t* frames_done, uint32_t* settled) {
+  if (!ctx || !pc) return HRT_ERR_INVALID_ARGUMENT;
+  if (!rule || !frames_done)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_until: rule and frames_done must not be NULL");
+  if (rule->flags != 0) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_until: rule flags must be 0");
+  if (rule->quiet_frames == 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_until: rule quiet_frames must be at least 1");
+  if (pc->init) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_until: init dispatches go through hrt_trace");
+  if (ctx->comm)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT,
+                "hrt_compute_until: the context is joined to a communicator: a group-wide rule is not supported");
+  if (ctx->part_count > 1)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT,
+                "hrt_compute_until: a context of a row-tile partition (part_count > 1): the parts would stop at "
+                "different frames");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if ((st = check_dispatch(ctx, pc, "hrt_compute_until")) != HRT_OK) return st;
+  *frames_done = 0;
+  if (settled) *settled = 0;
+  if (max_frames == 0) return HRT_OK;
+  if (!ctx->fold_scratch)
+    HRT_HIP(ctx, hrt::dev_alloc(ctx, (void**)&ctx->fold_scratch, HRT_FOLD_RECORD_RING * sizeof(hrt_fold_record)));
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
+  hrt::TraceParams p = make_params(ctx, pc, 0);
+  hrt::Lane& lane = ctx->lane[0];
+  const size_t np = ctx->npix(), px_bytes = ctx->px_bytes(), fb = np * px_bytes;
+  // frames per launch as in hrt_compute_n (and one slot of the scratch ring each)
+  const uint32_t cap = (uint32_t)std::max<size_t>(
+      1, std::min<size_t>(std::min<uint32_t>(ctx->frames_per_launch, HRT_FOLD_RECORD_RING),
+                          ((size_t)1 << 30) / std::max<size_t>(fb, 1)));
+  bool batch = persistent_kernel(hrt::resolve_variant(p, ctx->variant)) && cap > 1 && max_frames > 1;
+  if (batch && (st = grow_frame_stack(ctx, cap, max_frames, np, px_bytes)) != HRT_OK) return st;
+  const uint32_t lcap = batch ? std::min(cap, ctx->frame_stack_frames) : 1;
+  std::vector<hrt_fold_record> recs(lcap);
+  uint32_t done = 0, quiet_run = 0;
+  bool stop = false;
+  while (done < max_frames && !stop) {
+    const uint32_t nf = std::min(lcap, max_frames - done), frame0 = pc->rng_offset + done;
+    hrt::TraceParams q = p;
+    q.pc.rng_offset = frame0;
+    q.n_frames = nf;
+    q.plan_valid = lane.plan_valid ? 1u : 0u;
+    if (nf > 1) {
+      q.img8 = lane.trace8 ? reinterpret_cast<uint32_t*>(ctx->frame_stack) : nullptr;
+      q.img32 = lane.trace32 ? reinterpret_cast<float4*>(ctx->frame_stack) : nullptr;
+    }
+    if ((st = launch_frames(ctx, q, ctx->stream, 0)) != HRT_OK) return st;
+    const char* stack = static_cast<const char*>(nf > 1 ? ctx->frame_stack : lane.image());
+    const uint32_t* stack8 = ctx->accum8 ? reinterpret_cast<const uint32_t*>(stack) : nullptr;
+    const float4* stack32 = ctx->accum32 ? reinterpret_cast<const float4*>(stack) : nullptr;
+    // the count pass, and its records on the host
+    HRT_HIP(ctx, hipMemsetAsync(ctx->fold_scratch, 0, (size_t)nf * sizeof(hrt_fold_record), ctx->stream));
+    HRT_HIP(ctx, hrt::launch_fold_records(ctx->accum8, stack8, ctx->accum32, stack32, np, ctx->real_pix(), nf, frame0,
+                                          false, ctx->fold_scratch, 0, ctx->num_cus, ctx->stream));
+    HRT_HIP(ctx, hipMemcpyAsync(recs.data(), ctx->fold_scratch, (size_t)nf * sizeof(hrt_fold_record),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t s = nf;  // frames of this launch to fold
+    for (uint32_t f = 0; f < nf; ++f) {
+      const bool quiet = recs[f].changed_pixels <= rule->max_changed_pixels && recs[f].max_delta <= rule->max_delta;
+      quiet_run = quiet ? quiet_run + 1 : 0;
+      if (quiet_run >= rule->quiet_frames) {
+        s = f + 1;
+        stop = true;
+        break;
+      }
+    }
+    // the ordinary fold of the first s frames
+    if (ctx->fold_on) {
+      if ((st = hrt::fold_recorded(ctx, stack, s, frame0)) != HRT_OK) return st;
+    } else if (s > 1) {
+      HRT_HIP(ctx, hrt::launch_accumulate_frames(ctx->accum8, stack8, ctx->accum32, stack32, np, s, frame0, ctx->stream));
+    } else {
+      HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, stack8, ctx->accum32, stack32, np, frame0, ctx->stream));
+    }
+    ctx->accumulates += s;
+    if (nf > 1)  // the trace image holds the last frame folded
+      HRT_HIP(ctx, hipMemcpyAsync(lane.image(), stack + (size_t)(s - 1) * fb, fb, hipMemcpyDeviceToDevice, ctx->stream));
+    done += s;
+  }
+  *frames_done = done;
+  if (settled) *settled = stop ? 1u : 0u;
+  ctx->cur_lane = 0;
+  ctx->cur_slot = -1;
+  ctx->lane_used = true;
+  return hrt::release_lane(ctx, 0);
+}
+
+extern "C" hrt_status hrt_get_fold_records(hrt_context* ctx, hrt_fold_record* out, uint32_t cap, uint32_t* count,
+                                           uint64_t* total) {
+  if (!ctx || !count || (cap != 0 && !out)) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = hrt_synchronize(ctx);  // (folds the deferred combines first)
+  if (st != HRT_OK) return st;
+  const uint32_t ring = HRT_FOLD_RECORD_RING;
+  const uint32_t n = (uint32_t)std::min<uint64_t>(cap, std::min<uint64_t>(ctx->fold_total, ring));
+  if (n != 0) {
+    std::vector<hrt_fold_record> all(ring);
+    HRT_HIP(ctx, hipMemcpy(all.data(), ctx->fold_ring, ring * sizeof(hrt_fold_record), hipMemcpyDeviceToHost));
+    for (uint32_t k = 0; k < n; ++k) {
+      const uint32_t slot = (uint32_t)((ctx->fold_total - n + k) % ring);
+      out[k] = all[slot];
+      out[k].frame = ctx->fold_frame[slot];
+      out[k].reserved = 0;
+    }
+  }
+  *count = n;
+  if (total) *total = ctx->fold_total;
+  return HRT_OK;
 }
 
 extern "C" hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame) {
@@ -1044,9 +1200,13 @@ extern "C" hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame) {
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // frames fold in call order
   if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
   void* img = hrt::trace_image(ctx);
-  HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, ctx->accum8 ? static_cast<uint32_t*>(img) : nullptr, ctx->accum32,
-                                      ctx->accum32 ? static_cast<float4*>(img) : nullptr, ctx->npix(), frame,
-                                      ctx->stream));
+  if (ctx->fold_on) {
+    if ((st = hrt::fold_recorded(ctx, img, 1, frame)) != HRT_OK) return st;
+  } else {
+    HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, ctx->accum8 ? static_cast<uint32_t*>(img) : nullptr, ctx->accum32,
+                                        ctx->accum32 ? static_cast<float4*>(img) : nullptr, ctx->npix(), frame,
+                                        ctx->stream));
+  }
   ctx->accumulates++;
   return hrt::release_lane(ctx, l);
 }
@@ -1259,8 +1419,9 @@ extern "C" hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, c
     if ((st = enqueue_present(ctx, info, dst)) != HRT_OK) return st;
     return ticket_end(ctx, ev, ticket);
   }
-  if (ctx->defer || info->width != ctx->width || info->height != ctx->local_rows) {
-    // the two passes: a deferred combine is folded by the present, a scaled target samples the new accumulator
+  if (ctx->defer || ctx->fold_on || info->width != ctx->width || info->height != ctx->local_rows) {
+    // the two passes: a deferred combine is folded by the present, a scaled target samples the new accumulator,
+    // a recorded fold (HRT_OPT_FOLD_RECORDS) is the recording combiner's
     if ((st = hrt_accumulate(ctx, frame)) != HRT_OK) return st;
     if ((st = enqueue_present(ctx, info, dst)) != HRT_OK) return st;
     return ticket_end(ctx, ev, ticket);
@@ -1670,6 +1831,18 @@ extern "C" hrt_status hrt_set_option(hrt_context* ctx, uint32_t key, int64_t val
       if (st == HRT_OK) st = hrt::flush_combines(ctx);
       if (st != HRT_OK) return st;
       ctx->defer = (uint32_t)value;
+      return HRT_OK;
+    }
+    case HRT_OPT_FOLD_RECORDS: {
+      if (value < 0 || value > 1) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "fold records must be 0 or 1");
+      hrt_status st = bind(ctx);
+      if (st == HRT_OK) st = hrt::flush_combines(ctx);  // (combines deferred so far fold under the old setting)
+      if (st != HRT_OK) return st;
+      if (value == 1 && !ctx->fold_ring)  // allocated here, so that no fold allocates
+        HRT_HIP(ctx, hrt::dev_alloc(ctx, (void**)&ctx->fold_ring, HRT_FOLD_RECORD_RING * sizeof(hrt_fold_record)));
+      if (value == 1) ctx->fold_frame.assign(HRT_FOLD_RECORD_RING, 0u);
+      ctx->fold_total = 0;  // the ring is empty: a slot is zeroed before the fold that uses it
+      ctx->fold_on = (uint32_t)value;
       return HRT_OK;
     }
     case HRT_OPT_COMM_TIMEOUT_MS:

@@ -196,12 +196,30 @@ struct hrt_context {
   hipEvent_t fold_done = nullptr;  // recorded on `stream` after the last fold (a slot's next trace waits)
   bool fold_set = false;
   uint32_t defer = 0;          // HRT_OPT_DEFER_COMBINE (off: measured slower, hip_raytrace.h)
+  // Fold records (HRT_OPT_FOLD_RECORDS, hrt_compute_until).  Record t (0-based since the option was set)
+  // lives in fold_ring[t % HRT_FOLD_RECORD_RING]: the host zeroes the slot on `stream` before the fold
+  // that adds its counts and keeps the slot's frame number in fold_frame.  fold_scratch is the ring of
+  // hrt_compute_until's count pass (slot f = frame f of the launch).  Both are allocated on first use.
+  hrt_fold_record* fold_ring = nullptr;
+  hrt_fold_record* fold_scratch = nullptr;
+  std::vector<uint32_t> fold_frame;
+  uint64_t fold_total = 0;
+  uint32_t fold_on = 0;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 
   std::string err;
 
   size_t npix() const { return (size_t)local_rows * width; }
+  // the pixels of the local rows whose global row is below height: a prefix of the local rows (the padding
+  // rows of a row-tile part follow them) -- what a fold record counts
+  size_t real_pix() const {
+    if (part_count <= 1) return npix();
+    uint32_t rows = 0;
+    for (uint32_t r = 0; r < local_rows; ++r)
+      if (((uint64_t)(r / row_tile) * part_count + part_index) * row_tile + r % row_tile < height) ++rows;
+    return (size_t)rows * width;
+  }
   size_t px_bytes() const { return mode == HRT_MODE_RGBA8 ? 4 : 16; }
   size_t num_tiles() const { return (size_t)((width + 7) / 8) * ((local_rows + 7) / 8); }
 };
@@ -221,6 +239,8 @@ hrt_status release_lane(hrt_context* ctx, int l);  // lane l's buffers are free 
 const void* local_image(hrt_context* ctx, uint32_t image_id);
 // Folds the deferred combines (hrt_context::pend) into the accumulator on ctx->stream.
 hrt_status flush_combines(hrt_context* ctx);
+// The recording fold of nf frames of a stack into the accumulator (HRT_OPT_FOLD_RECORDS = 1), on ctx->stream.
+hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0);
 // dst <- npix pixels at src (context format) converted to fmt via scratch, ordered on ctx->stream; blocking.
 hrt_status copy_frame_out(hrt_context* ctx, const void* src, size_t npix, uint32_t fmt, void* dst, void* scratch);
 // hrt_read_image on a context with a communicator (hrt_comm.cpp); arg = the caller's own argument

@@ -107,6 +107,14 @@ hipError_t launch_clear(uint32_t* img8, float4* img32, size_t npix, hipStream_t 
 // the nf frames of a stack (image f at f * npix) folded into the accumulator as frames frame0 + f
 hipError_t launch_accumulate_frames(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32,
                                    size_t npix, uint32_t nf, uint32_t frame0, hipStream_t stream);
+// The fold of launch_accumulate_frames (store) or its chain in registers only (!store) with one fold record
+// per frame: frame f's counts are ADDED to ring[(slot0 + f) % HRT_FOLD_RECORD_RING], which the caller zeroed
+// on the stream before (changed_pixels, max_delta and abs_delta_sum; the host keeps the frame numbers).
+// real_pix <= npix: the pixels that count.  nf <= HRT_FOLD_RECORD_RING.  A single-frame fold is nf == 1
+// with the trace image as the stack.  The grid is sized by num_cus, not by npix.
+hipError_t launch_fold_records(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32, size_t npix,
+                               size_t real_pix, uint32_t nf, uint32_t frame0, bool store, hrt_fold_record* ring,
+                               uint32_t slot0, uint32_t num_cus, hipStream_t stream);
 hipError_t launch_tri_normals(const hrt_triangle* tris, float4* nhat, uint32_t n, hipStream_t stream);
 // BUNDLE_WQ's per-cell band records from the offsets and the 16-bit lists (hrt_kernels.hip band_cell).
 hipError_t launch_band_records(const uint32_t* off, const uint32_t* band16, uint32_t* rec, uint32_t cells,

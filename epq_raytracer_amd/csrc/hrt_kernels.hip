@@ -3020,6 +3020,108 @@ __global__ __launch_bounds__(256) void accumulate_rgba32f(float4* cur, const flo
   cur[i] = combine_rgba32f(frame == 0 ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : cur[i], nw[i], frame);
 }
 
+// ---- fold records (HRT_OPT_FOLD_RECORDS, hrt_compute_until) -------------------------
+// The fold chain of accumulate_frames_* with, per frame, the record of what the fold did to the
+// DISPLAYED image: pixels whose displayed word changed, the byte sum of absolute differences, the
+// largest byte difference -- over the real pixels (i < real_pix; padding rows of a row-tile part are
+// folded but never counted).  All integers, so the sums do not depend on the order they are taken in.
+// Reduction: a wave ballots the changed lanes (no lane changed: nothing more for that frame), reduces
+// sum and maximum across its lanes, lane 0 adds them to the workgroup's per-frame LDS slots; after the
+// pixel walk the workgroup issues at most one global atomic triple (u32 add, u64 add, u32 max) per frame.
+// The grid is sized by the CU count (launch_fold_records) and strides over the pixels, so a frame's slot
+// sees at most 8 x CUs triples however large the image.  Store == false runs the chain in registers
+// only (hrt_compute_until's count pass).
+constexpr uint32_t kFoldMaxFrames = HRT_FOLD_RECORD_RING;  // per launch: the LDS slots
+static_assert((kFoldMaxFrames & (kFoldMaxFrames - 1u)) == 0, "the ring is indexed with a mask");
+__device__ __forceinline__ uint32_t displayed_word(uint32_t v) { return v; }
+__device__ __forceinline__ uint32_t displayed_word(float4 v) {  // f32_to_rgba8's word
+  return unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
+}
+__device__ __forceinline__ uint32_t fold_step(uint32_t v, uint32_t n, uint32_t frame, const float* tab) {
+#if HRT_COMBINE_FAST
+  return combine_rgba8_fast(v, n, frame, tab);
+#else
+  (void)tab;
+  return combine_rgba8(v, n, frame);
+#endif
+}
+__device__ __forceinline__ float4 fold_step(float4 v, float4 n, uint32_t frame, const float*) {
+  return combine_rgba32f(v, n, frame);
+}
+template <typename T>
+__device__ __forceinline__ T fold_zero();
+template <>
+__device__ __forceinline__ uint32_t fold_zero<uint32_t>() {
+  return 0u;
+}
+template <>
+__device__ __forceinline__ float4 fold_zero<float4>() {
+  return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+template <typename T, bool Store>
+__global__ __launch_bounds__(256) void fold_records(T* cur, const T* stack, size_t npix, size_t real_pix, uint32_t nf,
+                                                    uint32_t frame0, hrt_fold_record* ring, uint32_t slot0,
+                                                    uint32_t mask) {
+  __shared__ float tab[256];
+  __shared__ uint32_t s_cnt[kFoldMaxFrames], s_max[kFoldMaxFrames];
+  __shared__ unsigned long long s_sum[kFoldMaxFrames];
+  for (uint32_t f = threadIdx.x; f < nf; f += 256u) {
+    s_cnt[f] = 0u;
+    s_max[f] = 0u;
+    s_sum[f] = 0ull;
+  }
+  unorm8_table(tab);  // (and the barrier)
+  const uint32_t lane = threadIdx.x & 63u;
+  const size_t stride = (size_t)gridDim.x * 256u;
+  // (the walk is workgroup-uniform: every lane of a wave reaches the ballot and the shuffles)
+  for (size_t base = (size_t)blockIdx.x * 256u; base < npix; base += stride) {
+    const size_t i = base + threadIdx.x;
+    const bool in = i < npix, real = i < real_pix;
+    T v = in ? cur[i] : fold_zero<T>();
+    uint32_t d = displayed_word(v);
+    T nxt = in ? stack[i] : fold_zero<T>();
+    for (uint32_t f = 0; f < nf; ++f) {
+      const T n = nxt;
+      if (f + 1u < nf && in) nxt = stack[(size_t)(f + 1u) * npix + i];
+      v = fold_step(v, n, frame0 + f, tab);
+      const uint32_t dw = displayed_word(v);
+      const bool ch = real && dw != d;
+      const unsigned long long b = __ballot(ch);
+      if (b != 0ull) {
+        uint32_t sad = 0u, mx = 0u;
+        if (ch) {
+          sad = __builtin_amdgcn_sad_u8(dw, d, 0u);
+          const uint32_t b0 = __builtin_amdgcn_sad_u8(dw & 0xFFu, d & 0xFFu, 0u);
+          const uint32_t b1 = __builtin_amdgcn_sad_u8(dw & 0xFF00u, d & 0xFF00u, 0u);
+          const uint32_t b2 = __builtin_amdgcn_sad_u8(dw & 0xFF0000u, d & 0xFF0000u, 0u);
+          const uint32_t b3 = __builtin_amdgcn_sad_u8(dw >> 24, d >> 24, 0u);
+          mx = max(max(b0, b1), max(b2, b3));
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          sad += (uint32_t)__shfl_xor((int)sad, off, 64);
+          mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+        }
+        if (lane == 0u) {
+          atomicAdd(&s_cnt[f], (uint32_t)__popcll(b));
+          atomicAdd(&s_sum[f], (unsigned long long)sad);
+          atomicMax(&s_max[f], mx);
+        }
+      }
+      d = dw;
+    }
+    if (Store && in) cur[i] = v;
+  }
+  __syncthreads();
+  for (uint32_t f = threadIdx.x; f < nf; f += 256u) {
+    if (s_cnt[f] == 0u) continue;  // (a changed pixel has a byte difference >= 1: sum and maximum are 0 too)
+    hrt_fold_record* r = ring + ((slot0 + f) & mask);
+    atomicAdd(&r->changed_pixels, s_cnt[f]);
+    atomicAdd(reinterpret_cast<unsigned long long*>(&r->abs_delta_sum), s_sum[f]);
+    atomicMax(&r->max_delta, s_max[f]);
+  }
+}
+
 // format conversion for hrt_read_image
 __global__ __launch_bounds__(256) void rgba8_to_f32(const uint32_t* src, float4* dst, size_t npix) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3580,6 +3682,29 @@ hipError_t launch_accumulate_frames(uint32_t* cur8, const uint32_t* stack8, floa
     accumulate_frames_rgba8<<<blocks_for(npix), 256, 0, stream>>>(cur8, stack8, npix, nf, frame0);
   else
     accumulate_frames_rgba32f<<<blocks_for(npix), 256, 0, stream>>>(cur32, stack32, npix, nf, frame0);
+  return hipGetLastError();
+}
+
+hipError_t launch_fold_records(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32, size_t npix,
+                               size_t real_pix, uint32_t nf, uint32_t frame0, bool store, hrt_fold_record* ring,
+                               uint32_t slot0, uint32_t num_cus, hipStream_t stream) {
+  if (nf == 0) return hipSuccess;
+  if (nf > kFoldMaxFrames || !ring || real_pix > npix || npix == 0) return hipErrorInvalidValue;
+  // eight workgroups of four waves per CU (full occupancy beside 17 KiB of LDS each), never more than the pixels need
+  const unsigned int grid = std::min<unsigned int>(blocks_for(npix), std::max(1u, num_cus) * 8u);
+  const uint32_t mask = kFoldMaxFrames - 1u;
+  slot0 &= mask;
+  if (cur8) {
+    if (store)
+      fold_records<uint32_t, true><<<grid, 256, 0, stream>>>(cur8, stack8, npix, real_pix, nf, frame0, ring, slot0, mask);
+    else
+      fold_records<uint32_t, false><<<grid, 256, 0, stream>>>(cur8, stack8, npix, real_pix, nf, frame0, ring, slot0, mask);
+  } else {
+    if (store)
+      fold_records<float4, true><<<grid, 256, 0, stream>>>(cur32, stack32, npix, real_pix, nf, frame0, ring, slot0, mask);
+    else
+      fold_records<float4, false><<<grid, 256, 0, stream>>>(cur32, stack32, npix, real_pix, nf, frame0, ring, slot0, mask);
+  }
   return hipGetLastError();
 }
 

@@ -169,6 +169,28 @@ class HrtContext:
         """hrt_compute_n: n x (trace with rng_offset = pc.rng_offset + k, accumulate(that k))."""
         self._check(self.lib.hrt_compute_n(self.handle, ctypes.byref(pc), int(n)), "hrt_compute_n")
 
+    def compute_until(self, pc: _lib.PushConstants, max_frames: int, max_changed_pixels: int = _lib.RULE_ANY,
+                      max_delta: int = _lib.RULE_ANY, quiet_frames: int = 1):
+        """hrt_compute_until: compute_n stopped after the first run of quiet_frames consecutive quiet frames
+        (a frame is quiet when its fold record has changed_pixels <= max_changed_pixels and max_delta <=
+        max_delta).  Blocking.  Returns (frames_done, settled)."""
+        rule = _lib.SettleRule(int(max_changed_pixels), int(max_delta), int(quiet_frames), 0)
+        done, settled = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self.lib.hrt_compute_until(self.handle, ctypes.byref(pc), int(max_frames), ctypes.byref(rule),
+                                               ctypes.byref(done), ctypes.byref(settled)), "hrt_compute_until")
+        return done.value, bool(settled.value)
+
+    def fold_records(self, cap: int = _lib.FOLD_RECORD_RING, with_total: bool = False):
+        """hrt_get_fold_records: the newest min(cap, available) records (OPT_FOLD_RECORDS = 1), oldest first,
+        as a structured array (_lib.FOLD_RECORD_DTYPE); with_total=True returns (records, total appended
+        since the option was set)."""
+        out = np.zeros(max(int(cap), 0), dtype=_lib.FOLD_RECORD_DTYPE)
+        n, total = ctypes.c_uint32(), ctypes.c_uint64()
+        self._check(self.lib.hrt_get_fold_records(self.handle, _lib.ptr(out), len(out), ctypes.byref(n),
+                                                  ctypes.byref(total)), "hrt_get_fold_records")
+        recs = out[:n.value].copy()
+        return (recs, total.value) if with_total else recs
+
     def synchronize(self):
         self._check(self.lib.hrt_synchronize(self.handle), "hrt_synchronize")
 

@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
+/* 6, additive (no bump: nothing existing changed): fold records -- hrt_fold_record, hrt_settle_rule,
+ * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
+ * 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
  * hrt_present_info, hrt_present, hrt_accumulate_present, hrt_present_done, hrt_present_wait.
  * 6 (r06): hrt_release_caches; HRT_DEBUG_OPT_STACK_LIMIT.
  * 5 (r05): HRT_DIAG_WQ_STEPS_* / WQ_MEMBERS (HRT_NUM_DIAG 29), HRT_DEBUG_OPT_TIMELINE + hrt_debug_timeline.
@@ -192,6 +194,29 @@ typedef struct hrt_present_info {
   uint32_t flags;         /* must be 0 */
 } hrt_present_info;
 
+/* ---- fold records (HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until) ----
+ * The displayed word D(p) of an accumulator pixel: in HRT_MODE_RGBA8 the accumulator's 32-bit word; in
+ * HRT_MODE_RGBA32F the RGBA8 word hrt_read_image(HRT_FMT_RGBA8) and the present pass make of it.  The
+ * record of one fold (one frame folded into the accumulator) is taken over the context's REAL pixels: its
+ * local rows whose global row is below height (the padding rows of a row-tile part are never counted). */
+#define HRT_FOLD_RECORD_RING 1024u   /* records kept per context */
+#define HRT_RGBA8_FREEZE_FRAME 510u  /* HRT_MODE_RGBA8: a fold with frame >= this changes no pixel, whatever the new frame holds */
+
+typedef struct hrt_fold_record {
+  uint32_t frame;          /* the frame number the fold was given */
+  uint32_t changed_pixels; /* pixels with D before != D after */
+  uint32_t max_delta;      /* the largest |byte after - byte before| over the four bytes of every pixel */
+  uint32_t reserved;       /* 0 */
+  uint64_t abs_delta_sum;  /* the sum of |byte after - byte before| over the four bytes of every pixel */
+} hrt_fold_record;
+
+typedef struct hrt_settle_rule {
+  uint32_t max_changed_pixels; /* a frame is quiet when its record has changed_pixels <= this ... */
+  uint32_t max_delta;          /* ... and max_delta <= this (0xFFFFFFFF disables either bound) */
+  uint32_t quiet_frames;       /* stop after this many consecutive quiet frames of THIS call; >= 1 */
+  uint32_t flags;              /* must be 0 */
+} hrt_settle_rule;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -218,6 +243,12 @@ HRT_STATIC_ASSERT(sizeof(hrt_stats) == 64 && offsetof(hrt_stats, last_trace_ms) 
 HRT_STATIC_ASSERT(sizeof(hrt_present_info) == 24 && offsetof(hrt_present_info, pitch) == 16 &&
                       offsetof(hrt_present_info, flags) == 20,
                   "hrt_present_info");
+HRT_STATIC_ASSERT(sizeof(hrt_fold_record) == 24 && offsetof(hrt_fold_record, max_delta) == 8 &&
+                      offsetof(hrt_fold_record, abs_delta_sum) == 16,
+                  "hrt_fold_record");
+HRT_STATIC_ASSERT(sizeof(hrt_settle_rule) == 16 && offsetof(hrt_settle_rule, quiet_frames) == 8 &&
+                      offsetof(hrt_settle_rule, flags) == 12,
+                  "hrt_settle_rule");
 
 typedef struct hrt_context hrt_context;
 
@@ -323,6 +354,14 @@ typedef enum hrt_option {
    * deferred against 2.53 immediate -- without the combiners pacing them, the three lanes' persistent
    * traces all run at once and contend for the CUs -- so it is off by default. */
   HRT_OPT_DEFER_COMBINE = 18,
+  /* 1 = every fold on the context (hrt_accumulate, hrt_accumulate_present -- which then runs as its two
+   * passes, same bytes --, each frame of hrt_compute_n's multi-frame fold, each frame of a deferred-combine
+   * flush) appends one hrt_fold_record to the context's ring, in fold order, computed on the device by the
+   * combiner itself; 0 (default) = off: every path issues the kernels it issues without this option.
+   * Setting it (to 0 or 1) empties the ring and zeroes the total.  Accumulator, trace image, targets and
+   * hrt_stats are byte for byte the same either way.  On an hrt_comm_init_all group each member records
+   * its own rows when its own option is set; there is no collective. */
+  HRT_OPT_FOLD_RECORDS = 19,
   /* libhip_raytrace_debug.so only (tests): the value-th device allocation of the next hrt_set_scene
    * fails with HRT_ERR_OUT_OF_MEMORY (0 = off) */
   HRT_DEBUG_OPT_FAIL_ALLOC = 1001,
@@ -433,6 +472,31 @@ hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame);
  * per-pixel sample chains of one frame run beside the other frames' work instead of ending each
  * frame alone; the combiner then folds the frames in order.  pc->init must be 0. */
 hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* pc, uint32_t n);
+
+/* The records of the newest min(cap, available) folds (HRT_OPT_FOLD_RECORDS = 1), oldest first; the ring
+ * keeps the last HRT_FOLD_RECORD_RING.  Folds deferred combines and synchronizes the context, as
+ * hrt_get_stats does.  *count = the records copied; *total (may be NULL) = the records appended since the
+ * option was last set.  out may be NULL when cap is 0. */
+hrt_status hrt_get_fold_records(hrt_context* ctx, hrt_fold_record* out, uint32_t cap, uint32_t* count,
+                                uint64_t* total);
+
+/* hrt_compute_n, stopped after the first run of quiet frames.  Let r_1, r_2, ... be the fold records of the
+ * frames pc->rng_offset, pc->rng_offset + 1, ... as hrt_compute_n would fold them, and m the smallest index
+ * >= rule->quiet_frames such that r_(m - quiet_frames + 1) ... r_m are all quiet (hrt_settle_rule).  If
+ * m <= max_frames: *frames_done = m, *settled = 1; else *frames_done = max_frames, *settled = 0 (settled may
+ * be NULL).  On return the accumulator, the trace image and hrt_stats.accumulates are byte for byte those of
+ * hrt_compute_n(ctx, pc, *frames_done); with HRT_OPT_FOLD_RECORDS = 1 the ring gains exactly *frames_done
+ * records (the call works with the option off too).  max_frames == 0: OK, 0 frames, not settled.
+ * BLOCKING: the counts are needed on the host, so the call waits for each launch's count pass (a launch
+ * holds min(HRT_OPT_FRAMES_PER_LAUNCH, frames left) frames on the persistent kernels, else one frame).
+ * hrt_stats.traces, segments and tri_tests count every frame TRACED: the frames of the last launch past
+ * the stop are traced and discarded, so they exceed hrt_compute_n(*frames_done)'s by up to one launch;
+ * bound the waste with HRT_OPT_FRAMES_PER_LAUNCH.
+ * HRT_ERR_INVALID_ARGUMENT before anything is enqueued (the message names the reason): a NULL rule or
+ * frames_done, rule->flags != 0, rule->quiet_frames == 0, pc->init != 0, a context of a row-tile partition
+ * (part_count > 1) and a context joined to any communicator (the parts would stop at different frames). */
+hrt_status hrt_compute_until(hrt_context* ctx, const hrt_push_constants* pc, uint32_t max_frames,
+                             const hrt_settle_rule* rule, uint32_t* frames_done, uint32_t* settled);
 
 /* Copy an image (row-major, x 4 channels) into dst, host or device memory.  Blocking.
  *  - Without a communicator, or with image_id | HRT_IMG_LOCAL: this context's local rows

@@ -16,6 +16,8 @@
  *   RenderPassOverFrame, PresentTarget     src/texture_draw_pipeline.rs:96-157 (render into caller memory)
  *   RayTracingApp, compute_then_render,    src/raytracing_app.rs:32-227 (without the window: a render
  *   compute_n_then_render                  callback receives the accumulated image)
+ *   compute_until_then_render              (no reference counterpart) compute_n_then_render stopped when the
+ *                                          image settles: hrt_compute_until, Context::fold_records
  *   load_obj                               graphics::load_obj (one mesh per `o` record)
  *
  * Header-only; link with -lhip_raytrace.  Nothing here runs on the CPU in place of the device: a
@@ -237,6 +239,23 @@ class Context {
     return done != 0;
   }
   void present_wait(uint64_t ticket) { check(hrt_present_wait(get(), ticket), "hrt_present_wait", get()); }
+  // the newest min(cap, available) fold records (HRT_OPT_FOLD_RECORDS = 1), oldest first; *total (may be
+  // null) = the records appended since the option was set
+  std::vector<hrt_fold_record> fold_records(uint32_t cap = HRT_FOLD_RECORD_RING, uint64_t* total = nullptr) {
+    std::vector<hrt_fold_record> out(cap);
+    uint32_t n = 0;
+    check(hrt_get_fold_records(get(), out.data(), cap, &n, total), "hrt_get_fold_records", get());
+    out.resize(n);
+    return out;
+  }
+  // hrt_compute_until: hrt_compute_n stopped after the first run of rule.quiet_frames quiet frames
+  // (blocking); {frames folded, settled}
+  std::pair<uint32_t, bool> compute_until(const hrt_push_constants& pc, uint32_t max_frames,
+                                          const hrt_settle_rule& rule) {
+    uint32_t done = 0, settled = 0;
+    check(hrt_compute_until(get(), &pc, max_frames, &rule, &done, &settled), "hrt_compute_until", get());
+    return {done, settled != 0};
+  }
 
  private:
   struct Del {
@@ -437,6 +456,8 @@ class RayTracingApp {
  private:
   friend void compute_then_render(RayTracingApp& app, float frame_time);
   friend void compute_n_then_render(RayTracingApp& app, uint32_t num_renders);
+  friend std::pair<uint32_t, bool> compute_until_then_render(RayTracingApp& app, uint32_t max_renders,
+                                                             const hrt_settle_rule& rule);
   void require_open() const {
     if (!ctx_) throw HrtError(HRT_ERR_INVALID_ARGUMENT, "RayTracingApp: open() has not been called");
   }
@@ -470,6 +491,19 @@ inline void compute_n_then_render(RayTracingApp& app, uint32_t num_renders) {
     app.frame_ += num_renders;
   }
   if (app.render_) app.render_(app.diffuse_->image());
+}
+
+// compute_n_then_render that stops when the image settles: one hrt_compute_until of at most max_renders
+// frames under the rule, then one present; the frame counter advances by the frames folded.
+// Returns {frames folded, settled}.
+inline std::pair<uint32_t, bool> compute_until_then_render(RayTracingApp& app, uint32_t max_renders,
+                                                           const hrt_settle_rule& rule) {
+  app.require_open();
+  const hrt_push_constants pc = app.raytrace_->push_constants(app.camera, app.frame_, false);
+  const std::pair<uint32_t, bool> r = app.ctx_->compute_until(pc, max_renders, rule);
+  app.frame_ += r.first;
+  if (app.render_) app.render_(app.diffuse_->image());
+  return r;
 }
 
 }  // namespace epq
