@@ -23,6 +23,7 @@
 #include "hrt_bvh.h"
 #include "hrt_context.h"
 #include "hrt_host.h"
+#include "hrt_image.h"
 #include "hrt_kernels.h"
 
 // (the record, push-block, hrt_create_info / hrt_layout / hrt_stats sizes and offsets are
@@ -160,13 +161,13 @@ void dev_free(hrt_context* ctx, void* p) {
 // The trace image: the most recent trace's ring slot, or its lane's own image.
 void* trace_image(hrt_context* ctx) {
   if (ctx->cur_slot >= 0) return static_cast<char*>(ctx->ring) + (size_t)ctx->cur_slot * ctx->npix() * ctx->px_bytes();
-  return ctx->lane[ctx->cur_lane].image();
+  return ctx->lane[ctx->cur_lane].trace;
 }
 
 const void* local_image(hrt_context* ctx, uint32_t image_id) {
   if (image_id == HRT_IMG_ACCUM) {
     if (flush_combines(ctx) != HRT_OK) return nullptr;
-    return ctx->accum8 ? (const void*)ctx->accum8 : (const void*)ctx->accum32;
+    return ctx->accum;
   }
   if (wait_lane(ctx, ctx->cur_lane) != HRT_OK) return nullptr;
   return trace_image(ctx);
@@ -175,7 +176,7 @@ const void* local_image(hrt_context* ctx, uint32_t image_id) {
 // HRT_OPT_FOLD_RECORDS = 1: the fold of nf frames (image f of the stack = frame frame0 + f) into the
 // accumulator by the recording kernel, appending nf records to the ring -- the slots zeroed on the stream
 // first, their frame numbers kept on the host.  A fold may wrap the ring's end.
-hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0) {
+static hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0) {
   const size_t np = ctx->npix(), fb = np * ctx->px_bytes();
   const uint32_t ring = HRT_FOLD_RECORD_RING;
   for (uint32_t done = 0; done < nf;) {  // (a launch's frames have a slot each)
@@ -186,13 +187,23 @@ hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint3
       HRT_HIP(ctx, hipMemsetAsync(ctx->fold_ring, 0, (size_t)(n - head) * sizeof(hrt_fold_record), ctx->stream));
     for (uint32_t f = 0; f < n; ++f) ctx->fold_frame[(slot0 + f) % ring] = frame0 + done + f;
     const char* base = static_cast<const char*>(stack) + (size_t)done * fb;
-    HRT_HIP(ctx, launch_fold_records(ctx->accum8, ctx->accum8 ? reinterpret_cast<const uint32_t*>(base) : nullptr,
-                                     ctx->accum32, ctx->accum32 ? reinterpret_cast<const float4*>(base) : nullptr, np,
-                                     ctx->real_pix(), n, frame0 + done, true, ctx->fold_ring, slot0, ctx->num_cus,
-                                     ctx->stream));
+    HRT_HIP(ctx, launch_fold_records(ctx->accum, base, ctx->f32(), np, ctx->real_pix(), n, frame0 + done, true,
+                                     ctx->fold_ring, slot0, ctx->num_cus, ctx->stream));
     ctx->fold_total += n;
     done += n;
   }
+  return HRT_OK;
+}
+
+// Every fold into the accumulator, on ctx->stream: the nf frames of a stack (image f = frame frame0 + f) by the
+// recording kernel when HRT_OPT_FOLD_RECORDS is on, else one frame by the single-frame combiner (the
+// realtime loop's) and several by the stack combiner.
+static hrt_status fold_frames(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0) {
+  if (ctx->fold_on) return fold_recorded(ctx, stack, nf, frame0);
+  if (nf == 1)
+    HRT_HIP(ctx, launch_accumulate(ctx->accum, stack, ctx->f32(), ctx->npix(), frame0, ctx->stream));
+  else
+    HRT_HIP(ctx, launch_accumulate_frames(ctx->accum, stack, ctx->f32(), ctx->npix(), nf, frame0, ctx->stream));
   return HRT_OK;
 }
 
@@ -201,20 +212,14 @@ hrt_status flush_combines(hrt_context* ctx) {
   // the folds read slots that traces on every lane wrote: after each lane's latest trace
   hrt_status st = join_lanes(ctx);
   if (st != HRT_OK) return st;
-  const size_t np = ctx->npix(), fb = np * ctx->px_bytes();
+  const size_t fb = ctx->npix() * ctx->px_bytes();
   for (size_t i = 0; i < ctx->pend.size();) {
     size_t j = i;  // a run of consecutive slots (no wrap) and frames: one pass over the stack
     while (j + 1 < ctx->pend.size() && ctx->pend[j + 1].slot == ctx->pend[j].slot + 1 &&
            ctx->pend[j + 1].frame == ctx->pend[j].frame + 1)
       ++j;
-    char* base = static_cast<char*>(ctx->ring) + (size_t)ctx->pend[i].slot * fb;
-    if (ctx->fold_on) {
-      if ((st = fold_recorded(ctx, base, (uint32_t)(j - i + 1), ctx->pend[i].frame)) != HRT_OK) return st;
-    } else {
-      HRT_HIP(ctx, launch_accumulate_frames(ctx->accum8, ctx->accum8 ? reinterpret_cast<const uint32_t*>(base) : nullptr,
-                                            ctx->accum32, ctx->accum32 ? reinterpret_cast<const float4*>(base) : nullptr,
-                                            np, (uint32_t)(j - i + 1), ctx->pend[i].frame, ctx->stream));
-    }
+    const char* base = static_cast<const char*>(ctx->ring) + (size_t)ctx->pend[i].slot * fb;
+    if ((st = fold_frames(ctx, base, (uint32_t)(j - i + 1), ctx->pend[i].frame)) != HRT_OK) return st;
     i = j + 1;
   }
   ctx->pend.clear();
@@ -387,11 +392,8 @@ extern "C" hrt_status hrt_create(const hrt_create_info* info, hrt_context** out_
     if ((e = hipEventCreateWithFlags(&l.done, hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&l.free, hipEventDisableTiming)) != hipSuccess)
       return bail(hip_fail(ctx, e, "hipEventCreate(lane)"));
-    if (ctx->mode == HRT_MODE_RGBA8)
-      e = hrt::dev_alloc(ctx, (void**)&l.trace8, np * 4);
-    else
-      e = hrt::dev_alloc(ctx, (void**)&l.trace32, np * 16);
-    if (e != hipSuccess) return bail(hip_fail(ctx, e, "hipMalloc(trace)"));
+    if ((e = hrt::dev_alloc(ctx, &l.trace, np * ctx->px_bytes())) != hipSuccess)
+      return bail(hip_fail(ctx, e, "hipMalloc(trace)"));
     if ((e = hrt::dev_alloc(ctx, (void**)&l.sched, hrt::kSchedWords * 4)) != hipSuccess) return bail(hip_fail(ctx, e, "hipMalloc(sched)"));
     if ((e = hrt::dev_alloc(ctx, (void**)&l.tile_cost, tiles * 4)) != hipSuccess)
       return bail(hip_fail(ctx, e, "hipMalloc(tile costs)"));
@@ -400,11 +402,8 @@ extern "C" hrt_status hrt_create(const hrt_create_info* info, hrt_context** out_
     if ((e = hrt::dev_alloc(ctx, (void**)&l.tl_cache, tiles * hrt::kTlRecWords * 4)) != hipSuccess)
       return bail(hip_fail(ctx, e, "hipMalloc(tile lists)"));
   }
-  if (ctx->mode == HRT_MODE_RGBA8)
-    e = hrt::dev_alloc(ctx, (void**)&ctx->accum8, np * 4);
-  else
-    e = hrt::dev_alloc(ctx, (void**)&ctx->accum32, np * 16);
-  if (e != hipSuccess) return bail(hip_fail(ctx, e, "hipMalloc(accum)"));
+  if ((e = hrt::dev_alloc(ctx, &ctx->accum, np * ctx->px_bytes())) != hipSuccess)
+    return bail(hip_fail(ctx, e, "hipMalloc(accum)"));
   if ((e = hrt::dev_alloc(ctx, (void**)&ctx->scratch, np * 16)) != hipSuccess) return bail(hip_fail(ctx, e, "hipMalloc(scratch)"));
   if ((e = hipEventCreateWithFlags(&ctx->fold_done, hipEventDisableTiming)) != hipSuccess)
     return bail(hip_fail(ctx, e, "hipEventCreate(fold)"));
@@ -420,8 +419,8 @@ extern "C" hrt_status hrt_create(const hrt_create_info* info, hrt_context** out_
     return bail(hip_fail(ctx, e, "hipMemset(counters)"));
   // Fresh images read as the cleared state (0,0,0,1) until the first dispatch writes them.
   for (auto& l : ctx->lane)
-    if ((e = hrt::launch_clear(l.trace8, l.trace32, np, ctx->stream)) != hipSuccess) return bail(hip_fail(ctx, e, "clear"));
-  if ((e = hrt::launch_clear(ctx->accum8, ctx->accum32, np, ctx->stream)) != hipSuccess)
+    if ((e = hrt::launch_clear(l.trace, ctx->f32(), np, ctx->stream)) != hipSuccess) return bail(hip_fail(ctx, e, "clear"));
+  if ((e = hrt::launch_clear(ctx->accum, ctx->f32(), np, ctx->stream)) != hipSuccess)
     return bail(hip_fail(ctx, e, "clear"));
   if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return bail(hip_fail(ctx, e, "hipStreamSynchronize"));
   *out_ctx = ctx;
@@ -438,8 +437,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   (void)hipSetDevice(ctx->device);
   hrt::free_scene(ctx, ctx->scene, false);
   for (auto& l : ctx->lane) {
-    free_dev(ctx, l.trace8);
-    free_dev(ctx, l.trace32);
+    free_dev(ctx, l.trace);
     free_dev(ctx, l.sched);
     free_dev(ctx, l.tile_cost);
     free_dev(ctx, l.item_buf);
@@ -448,8 +446,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
     if (l.free) (void)hipEventDestroy(l.free);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
-  free_dev(ctx, ctx->accum8);
-  free_dev(ctx, ctx->accum32);
+  free_dev(ctx, ctx->accum);
   free_dev(ctx, ctx->scratch);
   free_dev(ctx, ctx->counters);
   free_dev(ctx, ctx->tile_cycles);
@@ -710,6 +707,12 @@ hrt_status check_dispatch(hrt_context* ctx, const hrt_push_constants* pc, const 
   return HRT_OK;
 }
 
+// The image a trace writes: the one place that fills TraceParams' (RGBA8 pointer, RGBA32F pointer) pair.
+void set_image(hrt::TraceParams& p, const hrt_context* ctx, void* img) {
+  p.img8 = ctx->f32() ? nullptr : static_cast<uint32_t*>(img);
+  p.img32 = ctx->f32() ? static_cast<float4*>(img) : nullptr;
+}
+
 // The kernel argument block of a dispatch of pc into trace lane l's image.
 hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int l) {
   const hrt::SceneBufs& s = ctx->scene;
@@ -720,8 +723,7 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   p.tris = s.tris;
   p.tri_nhat = s.tri_nhat;
   p.meshes = s.meshes;
-  p.img8 = lane.trace8;
-  p.img32 = lane.trace32;
+  set_image(p, ctx, lane.trace);
   p.counters = ctx->counters_on ? ctx->counters : nullptr;
   p.diag = ctx->diag_on ? ctx->counters + 3 : nullptr;
   p.tile_cycles = ctx->diag_on ? ctx->tile_cycles : nullptr;
@@ -841,8 +843,7 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
     hrt::TraceParams q = p;
     q.pc.num_samples = 1;
     q.n_frames = 1;
-    q.img8 = lane.trace8;
-    q.img32 = lane.trace32;
+    set_image(q, ctx, lane.trace);
     q.counters = nullptr;
     q.diag = nullptr;
     q.tile_cycles = nullptr;
@@ -942,14 +943,12 @@ extern "C" hrt_status hrt_trace(hrt_context* ctx, const hrt_push_constants* pc) 
   if ((st = begin_lane(ctx, &l)) != HRT_OK) return st;
   hrt::Lane& lane = ctx->lane[l];
   if (pc->init) {  // RayTracePipeline::init, src/raytrace_pipeline.rs:190-213
-    HRT_HIP(ctx, hrt::launch_clear(lane.trace8, lane.trace32, ctx->npix(), lane.stream));
+    HRT_HIP(ctx, hrt::launch_clear(lane.trace, ctx->f32(), ctx->npix(), lane.stream));
   } else {
     hrt::TraceParams p = make_params(ctx, pc, l);
     if (slot >= 0) {  // after the fold that last read the slot
       if (ctx->fold_set) HRT_HIP(ctx, hipStreamWaitEvent(lane.stream, ctx->fold_done, 0));
-      char* img = static_cast<char*>(ctx->ring) + (size_t)slot * ctx->npix() * ctx->px_bytes();
-      p.img8 = lane.trace8 ? reinterpret_cast<uint32_t*>(img) : nullptr;
-      p.img32 = lane.trace32 ? reinterpret_cast<float4*>(img) : nullptr;
+      set_image(p, ctx, static_cast<char*>(ctx->ring) + (size_t)slot * ctx->npix() * ctx->px_bytes());
     }
     // Throughput mode: when another lane's trace is still running, this one shares the chip with it
     // (a persistent grid over 1 / HRT_OPT_BUSY_SPLIT of the CUs), so two frames' long sample chains run
@@ -1003,6 +1002,68 @@ static hrt_status grow_frame_stack(hrt_context* ctx, uint32_t cap, uint32_t n, s
   return HRT_OK;
 }
 
+// ---- the batched loops (hrt_compute_n, hrt_compute_until): lane 0's buffers on the context stream ----
+namespace {
+
+// A call's parameter block and its frames per launch (1: one launch per frame).
+struct Batch {
+  hrt::TraceParams p;
+  uint32_t lcap;
+};
+
+// The whole loop runs on the context stream with lane 0's buffers, after every lane's last trace
+// and every deferred combine (frames fold in call order).  Frames per launch: up to
+// HRT_OPT_FRAMES_PER_LAUNCH and `bound`, and at most 1 GiB of frame images.
+// The stack is sized for a whole launch of cap frames at once (a stack grown from a short first call --
+// bench.py's 5 warm-up frames -- was re-allocated by the next longer call, a device synchronisation and
+// ~0.3 ms of hipFree / hipMalloc inside that call).  Where that does not fit (several contexts on one
+// device, little free memory) the call's own min(cap, n) frames are allocated instead; where even those
+// do not fit, the call runs with the stack it has (more, shorter launches) or one launch per frame.
+// Never an error: the frames are the same bytes whatever the launches hold.
+hrt_status begin_batch(hrt_context* ctx, const hrt_push_constants* pc, uint32_t n, uint32_t bound, Batch* b) {
+  hrt_status st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
+  b->p = make_params(ctx, pc, 0);
+  const size_t np = ctx->npix(), px_bytes = ctx->px_bytes();
+  const uint32_t cap = (uint32_t)std::max<size_t>(
+      1, std::min<size_t>(std::min(ctx->frames_per_launch, bound), ((size_t)1 << 30) / std::max<size_t>(np * px_bytes, 1)));
+  const bool batch = persistent_kernel(hrt::resolve_variant(b->p, ctx->variant)) && cap > 1 && n > 1;
+  if (batch && (st = grow_frame_stack(ctx, cap, n, np, px_bytes)) != HRT_OK) return st;
+  b->lcap = batch ? std::max(1u, std::min(cap, ctx->frame_stack_frames)) : 1;  // (no stack at all: per frame)
+  return HRT_OK;
+}
+
+// One trace launch of the nf frames from frame0 (u32, wrapping like the per-frame loop's pushes);
+// *stack: where it left them -- the frame stack, or lane 0's image for a single frame.
+hrt_status launch_batch(hrt_context* ctx, const Batch& b, uint32_t frame0, uint32_t nf, const char** stack) {
+  hrt::Lane& lane = ctx->lane[0];
+  hrt::TraceParams q = b.p;
+  q.pc.rng_offset = frame0;
+  q.n_frames = nf;
+  q.plan_valid = lane.plan_valid ? 1u : 0u;
+  if (nf > 1) set_image(q, ctx, ctx->frame_stack);
+  *stack = static_cast<const char*>(nf > 1 ? ctx->frame_stack : lane.trace);
+  return launch_frames(ctx, q, ctx->stream, 0);
+}
+
+// The trace image holds the last frame folded (frame s - 1 of a launch of nf), as after the per-frame loop.
+hrt_status keep_last_frame(hrt_context* ctx, const char* stack, uint32_t nf, uint32_t s) {
+  const size_t fb = ctx->npix() * ctx->px_bytes();
+  if (nf > 1)
+    HRT_HIP(ctx, hipMemcpyAsync(ctx->lane[0].trace, stack + (size_t)(s - 1) * fb, fb, hipMemcpyDeviceToDevice, ctx->stream));
+  return HRT_OK;
+}
+
+hrt_status end_batch(hrt_context* ctx) {
+  ctx->cur_lane = 0;
+  ctx->cur_slot = -1;  // the trace image is lane 0's
+  ctx->lane_used = true;
+  return hrt::release_lane(ctx, 0);  // lane 0's next trace follows this loop
+}
+
+}  // namespace
+
 extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* pc, uint32_t n) {
   if (!ctx || !pc) return HRT_ERR_INVALID_ARGUMENT;
   if (pc->init) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_compute_n: init dispatches go through hrt_trace");
@@ -1010,59 +1071,21 @@ extern "C" hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* 
   if (st != HRT_OK) return st;
   if ((st = check_dispatch(ctx, pc, "hrt_compute_n")) != HRT_OK) return st;
   if (n == 0) return HRT_OK;
-  // The whole loop runs on the context stream with lane 0's buffers, after every lane's last trace
-  // and every deferred combine (frames fold in call order).
-  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
-  if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
-  hrt::TraceParams p = make_params(ctx, pc, 0);
-  hrt::Lane& lane = ctx->lane[0];
-  const size_t np = ctx->npix(), px_bytes = ctx->px_bytes();
-  // Frames per launch: up to HRT_OPT_FRAMES_PER_LAUNCH, and at most 1 GiB of frame images.
-  const uint32_t cap = (uint32_t)std::max<size_t>(
-      1, std::min<size_t>(ctx->frames_per_launch, ((size_t)1 << 30) / std::max<size_t>(np * px_bytes, 1)));
-  bool batch = persistent_kernel(hrt::resolve_variant(p, ctx->variant)) && cap > 1 && n > 1;
-  // The stack is sized for a whole launch of cap frames at once (a stack grown from a short first call --
-  // bench.py's 5 warm-up frames -- was re-allocated by the next longer call, a device synchronisation and
-  // ~0.3 ms of hipFree / hipMalloc inside that call).  Where that does not fit (several contexts on one
-  // device, little free memory) the call's own min(cap, n) frames are allocated instead; where even those
-  // do not fit, the call runs with the stack it has (more, shorter launches) or one launch per frame.
-  // Never an error: the frames are the same bytes whatever the launches hold.
-  if (batch && (st = grow_frame_stack(ctx, cap, n, np, px_bytes)) != HRT_OK) return st;
-  const uint32_t lcap = batch ? std::min(cap, ctx->frame_stack_frames) : 1;  // frames per launch this call
-  batch = batch && lcap > 1;
+  Batch b;
+  if ((st = begin_batch(ctx, pc, n, UINT32_MAX, &b)) != HRT_OK) return st;
   for (uint32_t done = 0; done < n;) {
     // near-equal launches: ceil(remaining / lcap) of them
-    const uint32_t left = n - done, launches = batch ? (left + lcap - 1) / lcap : left;
-    const uint32_t nf = (left + launches - 1) / launches;
-    hrt::TraceParams q = p;
-    q.pc.rng_offset = pc->rng_offset + done;  // u32, wrapping like the per-frame loop's pushes
-    q.n_frames = nf;
-    q.plan_valid = lane.plan_valid ? 1u : 0u;
-    if (nf > 1) {
-      q.img8 = lane.trace8 ? reinterpret_cast<uint32_t*>(ctx->frame_stack) : nullptr;
-      q.img32 = lane.trace32 ? reinterpret_cast<float4*>(ctx->frame_stack) : nullptr;
-    }
-    if ((st = launch_frames(ctx, q, ctx->stream, 0)) != HRT_OK) return st;
+    const uint32_t left = n - done, launches = (left + b.lcap - 1) / b.lcap;
+    const uint32_t nf = (left + launches - 1) / launches, frame0 = pc->rng_offset + done;
+    const char* stack = nullptr;
+    if ((st = launch_batch(ctx, b, frame0, nf, &stack)) != HRT_OK) return st;
     // DiffusePipeline::next_frame(frame) for each frame, in frame order: one pass over the stack
-    if (ctx->fold_on) {
-      if ((st = hrt::fold_recorded(ctx, nf > 1 ? ctx->frame_stack : lane.image(), nf, q.pc.rng_offset)) != HRT_OK)
-        return st;
-    } else if (nf > 1)
-      HRT_HIP(ctx, hrt::launch_accumulate_frames(ctx->accum8, q.img8, ctx->accum32, q.img32, np, nf, q.pc.rng_offset,
-                                                 ctx->stream));
-    else
-      HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, lane.trace8, ctx->accum32, lane.trace32, np, q.pc.rng_offset,
-                                          ctx->stream));
+    if ((st = hrt::fold_frames(ctx, stack, nf, frame0)) != HRT_OK) return st;
     ctx->accumulates += nf;
-    if (nf > 1)  // the trace image holds the last frame, as after the per-frame loop
-      HRT_HIP(ctx, hipMemcpyAsync(lane.image(), static_cast<const char*>(ctx->frame_stack) + (size_t)(nf - 1) * np * px_bytes,
-                                  np * px_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((st = keep_last_frame(ctx, stack, nf, nf)) != HRT_OK) return st;
     done += nf;
   }
-  ctx->cur_lane = 0;
-  ctx->cur_slot = -1;  // the trace image is lane 0's
-  ctx->lane_used = true;
-  return hrt::release_lane(ctx, 0);  // lane 0's next trace follows this loop
+  return end_batch(ctx);
 }
 
 // hrt_compute_n's loop with a count pass between a launch's trace and its fold: the count pass runs the fold
@@ -1092,39 +1115,20 @@ extern "C" hrt_status hrt_compute_until(hrt_context* ctx, const hrt_push_constan
   if (max_frames == 0) return HRT_OK;
   if (!ctx->fold_scratch)
     HRT_HIP(ctx, hrt::dev_alloc(ctx, (void**)&ctx->fold_scratch, HRT_FOLD_RECORD_RING * sizeof(hrt_fold_record)));
-  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
-  if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
-  hrt::TraceParams p = make_params(ctx, pc, 0);
-  hrt::Lane& lane = ctx->lane[0];
-  const size_t np = ctx->npix(), px_bytes = ctx->px_bytes(), fb = np * px_bytes;
-  // frames per launch as in hrt_compute_n (and one slot of the scratch ring each)
-  const uint32_t cap = (uint32_t)std::max<size_t>(
-      1, std::min<size_t>(std::min<uint32_t>(ctx->frames_per_launch, HRT_FOLD_RECORD_RING),
-                          ((size_t)1 << 30) / std::max<size_t>(fb, 1)));
-  bool batch = persistent_kernel(hrt::resolve_variant(p, ctx->variant)) && cap > 1 && max_frames > 1;
-  if (batch && (st = grow_frame_stack(ctx, cap, max_frames, np, px_bytes)) != HRT_OK) return st;
-  const uint32_t lcap = batch ? std::min(cap, ctx->frame_stack_frames) : 1;
-  std::vector<hrt_fold_record> recs(lcap);
+  Batch b;  // (a launch's frames have a slot of the scratch ring each)
+  if ((st = begin_batch(ctx, pc, max_frames, HRT_FOLD_RECORD_RING, &b)) != HRT_OK) return st;
+  std::vector<hrt_fold_record> recs(b.lcap);
   uint32_t done = 0, quiet_run = 0;
   bool stop = false;
   while (done < max_frames && !stop) {
-    const uint32_t nf = std::min(lcap, max_frames - done), frame0 = pc->rng_offset + done;
-    hrt::TraceParams q = p;
-    q.pc.rng_offset = frame0;
-    q.n_frames = nf;
-    q.plan_valid = lane.plan_valid ? 1u : 0u;
-    if (nf > 1) {
-      q.img8 = lane.trace8 ? reinterpret_cast<uint32_t*>(ctx->frame_stack) : nullptr;
-      q.img32 = lane.trace32 ? reinterpret_cast<float4*>(ctx->frame_stack) : nullptr;
-    }
-    if ((st = launch_frames(ctx, q, ctx->stream, 0)) != HRT_OK) return st;
-    const char* stack = static_cast<const char*>(nf > 1 ? ctx->frame_stack : lane.image());
-    const uint32_t* stack8 = ctx->accum8 ? reinterpret_cast<const uint32_t*>(stack) : nullptr;
-    const float4* stack32 = ctx->accum32 ? reinterpret_cast<const float4*>(stack) : nullptr;
+    // greedy launches: whole launches until the stop
+    const uint32_t nf = std::min(b.lcap, max_frames - done), frame0 = pc->rng_offset + done;
+    const char* stack = nullptr;
+    if ((st = launch_batch(ctx, b, frame0, nf, &stack)) != HRT_OK) return st;
     // the count pass, and its records on the host
     HRT_HIP(ctx, hipMemsetAsync(ctx->fold_scratch, 0, (size_t)nf * sizeof(hrt_fold_record), ctx->stream));
-    HRT_HIP(ctx, hrt::launch_fold_records(ctx->accum8, stack8, ctx->accum32, stack32, np, ctx->real_pix(), nf, frame0,
-                                          false, ctx->fold_scratch, 0, ctx->num_cus, ctx->stream));
+    HRT_HIP(ctx, hrt::launch_fold_records(ctx->accum, stack, ctx->f32(), ctx->npix(), ctx->real_pix(), nf, frame0, false,
+                                          ctx->fold_scratch, 0, ctx->num_cus, ctx->stream));
     HRT_HIP(ctx, hipMemcpyAsync(recs.data(), ctx->fold_scratch, (size_t)nf * sizeof(hrt_fold_record),
                                 hipMemcpyDeviceToHost, ctx->stream));
     HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1139,24 +1143,14 @@ extern "C" hrt_status hrt_compute_until(hrt_context* ctx, const hrt_push_constan
       }
     }
     // the ordinary fold of the first s frames
-    if (ctx->fold_on) {
-      if ((st = hrt::fold_recorded(ctx, stack, s, frame0)) != HRT_OK) return st;
-    } else if (s > 1) {
-      HRT_HIP(ctx, hrt::launch_accumulate_frames(ctx->accum8, stack8, ctx->accum32, stack32, np, s, frame0, ctx->stream));
-    } else {
-      HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, stack8, ctx->accum32, stack32, np, frame0, ctx->stream));
-    }
+    if ((st = hrt::fold_frames(ctx, stack, s, frame0)) != HRT_OK) return st;
     ctx->accumulates += s;
-    if (nf > 1)  // the trace image holds the last frame folded
-      HRT_HIP(ctx, hipMemcpyAsync(lane.image(), stack + (size_t)(s - 1) * fb, fb, hipMemcpyDeviceToDevice, ctx->stream));
+    if ((st = keep_last_frame(ctx, stack, nf, s)) != HRT_OK) return st;
     done += s;
   }
   *frames_done = done;
   if (settled) *settled = stop ? 1u : 0u;
-  ctx->cur_lane = 0;
-  ctx->cur_slot = -1;
-  ctx->lane_used = true;
-  return hrt::release_lane(ctx, 0);
+  return end_batch(ctx);
 }
 
 extern "C" hrt_status hrt_get_fold_records(hrt_context* ctx, hrt_fold_record* out, uint32_t cap, uint32_t* count,
@@ -1199,14 +1193,7 @@ extern "C" hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame) {
   }
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // frames fold in call order
   if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
-  void* img = hrt::trace_image(ctx);
-  if (ctx->fold_on) {
-    if ((st = hrt::fold_recorded(ctx, img, 1, frame)) != HRT_OK) return st;
-  } else {
-    HRT_HIP(ctx, hrt::launch_accumulate(ctx->accum8, ctx->accum8 ? static_cast<uint32_t*>(img) : nullptr, ctx->accum32,
-                                        ctx->accum32 ? static_cast<float4*>(img) : nullptr, ctx->npix(), frame,
-                                        ctx->stream));
-  }
+  if ((st = hrt::fold_frames(ctx, hrt::trace_image(ctx), 1, frame)) != HRT_OK) return st;
   ctx->accumulates++;
   return hrt::release_lane(ctx, l);
 }
@@ -1218,10 +1205,7 @@ hrt_status copy_out(hrt_context* ctx, const void* src, size_t npix, uint32_t fmt
   const size_t need = npix * (fmt == HRT_FMT_RGBA8 ? 4 : 16);
   const bool native = (ctx->mode == HRT_MODE_RGBA8) == (fmt == HRT_FMT_RGBA8);
   if (!native) {
-    if (ctx->mode == HRT_MODE_RGBA8)
-      HRT_HIP(ctx, hrt::launch_convert((const uint32_t*)src, (float4*)scratch, nullptr, nullptr, npix, ctx->stream));
-    else
-      HRT_HIP(ctx, hrt::launch_convert(nullptr, nullptr, (const float4*)src, (uint32_t*)scratch, npix, ctx->stream));
+    HRT_HIP(ctx, hrt::launch_convert(src, ctx->f32(), scratch, npix, ctx->stream));
     src = scratch;
   }
   HRT_HIP(ctx, hipMemcpyAsync(dst, src, need, hipMemcpyDefault, ctx->stream));
@@ -1261,7 +1245,7 @@ extern "C" hrt_status hrt_read_image(hrt_context* ctx, uint32_t image_id, uint32
 // continuing with the saved frame number renders exactly what an uninterrupted run would.
 extern "C" hrt_status hrt_load_accumulator(hrt_context* ctx, uint32_t fmt, const void* src, size_t bytes) {
   if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
-  const uint32_t native = ctx->accum8 ? HRT_FMT_RGBA8 : HRT_FMT_RGBA32F;
+  const uint32_t native = ctx->f32() ? HRT_FMT_RGBA32F : HRT_FMT_RGBA8;
   if (fmt != native)
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_load_accumulator: format must be the context's own (no conversion)");
   if (!src) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_load_accumulator: null source");
@@ -1271,9 +1255,8 @@ extern "C" hrt_status hrt_load_accumulator(hrt_context* ctx, uint32_t fmt, const
   if (st != HRT_OK) return st;
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // (overwritten below, but in call order)
   if ((st = sync_all(ctx)) != HRT_OK) return st;  // no accumulate in flight
-  void* dst = ctx->accum8 ? (void*)ctx->accum8 : (void*)ctx->accum32;
   // on the context stream (non-blocking w.r.t. the null stream): the next hrt_accumulate follows it
-  HRT_HIP(ctx, hipMemcpyAsync(dst, src, need, hipMemcpyDefault, ctx->stream));  // host or device source
+  HRT_HIP(ctx, hipMemcpyAsync(ctx->accum, src, need, hipMemcpyDefault, ctx->stream));  // host or device source
   HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return HRT_OK;
 }
@@ -1372,10 +1355,7 @@ hrt_status enqueue_present(hrt_context* ctx, const hrt_present_info* info, void*
   if (ctx->comm) return hrt::comm_present(ctx, info->image_id, present_target(info, dst));
   const void* src = hrt::local_image(ctx, info->image_id);
   if (!src) return fail(ctx, HRT_ERR_HIP, "hrt_present: lane wait failed");
-  const bool f32 = ctx->mode != HRT_MODE_RGBA8;
-  HRT_HIP(ctx, hrt::launch_present(f32 ? nullptr : static_cast<const uint32_t*>(src),
-                                   f32 ? static_cast<const float4*>(src) : nullptr, ctx->width, ctx->local_rows,
-                                   present_target(info, dst), ctx->stream));
+  HRT_HIP(ctx, hrt::launch_present(src, ctx->f32(), ctx->width, ctx->local_rows, present_target(info, dst), ctx->stream));
   if (info->image_id != HRT_IMG_TRACE) return HRT_OK;
   // the trace image's next writer follows the pass: its lane's next trace, and -- when the image is a
   // slot of the deferred combiner's ring -- the slot's next trace, which waits for fold_done
@@ -1430,10 +1410,8 @@ extern "C" hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, c
   const int l = ctx->cur_lane;
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
   if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
-  void* img = hrt::trace_image(ctx);
-  HRT_HIP(ctx, hrt::launch_accumulate_present(ctx->accum8, ctx->accum8 ? static_cast<uint32_t*>(img) : nullptr,
-                                              ctx->accum32, ctx->accum32 ? static_cast<float4*>(img) : nullptr,
-                                              ctx->width, ctx->local_rows, frame, present_target(info, dst), ctx->stream));
+  HRT_HIP(ctx, hrt::launch_accumulate_present(ctx->accum, hrt::trace_image(ctx), ctx->f32(), ctx->width, ctx->local_rows,
+                                              frame, present_target(info, dst), ctx->stream));
   ctx->accumulates++;
   if ((st = hrt::release_lane(ctx, l)) != HRT_OK) return st;
   return ticket_end(ctx, ev, ticket);

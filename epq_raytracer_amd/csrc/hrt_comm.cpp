@@ -42,7 +42,7 @@
 #include "hip_raytrace.h"
 #include "hrt_comm_protocol.h"
 #include "hrt_context.h"
-#include "hrt_kernels.h"
+#include "hrt_image.h"
 
 namespace {
 
@@ -384,9 +384,8 @@ hrt_status present_group(hrt_context* root, Comm* rc, uint32_t image_id, const P
     HRT_HIP(root, hipEventRecord(rc->ev, root->stream));
     for (size_t i = 1; i < n; ++i) HRT_HIP(root, hipStreamWaitEvent(g.members[i]->stream, rc->ev, 0));
   }
-  const bool f32 = root->mode != HRT_MODE_RGBA8;
-  const GatheredImage img{f32 ? nullptr : static_cast<const uint32_t*>(rc->gather_buf),
-                          f32 ? static_cast<const float4*>(rc->gather_buf) : nullptr,
+  const GatheredImage img{rc->gather_buf,
+                          root->f32(),
                           root->width,
                           root->height,
                           rc->world == 1 ? root->height : root->row_tile,

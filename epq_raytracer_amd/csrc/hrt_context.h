@@ -75,8 +75,7 @@ void free_scene(hrt_context* ctx, SceneBufs& s, bool keep_rays);
 // One trace lane (see the header comment).
 struct Lane {
   hipStream_t stream = nullptr;
-  uint32_t* trace8 = nullptr;  // local_rows x W rgba8 (RGBA8 mode)
-  float4* trace32 = nullptr;   // or float4 (RGBA32F mode)
+  void* trace = nullptr;  // the lane's trace image: local_rows x W pixels in the context's format
   uint32_t* sched = nullptr;      // persistent kernels' scheduler words (hrt_kernels.h)
   uint32_t* tile_cost = nullptr;  // per 8x8 tile
   uint32_t* item_buf = nullptr;   // planned work items (tiles x 64)
@@ -91,7 +90,6 @@ struct Lane {
   hipEvent_t done = nullptr;      // recorded on `stream` after each trace / clear of the lane
   hipEvent_t free = nullptr;      // recorded on the context stream after the lane's last reader
   bool done_set = false, free_set = false;
-  void* image() const { return trace8 ? (void*)trace8 : (void*)trace32; }
 };
 
 // Multi-GPU framebuffer gather (hrt_comm.cpp).
@@ -124,8 +122,7 @@ struct hrt_context {
   uint32_t busy_split = 2;    // HRT_OPT_BUSY_SPLIT: grid share of a trace launched while another runs
   uint32_t overlap = hrt::kLanes;  // HRT_OPT_OVERLAP: trace lanes in rotation (1: every trace on lane 0)
 
-  uint32_t* accum8 = nullptr;
-  float4* accum32 = nullptr;
+  void* accum = nullptr;    // the accumulated image: local_rows x W pixels in the context's format
   void* scratch = nullptr;  // format conversion for hrt_read_image
   unsigned long long* counters = nullptr;
   unsigned long long* tile_cycles = nullptr;  // diagnostics: shader clocks per 8x8 tile of the last trace
@@ -183,7 +180,7 @@ struct hrt_context {
   // Deferred combiner (HRT_OPT_DEFER_COMBINE).  The accumulator is observable only through
   // hrt_read_image / hrt_stream / hrt_synchronize, so hrt_accumulate after an hrt_trace only records
   // (ring slot, frame): the trace wrote a slot of a ring of frame images instead of its lane's image,
-  // and the recorded frames are folded in frame order (accumulate_frames_*, the hrt_compute_n combiner)
+  // and the recorded frames are folded in frame order (fold_frames, the hrt_compute_n combiner)
   // at the next observation or when the ring is full -- the per-frame combine's bytes, without a
   // combiner kernel queued between every two traces.
   void* ring = nullptr;        // ring_n frame images (context format), allocated by the first trace
@@ -220,7 +217,8 @@ struct hrt_context {
       if (((uint64_t)(r / row_tile) * part_count + part_index) * row_tile + r % row_tile < height) ++rows;
     return (size_t)rows * width;
   }
-  size_t px_bytes() const { return mode == HRT_MODE_RGBA8 ? 4 : 16; }
+  bool f32() const { return mode != HRT_MODE_RGBA8; }  // the format of every image of the context (hrt_image.h)
+  size_t px_bytes() const { return f32() ? 16 : 4; }
   size_t num_tiles() const { return (size_t)((width + 7) / 8) * ((local_rows + 7) / 8); }
 };
 
@@ -239,8 +237,6 @@ hrt_status release_lane(hrt_context* ctx, int l);  // lane l's buffers are free 
 const void* local_image(hrt_context* ctx, uint32_t image_id);
 // Folds the deferred combines (hrt_context::pend) into the accumulator on ctx->stream.
 hrt_status flush_combines(hrt_context* ctx);
-// The recording fold of nf frames of a stack into the accumulator (HRT_OPT_FOLD_RECORDS = 1), on ctx->stream.
-hrt_status fold_recorded(hrt_context* ctx, const void* stack, uint32_t nf, uint32_t frame0);
 // dst <- npix pixels at src (context format) converted to fmt via scratch, ordered on ctx->stream; blocking.
 hrt_status copy_frame_out(hrt_context* ctx, const void* src, size_t npix, uint32_t fmt, void* dst, void* scratch);
 // hrt_read_image on a context with a communicator (hrt_comm.cpp); arg = the caller's own argument
@@ -248,7 +244,7 @@ hrt_status copy_frame_out(hrt_context* ctx, const void* src, size_t npix, uint32
 hrt_status comm_read_image(hrt_context* ctx, uint32_t image_id, uint32_t fmt, void* dst, size_t bytes,
                            hrt_status arg);
 // The gathered present (hrt_present / hrt_accumulate_present on a context with a communicator, hrt_comm.cpp).
-struct PresentTarget;
+struct PresentTarget;  // hrt_image.h
 // HRT_OK when ctx is member 0 of an intact hrt_comm_init_all group; else HRT_ERR_INVALID_ARGUMENT with
 // the reason (`who` prefixes the message).  Host only: nothing is enqueued.
 hrt_status comm_present_check(hrt_context* ctx, const char* who);

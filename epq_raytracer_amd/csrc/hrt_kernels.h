@@ -1,4 +1,5 @@
-// hrt_kernels.h -- launch interface between the C-ABI layer (hrt_api.cpp) and the gfx950 kernels.
+// hrt_kernels.h -- launch interface between the C-ABI layer (hrt_api.cpp) and the gfx950 trace kernels
+// (hrt_kernels.hip); the image passes' is hrt_image.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,51 +104,10 @@ int resolve_variant(const TraceParams& p, int variant);  // the kernel an HRT_KE
 // Ray centres (first + px * x) + py * y for every pixel of a width x height image (hrt_generate_rays).
 hipError_t launch_make_rays(float4* rays, uint32_t width, uint32_t height, const float first[3], const float px[3],
                             const float py[3], hipStream_t stream);
-hipError_t launch_clear(uint32_t* img8, float4* img32, size_t npix, hipStream_t stream);
-// the nf frames of a stack (image f at f * npix) folded into the accumulator as frames frame0 + f
-hipError_t launch_accumulate_frames(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32,
-                                   size_t npix, uint32_t nf, uint32_t frame0, hipStream_t stream);
-// The fold of launch_accumulate_frames (store) or its chain in registers only (!store) with one fold record
-// per frame: frame f's counts are ADDED to ring[(slot0 + f) % HRT_FOLD_RECORD_RING], which the caller zeroed
-// on the stream before (changed_pixels, max_delta and abs_delta_sum; the host keeps the frame numbers).
-// real_pix <= npix: the pixels that count.  nf <= HRT_FOLD_RECORD_RING.  A single-frame fold is nf == 1
-// with the trace image as the stack.  The grid is sized by num_cus, not by npix.
-hipError_t launch_fold_records(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32, size_t npix,
-                               size_t real_pix, uint32_t nf, uint32_t frame0, bool store, hrt_fold_record* ring,
-                               uint32_t slot0, uint32_t num_cus, hipStream_t stream);
 hipError_t launch_tri_normals(const hrt_triangle* tris, float4* nhat, uint32_t n, hipStream_t stream);
 // BUNDLE_WQ's per-cell band records from the offsets and the 16-bit lists (hrt_kernels.hip band_cell).
 hipError_t launch_band_records(const uint32_t* off, const uint32_t* band16, uint32_t* rec, uint32_t cells,
                                hipStream_t stream);
-hipError_t launch_accumulate(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32, size_t npix,
-                             uint32_t frame, hipStream_t stream);
-// The present pass (hrt_present): the target of width x height pixels of 4 bytes, rows pitch bytes apart
-// (dst 4-byte aligned, pitch a multiple of 4); bgra: bytes 0 and 2 of each pixel swapped.
-struct PresentTarget {
-  unsigned char* dst;
-  uint32_t width, height, pitch, bgra;
-};
-// target(x, y) = the ws x hs image's texel (((2x+1) ws) div (2 width), hs - 1 - ((2y+1) hs) div (2 height)):
-// present_rows at the image's own size, else present_nearest (src8 or src32 set)
-hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws, uint32_t hs, const PresentTarget& t,
-                          hipStream_t stream);
-// The gathered present: the full width x height image as the root of a row-tile group holds it after the
-// gather -- parts blocks of local_rows x width pixels in part order (src8 or src32 set), global row y in
-// block (y / row_tile) % parts (hrt_present_map.h).  launch_present's rule over the full image, read
-// straight from the blocks: present_gathered_rows at the image's own size, else present_gathered_nearest.
-struct GatheredImage {
-  const uint32_t* src8;
-  const float4* src32;
-  uint32_t width, height, row_tile, parts, local_rows;
-};
-hipError_t launch_present_gathered(const GatheredImage& g, const PresentTarget& t, hipStream_t stream);
-// launch_accumulate on a w x h image (t of the same size) whose kernel also writes the folded pixel to t
-hipError_t launch_accumulate_present(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32,
-                                     uint32_t w, uint32_t h, uint32_t frame, const PresentTarget& t, hipStream_t stream);
-// Row-tile framebuffer assembly: gathered = parts x local_rows rows (rank-major), frame = height rows of
-// row_words 4-byte words; global row y comes from part (y / row_tile) % parts (hip_raytrace.h partition).
-hipError_t launch_assemble_rows(const uint32_t* gathered, uint32_t* frame, uint32_t row_words, uint32_t height,
-                                uint32_t local_rows, uint32_t row_tile, uint32_t parts, hipStream_t stream);
 // hrt_debug_math_check: fast division / sqrt paths vs the IEEE sequences (out[4] device counters).
 hipError_t launch_math_check(uint32_t n, uint32_t seed, unsigned long long* out, hipStream_t stream);
 hipError_t launch_band_flatten_check(const uint32_t* n, const uint32_t* b0, uint32_t rounds, uint32_t* out,
@@ -162,7 +122,5 @@ hipError_t launch_wq_protocol_check(uint32_t rounds, const uint32_t* cnt, const 
 // leaves of at most max_leaf triangles (0: does not fit the LDS)
 uint32_t wq_stack_cap(uint32_t n_nodes, uint32_t width, uint32_t max_leaf);
 constexpr uint32_t kAutoLeafWqStack = 512;  // auto leaf size: the smallest leaf whose image leaves this much
-hipError_t launch_convert(const uint32_t* src8, float4* dst32, const float4* src32, uint32_t* dst8, size_t npix,
-                          hipStream_t stream);
 
 }  // namespace hrt

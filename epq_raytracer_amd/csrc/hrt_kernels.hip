@@ -1,5 +1,4 @@
-// hrt_kernels.hip -- gfx950 kernels for the path-trace dispatch (assets/raytracing.glsl) and the
-// progressive accumulator (assets/image_combiner.glsl).
+// hrt_kernels.hip -- gfx950 kernels for the path-trace dispatch (assets/raytracing.glsl).
 //
 // One lane per pixel; each wave owns an 8x8 pixel tile (coherent primary rays), 256-thread
 // workgroups (1024 for the LDS-resident scene).  Scene records are read with wave-uniform addresses,
@@ -27,7 +26,6 @@
 #include "hrt_bvh.h"
 #include "hrt_kernels.h"
 #include "hrt_math.h"
-#include "hrt_present_map.h"
 
 namespace hrt {
 
@@ -2922,363 +2920,6 @@ __global__ __launch_bounds__(256) void make_rays(float4* rays, uint32_t width, u
                                             (fz + pxz * xf) + pyz * yf, 1.0f);
 }
 
-// ---- init clear (raytracing.glsl:363-366) and image_combiner.glsl (:22-43) ----------------------
-__global__ __launch_bounds__(256) void clear_kernel(uint32_t* img8, float4* img32, size_t npix) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix) return;
-  if (img8) img8[i] = 255u << 24;
-  if (img32) img32[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-}
-
-// image_combiner.glsl:22-43 for one pixel: frame 0 clears, frame k folds the new frame in.
-__device__ __forceinline__ uint32_t combine_rgba8(uint32_t pv, uint32_t nv, uint32_t frame) {
-  if (frame == 0) return 255u << 24;
-  const float ff = (float)frame, ff1 = (float)(frame + 1u);
-  uint32_t out = 255u << 24;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float prev = unorm8_to_float((pv >> (8 * ch)) & 255u);
-    const float nc = unorm8_to_float((nv >> (8 * ch)) & 255u);
-    out |= unorm8((nc + prev * ff) / ff1) << (8 * ch);
-  }
-  return out;
-}
-__device__ __forceinline__ float4 combine_rgba32f(float4 p, float4 n, uint32_t frame) {
-  if (frame == 0) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-  const float ff = (float)frame, ff1 = (float)(frame + 1u);
-  return make_float4((n.x + p.x * ff) / ff1, (n.y + p.y * ff) / ff1, (n.z + p.z * ff) / ff1, 1.0f);
-}
-// combine_rgba8 with its nine IEEE divisions replaced by the same quotients (r05): the six UNORM8 loads
-// k / 255 from a 256-entry table of those quotients (unorm8_to_float, built once per workgroup in LDS),
-// and the three divisions by frame + 1 through that denominator's reciprocal, shared by the channels
-// (div_core: rcp_core is RN(1 / b) on [2^-40, 2^40], every numerator here is 0 or in [2^-8, 2^33], so
-// Markstein's correction gives the correctly rounded quotient; a zero numerator gives +0 as the IEEE
-// division does).  combine_rgba8 stays the reference spelling (tests/test_gpu_parity.py holds every
-// accumulator to the oracle's combiner).
-__device__ __forceinline__ uint32_t combine_rgba8_fast(uint32_t pv, uint32_t nv, uint32_t frame, const float* tab) {
-  if (frame == 0) return 255u << 24;
-  const float ff = (float)frame, ff1 = (float)(frame + 1u), y = rcp_core(ff1);
-  uint32_t out = 255u << 24;
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const float prev = tab[(pv >> (8 * ch)) & 255u];
-    const float nc = tab[(nv >> (8 * ch)) & 255u];
-    out |= unorm8(div_core(nc + prev * ff, ff1, y)) << (8 * ch);
-  }
-  return out;
-}
-#ifndef HRT_COMBINE_FAST
-#define HRT_COMBINE_FAST 1
-#endif
-__device__ __forceinline__ void unorm8_table(float* tab) {  // blockDim.x == 256
-  tab[threadIdx.x] = unorm8_to_float(threadIdx.x);
-  __syncthreads();
-}
-__global__ __launch_bounds__(256) void accumulate_rgba8(uint32_t* cur, const uint32_t* nw, size_t npix, uint32_t frame) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-#if HRT_COMBINE_FAST
-  __shared__ float tab[256];
-  unorm8_table(tab);
-  if (i >= npix) return;
-  cur[i] = combine_rgba8_fast(frame == 0 ? 0u : cur[i], nw[i], frame, tab);
-#else
-  if (i >= npix) return;
-  cur[i] = combine_rgba8(frame == 0 ? 0u : cur[i], nw[i], frame);
-#endif
-}
-// hrt_compute_n: the nf frames of one launch folded in frame order in one pass (frame frame0 + f is
-// image f of the stack): the per-frame combiner's arithmetic, pixel by pixel, with the accumulator
-// read and written once instead of once per frame.
-__global__ __launch_bounds__(256) void accumulate_frames_rgba8(uint32_t* cur, const uint32_t* stack, size_t npix,
-                                                             uint32_t nf, uint32_t frame0) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-#if HRT_COMBINE_FAST
-  __shared__ float tab[256];
-  unorm8_table(tab);
-#endif
-  if (i >= npix) return;
-  uint32_t v = cur[i];
-#if HRT_COMBINE_FAST
-  for (uint32_t f = 0; f < nf; ++f) v = combine_rgba8_fast(v, stack[f * npix + i], frame0 + f, tab);
-#else
-  for (uint32_t f = 0; f < nf; ++f) v = combine_rgba8(v, stack[f * npix + i], frame0 + f);
-#endif
-  cur[i] = v;
-}
-__global__ __launch_bounds__(256) void accumulate_frames_rgba32f(float4* cur, const float4* stack, size_t npix,
-                                                               uint32_t nf, uint32_t frame0) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix) return;
-  float4 v = cur[i];
-  for (uint32_t f = 0; f < nf; ++f) v = combine_rgba32f(v, stack[f * npix + i], frame0 + f);
-  cur[i] = v;
-}
-
-__global__ __launch_bounds__(256) void accumulate_rgba32f(float4* cur, const float4* nw, size_t npix, uint32_t frame) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix) return;
-  cur[i] = combine_rgba32f(frame == 0 ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : cur[i], nw[i], frame);
-}
-
-// ---- fold records (HRT_OPT_FOLD_RECORDS, hrt_compute_until) -------------------------
-// The fold chain of accumulate_frames_* with, per frame, the record of what the fold did to the
-// DISPLAYED image: pixels whose displayed word changed, the byte sum of absolute differences, the
-// largest byte difference -- over the real pixels (i < real_pix; padding rows of a row-tile part are
-// folded but never counted).  All integers, so the sums do not depend on the order they are taken in.
-// Reduction: a wave ballots the changed lanes (no lane changed: nothing more for that frame), reduces
-// sum and maximum across its lanes, lane 0 adds them to the workgroup's per-frame LDS slots; after the
-// pixel walk the workgroup issues at most one global atomic triple (u32 add, u64 add, u32 max) per frame.
-// The grid is sized by the CU count (launch_fold_records) and strides over the pixels, so a frame's slot
-// sees at most 8 x CUs triples however large the image.  Store == false runs the chain in registers
-// only (hrt_compute_until's count pass).
-constexpr uint32_t kFoldMaxFrames = HRT_FOLD_RECORD_RING;  // per launch: the LDS slots
-static_assert((kFoldMaxFrames & (kFoldMaxFrames - 1u)) == 0, "the ring is indexed with a mask");
-__device__ __forceinline__ uint32_t displayed_word(uint32_t v) { return v; }
-__device__ __forceinline__ uint32_t displayed_word(float4 v) {  // f32_to_rgba8's word
-  return unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
-}
-__device__ __forceinline__ uint32_t fold_step(uint32_t v, uint32_t n, uint32_t frame, const float* tab) {
-#if HRT_COMBINE_FAST
-  return combine_rgba8_fast(v, n, frame, tab);
-#else
-  (void)tab;
-  return combine_rgba8(v, n, frame);
-#endif
-}
-__device__ __forceinline__ float4 fold_step(float4 v, float4 n, uint32_t frame, const float*) {
-  return combine_rgba32f(v, n, frame);
-}
-template <typename T>
-__device__ __forceinline__ T fold_zero();
-template <>
-__device__ __forceinline__ uint32_t fold_zero<uint32_t>() {
-  return 0u;
-}
-template <>
-__device__ __forceinline__ float4 fold_zero<float4>() {
-  return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-template <typename T, bool Store>
-__global__ __launch_bounds__(256) void fold_records(T* cur, const T* stack, size_t npix, size_t real_pix, uint32_t nf,
-                                                    uint32_t frame0, hrt_fold_record* ring, uint32_t slot0,
-                                                    uint32_t mask) {
-  __shared__ float tab[256];
-  __shared__ uint32_t s_cnt[kFoldMaxFrames], s_max[kFoldMaxFrames];
-  __shared__ unsigned long long s_sum[kFoldMaxFrames];
-  for (uint32_t f = threadIdx.x; f < nf; f += 256u) {
-    s_cnt[f] = 0u;
-    s_max[f] = 0u;
-    s_sum[f] = 0ull;
-  }
-  unorm8_table(tab);  // (and the barrier)
-  const uint32_t lane = threadIdx.x & 63u;
-  const size_t stride = (size_t)gridDim.x * 256u;
-  // (the walk is workgroup-uniform: every lane of a wave reaches the ballot and the shuffles)
-  for (size_t base = (size_t)blockIdx.x * 256u; base < npix; base += stride) {
-    const size_t i = base + threadIdx.x;
-    const bool in = i < npix, real = i < real_pix;
-    T v = in ? cur[i] : fold_zero<T>();
-    uint32_t d = displayed_word(v);
-    T nxt = in ? stack[i] : fold_zero<T>();
-    for (uint32_t f = 0; f < nf; ++f) {
-      const T n = nxt;
-      if (f + 1u < nf && in) nxt = stack[(size_t)(f + 1u) * npix + i];
-      v = fold_step(v, n, frame0 + f, tab);
-      const uint32_t dw = displayed_word(v);
-      const bool ch = real && dw != d;
-      const unsigned long long b = __ballot(ch);
-      if (b != 0ull) {
-        uint32_t sad = 0u, mx = 0u;
-        if (ch) {
-          sad = __builtin_amdgcn_sad_u8(dw, d, 0u);
-          const uint32_t b0 = __builtin_amdgcn_sad_u8(dw & 0xFFu, d & 0xFFu, 0u);
-          const uint32_t b1 = __builtin_amdgcn_sad_u8(dw & 0xFF00u, d & 0xFF00u, 0u);
-          const uint32_t b2 = __builtin_amdgcn_sad_u8(dw & 0xFF0000u, d & 0xFF0000u, 0u);
-          const uint32_t b3 = __builtin_amdgcn_sad_u8(dw >> 24, d >> 24, 0u);
-          mx = max(max(b0, b1), max(b2, b3));
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          sad += (uint32_t)__shfl_xor((int)sad, off, 64);
-          mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
-        }
-        if (lane == 0u) {
-          atomicAdd(&s_cnt[f], (uint32_t)__popcll(b));
-          atomicAdd(&s_sum[f], (unsigned long long)sad);
-          atomicMax(&s_max[f], mx);
-        }
-      }
-      d = dw;
-    }
-    if (Store && in) cur[i] = v;
-  }
-  __syncthreads();
-  for (uint32_t f = threadIdx.x; f < nf; f += 256u) {
-    if (s_cnt[f] == 0u) continue;  // (a changed pixel has a byte difference >= 1: sum and maximum are 0 too)
-    hrt_fold_record* r = ring + ((slot0 + f) & mask);
-    atomicAdd(&r->changed_pixels, s_cnt[f]);
-    atomicAdd(reinterpret_cast<unsigned long long*>(&r->abs_delta_sum), s_sum[f]);
-    atomicMax(&r->max_delta, s_max[f]);
-  }
-}
-
-// format conversion for hrt_read_image
-__global__ __launch_bounds__(256) void rgba8_to_f32(const uint32_t* src, float4* dst, size_t npix) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix) return;
-  const uint32_t v = src[i];
-  dst[i] = make_float4(unorm8_to_float(v & 255u), unorm8_to_float((v >> 8) & 255u), unorm8_to_float((v >> 16) & 255u),
-                       unorm8_to_float(v >> 24));
-}
-__global__ __launch_bounds__(256) void f32_to_rgba8(const float4* src, uint32_t* dst, size_t npix) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= npix) return;
-  const float4 v = src[i];
-  dst[i] = unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
-}
-
-// ---- the present pass (RenderPassOverFrame::render, src/texture_draw_pipeline.rs:96-157) ------------
-// The image as the reference's full-target quad draws it: nearest filter, flipped vertically.  One
-// target row per grid.y, so the source row is wave-uniform and the stores of a row stream coalesced.
-// A target pixel is the source's RGBA8 word (an RGBA32F texel converted as f32_to_rgba8 converts it),
-// with bytes 0 and 2 swapped for a B8G8R8A8 target: one v_perm_b32 per word.
-__device__ __forceinline__ uint32_t present_word(uint32_t v, uint32_t bgra) {
-  return bgra ? __builtin_amdgcn_perm(v, v, 0x03000102u) : v;
-}
-__device__ __forceinline__ uint32_t present_load(const uint32_t* s, size_t i) { return s[i]; }
-__device__ __forceinline__ uint32_t present_load(const float4* s, size_t i) {
-  const float4 v = s[i];
-  return unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
-}
-// Target of the image's own size: dst(x, y) = src(x, h - 1 - y).  Four pixels per lane -- one 128-bit
-// load (four float4 loads of an RGBA32F source) and one 128-bit store -- over the row's whole quads
-// while the row of the target and of an RGBA8 source both start on a 16 B boundary (an odd width, pitch
-// or base leaves only some rows there); the row's last w % 4 pixels, and every pixel of a row that
-// does not, go one word per lane.
-template <typename T>
-__global__ __launch_bounds__(256) void present_rows(const T* __restrict__ src, unsigned char* __restrict__ dst, uint32_t w,
-                                                    uint32_t h, uint32_t pitch, uint32_t bgra) {
-  const uint32_t y = blockIdx.y;
-  const T* s = src + (size_t)(h - 1u - y) * w;
-  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
-  const bool vec = (((uintptr_t)d | (sizeof(T) == 4 ? (uintptr_t)s : (uintptr_t)0)) & 15u) == 0;
-  const uint32_t quads = vec ? w / 4u : 0u;
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
-  for (uint32_t q = t; q < quads; q += stride) {
-    uint4 v;
-    if constexpr (sizeof(T) == 4) {
-      v = reinterpret_cast<const uint4*>(s)[q];
-    } else {
-      v = make_uint4(present_load(s, 4u * q), present_load(s, 4u * q + 1u), present_load(s, 4u * q + 2u),
-                     present_load(s, 4u * q + 3u));
-    }
-    reinterpret_cast<uint4*>(d)[q] =
-        make_uint4(present_word(v.x, bgra), present_word(v.y, bgra), present_word(v.z, bgra), present_word(v.w, bgra));
-  }
-  for (uint32_t i = quads * 4u + t; i < w; i += stride) d[i] = present_word(present_load(s, i), bgra);
-}
-// Target of another size: sample points at the target's pixel centres, texel = floor of the centre's
-// source coordinate -- the pinned integer rule, 64-bit so that no size overflows:
-//   sx = ((2x+1) ws) div (2 wt),  sy = hs - 1 - ((2y+1) hs) div (2 ht).
-// sy once per row (wave-uniform), sx per lane: coalesced stores, loads gathered along one source row.
-template <typename T>
-__global__ __launch_bounds__(256) void present_nearest(const T* __restrict__ src, uint32_t ws, uint32_t hs,
-                                                       unsigned char* __restrict__ dst, uint32_t wt, uint32_t ht,
-                                                       uint32_t pitch, uint32_t bgra) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t sy = hs - 1u - (uint32_t)(((2ull * y + 1ull) * hs) / (2ull * ht));
-  const T* s = src + (size_t)sy * ws;
-  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
-  for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < wt; x += gridDim.x * 256u) {
-    const uint32_t sx = (uint32_t)(((2ull * x + 1ull) * ws) / (2ull * wt));
-    d[x] = present_word(present_load(s, sx), bgra);
-  }
-}
-// The gathered present (hrt_present on the root of an hrt_comm_init_all group): the source is the root's
-// gather buffer -- the parts' blocks of local_rows x w pixels in part order -- read where the row-tile
-// partition put each global row (hrt_present_map.h gathered_row), so the un-interleave, the conversion
-// and the copy of the read path are one read and one write.  The shape is present_rows' / present_nearest's:
-// the target row is grid.y, so the source row, its part and its local row are wave-uniform; the row
-// offset is 64-bit (parts x local_rows x w x 16 B may pass 2^32).  At equal size the 128-bit body runs
-// on the rows whose target row and (RGBA8) gathered source row both start on a 16 B boundary: with an
-// odd width consecutive global rows of one tile alternate, and a tile's first row depends on its block.
-template <typename T>
-__global__ __launch_bounds__(256) void present_gathered_rows(const T* __restrict__ src, unsigned char* __restrict__ dst,
-                                                             uint32_t w, uint32_t h, uint32_t pitch, uint32_t bgra,
-                                                             uint32_t row_tile, uint32_t parts, uint32_t local_rows) {
-  const uint32_t y = blockIdx.y;
-  const T* s = src + gathered_row(present_sy(y, h, h), row_tile, parts, local_rows) * w;
-  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
-  const bool vec = (((uintptr_t)d | (sizeof(T) == 4 ? (uintptr_t)s : (uintptr_t)0)) & 15u) == 0;
-  const uint32_t quads = vec ? w / 4u : 0u;
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;
-  for (uint32_t q = t; q < quads; q += stride) {
-    uint4 v;
-    if constexpr (sizeof(T) == 4) {
-      v = reinterpret_cast<const uint4*>(s)[q];
-    } else {
-      v = make_uint4(present_load(s, 4u * q), present_load(s, 4u * q + 1u), present_load(s, 4u * q + 2u),
-                     present_load(s, 4u * q + 3u));
-    }
-    reinterpret_cast<uint4*>(d)[q] =
-        make_uint4(present_word(v.x, bgra), present_word(v.y, bgra), present_word(v.z, bgra), present_word(v.w, bgra));
-  }
-  for (uint32_t i = quads * 4u + t; i < w; i += stride) d[i] = present_word(present_load(s, i), bgra);
-}
-// ... into a target of another size: sy of the FULL ws x hs image once per row, then its gathered row.
-template <typename T>
-__global__ __launch_bounds__(256) void present_gathered_nearest(const T* __restrict__ src, uint32_t ws, uint32_t hs,
-                                                                unsigned char* __restrict__ dst, uint32_t wt, uint32_t ht,
-                                                                uint32_t pitch, uint32_t bgra, uint32_t row_tile,
-                                                                uint32_t parts, uint32_t local_rows) {
-  const uint32_t y = blockIdx.y;
-  const T* s = src + gathered_row(present_sy(y, hs, ht), row_tile, parts, local_rows) * ws;
-  uint32_t* d = reinterpret_cast<uint32_t*>(dst + (size_t)y * pitch);
-  for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < wt; x += gridDim.x * 256u)
-    d[x] = present_word(present_load(s, present_sx(x, ws, wt)), bgra);
-}
-// hrt_accumulate_present at the image's own size: accumulate_rgba8 / accumulate_rgba32f (the same
-// combine_* arithmetic, 256 threads, the UNORM8 table in LDS) whose thread also writes the folded pixel
-// to the flipped target row -- the accumulator is not read again by a present pass (w * h <= 2^28).
-__global__ __launch_bounds__(256) void accumulate_present_rgba8(uint32_t* cur, const uint32_t* nw, uint32_t w, uint32_t h,
-                                                                uint32_t frame, unsigned char* __restrict__ dst,
-                                                                uint32_t pitch, uint32_t bgra) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  __shared__ float tab[256];
-  unorm8_table(tab);
-  if (i >= w * h) return;
-  const uint32_t v = combine_rgba8_fast(frame == 0 ? 0u : cur[i], nw[i], frame, tab);
-  cur[i] = v;
-  const uint32_t y = i / w, x = i - y * w;
-  reinterpret_cast<uint32_t*>(dst + (size_t)(h - 1u - y) * pitch)[x] = present_word(v, bgra);
-}
-__global__ __launch_bounds__(256) void accumulate_present_rgba32f(float4* cur, const float4* nw, uint32_t w, uint32_t h,
-                                                                  uint32_t frame, unsigned char* __restrict__ dst,
-                                                                  uint32_t pitch, uint32_t bgra) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= w * h) return;
-  const float4 v = combine_rgba32f(frame == 0 ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : cur[i], nw[i], frame);
-  cur[i] = v;
-  const uint32_t y = i / w, x = i - y * w;
-  const uint32_t px = unorm8(v.x) | (unorm8(v.y) << 8) | (unorm8(v.z) << 16) | (unorm8(v.w) << 24);
-  reinterpret_cast<uint32_t*>(dst + (size_t)(h - 1u - y) * pitch)[x] = present_word(px, bgra);
-}
-
-// Row-tile framebuffer assembly after the gather: global row y lives in part
-// (y / row_tile) % parts at local row (y / row_tile / parts) * row_tile + y % row_tile.  One 4-byte word
-// per lane; grid.y = rows, so the row arithmetic is wave-uniform and both sides stream coalesced.
-__global__ __launch_bounds__(256) void assemble_rows(const uint32_t* __restrict__ gathered, uint32_t* __restrict__ frame,
-                                                     uint32_t row_words, uint32_t local_rows, uint32_t row_tile,
-                                                     uint32_t parts) {
-  const uint32_t y = blockIdx.y;
-  const uint32_t t = y / row_tile;
-  const uint32_t part = t % parts;
-  const uint32_t lr = (t / parts) * row_tile + y % row_tile;
-  const uint32_t* src = gathered + ((size_t)part * local_rows + lr) * row_words;
-  uint32_t* dst = frame + (size_t)y * row_words;
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < row_words; i += gridDim.x * 256) dst[i] = src[i];
-}
-
 // Self-check of hrt_math.h's shared-reciprocal division and sqrt paths against the compiler's IEEE
 // sequences, bit for bit, on hashed inputs (exponents over the whole range for a third of the
 // threads, the fast-path range for the rest).  out[0..3]: normalize, div3, sqrt mismatches, fast cases.
@@ -3418,7 +3059,6 @@ __global__ __launch_bounds__(256) void math_check(uint32_t n, uint32_t seed, uns
 // ---- launch wrappers (host) ----------------------------------------------------------------------
 namespace hrt {
 
-static inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 constexpr size_t kMaxLdsScene = 160 * 1024 - 64;  // dynamic LDS per CU, leaving room for the kernels' static LDS
 constexpr uint32_t kAutoCullTris = 256;   // BUNDLE_CULL from this many mesh triangles, BUNDLE below
 constexpr uint32_t kAutoBvhTris = 4096;   // BUNDLE_BVH from this many (profiles/r01d_bvh_scaling.log)
@@ -3675,39 +3315,6 @@ hipError_t launch_make_rays(float4* rays, uint32_t width, uint32_t height, const
   return hipGetLastError();
 }
 
-hipError_t launch_accumulate_frames(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32,
-                                   size_t npix, uint32_t nf, uint32_t frame0, hipStream_t stream) {
-  if (npix == 0 || nf == 0) return hipSuccess;
-  if (cur8)
-    accumulate_frames_rgba8<<<blocks_for(npix), 256, 0, stream>>>(cur8, stack8, npix, nf, frame0);
-  else
-    accumulate_frames_rgba32f<<<blocks_for(npix), 256, 0, stream>>>(cur32, stack32, npix, nf, frame0);
-  return hipGetLastError();
-}
-
-hipError_t launch_fold_records(uint32_t* cur8, const uint32_t* stack8, float4* cur32, const float4* stack32, size_t npix,
-                               size_t real_pix, uint32_t nf, uint32_t frame0, bool store, hrt_fold_record* ring,
-                               uint32_t slot0, uint32_t num_cus, hipStream_t stream) {
-  if (nf == 0) return hipSuccess;
-  if (nf > kFoldMaxFrames || !ring || real_pix > npix || npix == 0) return hipErrorInvalidValue;
-  // eight workgroups of four waves per CU (full occupancy beside 17 KiB of LDS each), never more than the pixels need
-  const unsigned int grid = std::min<unsigned int>(blocks_for(npix), std::max(1u, num_cus) * 8u);
-  const uint32_t mask = kFoldMaxFrames - 1u;
-  slot0 &= mask;
-  if (cur8) {
-    if (store)
-      fold_records<uint32_t, true><<<grid, 256, 0, stream>>>(cur8, stack8, npix, real_pix, nf, frame0, ring, slot0, mask);
-    else
-      fold_records<uint32_t, false><<<grid, 256, 0, stream>>>(cur8, stack8, npix, real_pix, nf, frame0, ring, slot0, mask);
-  } else {
-    if (store)
-      fold_records<float4, true><<<grid, 256, 0, stream>>>(cur32, stack32, npix, real_pix, nf, frame0, ring, slot0, mask);
-    else
-      fold_records<float4, false><<<grid, 256, 0, stream>>>(cur32, stack32, npix, real_pix, nf, frame0, ring, slot0, mask);
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_band_records(const uint32_t* off, const uint32_t* band16, uint32_t* rec, uint32_t cells,
                                hipStream_t stream) {
   if (cells == 0) return hipSuccess;
@@ -3718,96 +3325,6 @@ hipError_t launch_band_records(const uint32_t* off, const uint32_t* band16, uint
 hipError_t launch_tri_normals(const hrt_triangle* tris, float4* nhat, uint32_t n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   tri_normals<<<(n + 255) / 256, 256, 0, stream>>>(tris, nhat, n);
-  return hipGetLastError();
-}
-
-hipError_t launch_clear(uint32_t* img8, float4* img32, size_t npix, hipStream_t stream) {
-  if (npix == 0) return hipSuccess;
-  clear_kernel<<<blocks_for(npix), 256, 0, stream>>>(img8, img32, npix);
-  return hipGetLastError();
-}
-
-hipError_t launch_accumulate(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32, size_t npix,
-                             uint32_t frame, hipStream_t stream) {
-  if (npix == 0) return hipSuccess;
-  if (cur8)
-    accumulate_rgba8<<<blocks_for(npix), 256, 0, stream>>>(cur8, new8, npix, frame);
-  else
-    accumulate_rgba32f<<<blocks_for(npix), 256, 0, stream>>>(cur32, new32, npix, frame);
-  return hipGetLastError();
-}
-
-template <typename T>
-static void present_launch(const T* src, uint32_t ws, uint32_t hs, const PresentTarget& t, hipStream_t stream) {
-  if (t.width == ws && t.height == hs) {  // a lane moves four pixels; rows off the 16 B grid loop
-    const dim3 g(((t.width + 3) / 4 + 255) / 256, t.height, 1);
-    present_rows<T><<<g, 256, 0, stream>>>(src, t.dst, ws, hs, t.pitch, t.bgra);
-  } else {
-    const dim3 g((t.width + 255) / 256, t.height, 1);
-    present_nearest<T><<<g, 256, 0, stream>>>(src, ws, hs, t.dst, t.width, t.height, t.pitch, t.bgra);
-  }
-}
-
-hipError_t launch_present(const uint32_t* src8, const float4* src32, uint32_t ws, uint32_t hs, const PresentTarget& t,
-                          hipStream_t stream) {
-  // (grid.y = target rows; the checks of hrt_present, repeated where the launch is shaped)
-  if (ws == 0 || hs == 0 || t.width == 0 || t.height == 0 || t.height > 65535u || t.pitch / 4 < t.width || !t.dst)
-    return hipErrorInvalidValue;
-  if (src8)
-    present_launch(src8, ws, hs, t, stream);
-  else
-    present_launch(src32, ws, hs, t, stream);
-  return hipGetLastError();
-}
-
-template <typename T>
-static void present_gathered_launch(const T* src, const GatheredImage& g, const PresentTarget& t, hipStream_t stream) {
-  if (t.width == g.width && t.height == g.height) {
-    const dim3 grid(((t.width + 3) / 4 + 255) / 256, t.height, 1);
-    present_gathered_rows<T><<<grid, 256, 0, stream>>>(src, t.dst, g.width, g.height, t.pitch, t.bgra, g.row_tile,
-                                                        g.parts, g.local_rows);
-  } else {
-    const dim3 grid((t.width + 255) / 256, t.height, 1);
-    present_gathered_nearest<T><<<grid, 256, 0, stream>>>(src, g.width, g.height, t.dst, t.width, t.height, t.pitch,
-                                                           t.bgra, g.row_tile, g.parts, g.local_rows);
-  }
-}
-
-hipError_t launch_present_gathered(const GatheredImage& g, const PresentTarget& t, hipStream_t stream) {
-  if (g.width == 0 || g.height == 0 || t.width == 0 || t.height == 0 || t.height > 65535u || t.pitch / 4 < t.width ||
-      !t.dst || (!g.src8 && !g.src32))
-    return hipErrorInvalidValue;
-  // (launch_assemble_rows' bound: every global row below height lies inside its part's local rows)
-  if (g.parts == 0 || g.row_tile == 0 ||
-      (uint64_t)((g.height - 1) / g.row_tile / g.parts + 1) * g.row_tile > g.local_rows)
-    return hipErrorInvalidValue;
-  if (g.src8)
-    present_gathered_launch(g.src8, g, t, stream);
-  else
-    present_gathered_launch(g.src32, g, t, stream);
-  return hipGetLastError();
-}
-
-hipError_t launch_accumulate_present(uint32_t* cur8, const uint32_t* new8, float4* cur32, const float4* new32,
-                                     uint32_t w, uint32_t h, uint32_t frame, const PresentTarget& t, hipStream_t stream) {
-  if (w == 0 || h == 0 || t.width != w || t.height != h || (uint64_t)w * h > (1ull << 28) || t.pitch / 4 < w || !t.dst)
-    return hipErrorInvalidValue;
-  if (cur8)
-    accumulate_present_rgba8<<<blocks_for((size_t)w * h), 256, 0, stream>>>(cur8, new8, w, h, frame, t.dst, t.pitch,
-                                                                           t.bgra);
-  else
-    accumulate_present_rgba32f<<<blocks_for((size_t)w * h), 256, 0, stream>>>(cur32, new32, w, h, frame, t.dst, t.pitch,
-                                                                             t.bgra);
-  return hipGetLastError();
-}
-
-hipError_t launch_assemble_rows(const uint32_t* gathered, uint32_t* frame, uint32_t row_words, uint32_t height,
-                                uint32_t local_rows, uint32_t row_tile, uint32_t parts, hipStream_t stream) {
-  if (row_words == 0 || height == 0) return hipSuccess;
-  if (parts == 0 || row_tile == 0 || (uint64_t)((height - 1) / row_tile / parts + 1) * row_tile > local_rows)
-    return hipErrorInvalidValue;  // some global row would read outside its part's local rows
-  const dim3 g(std::min<uint32_t>((row_words + 255) / 256, 64), height, 1);
-  assemble_rows<<<g, 256, 0, stream>>>(gathered, frame, row_words, local_rows, row_tile, parts);
   return hipGetLastError();
 }
 
@@ -3834,16 +3351,6 @@ hipError_t launch_math_check_rng(unsigned long long* out, hipStream_t stream) {
 hipError_t launch_math_check(uint32_t n, uint32_t seed, unsigned long long* out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   math_check<<<(n + 255) / 256, 256, 0, stream>>>(n, seed, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_convert(const uint32_t* src8, float4* dst32, const float4* src32, uint32_t* dst8, size_t npix,
-                          hipStream_t stream) {
-  if (npix == 0) return hipSuccess;
-  if (src8)
-    rgba8_to_f32<<<blocks_for(npix), 256, 0, stream>>>(src8, dst32, npix);
-  else
-    f32_to_rgba8<<<blocks_for(npix), 256, 0, stream>>>(src32, dst8, npix);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // hrt_present_map.h -- the index arithmetic of the gathered present pass (hrt_present on the root of an
-// hrt_comm_init_all group), shared by the kernels (hrt_kernels.hip present_gathered_*) and a plain C++
+// hrt_comm_init_all group), shared by the kernels (hrt_image.hip present_rows / present_nearest) and a plain C++
 // test program (tests/cpp/present_map_test.cpp): no HIP header is needed to compile it.
 //
 // The sampling rule is the one pinned for hrt_present (include/hip_raytrace.h): sample

@@ -1,5 +1,5 @@
 // present_map_test.cpp -- prints the gathered present's index arithmetic (epq_raytracer_amd/csrc/
-// hrt_present_map.h, the functions the present_gathered_* kernels call) compiled as plain C++, for
+// hrt_present_map.h, the functions hrt_image.hip's present kernels call) compiled as plain C++, for
 // tests/test_present_gather_map.py to compare with the numpy rule (tests/present_ref.py) and the
 // row-tile assembly (epq_raytracer_amd/rowtiles.py).
 //

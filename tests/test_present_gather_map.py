@@ -1,5 +1,5 @@
 """The gathered present's index arithmetic (epq_raytracer_amd/csrc/hrt_present_map.h: present_sx,
-present_sy, gathered_row -- the functions the present_gathered_* kernels call), CPU only.  The test
+present_sy, gathered_row -- the functions hrt_image.hip's present kernels call), CPU only.  The test
 compiles tests/cpp/present_map_test.cpp as plain C++ against the header, runs it over every case and
 compares with the numpy sampling rule (tests/present_ref.py) and with the row-tile assembly of
 epq_raytracer_amd/rowtiles.py; once more with the program built under ASan + UBSan."""

@@ -1,5 +1,5 @@
 #!/bin/bash
-# r05l: the rgba8 combiner with a UNORM8 table and a shared reciprocal (HRT_COMBINE_FAST, ab_combfast) against
+# r05l: the rgba8 combiner with a UNORM8 table and a shared reciprocal (the ab_combfast build) against
 # the reference spelling (ab_base): GPU suite subset on the in-tree build, then bench.py itself (ms per step,
 # per_frame_dispatch_ms) alternating, and the accumulate kernels' times from a rocprofv3 kernel trace.
 set -o pipefail
