@@ -114,6 +114,7 @@ OPT_KERNEL_VARIANT, OPT_COUNTERS, OPT_SECONDARY_BATCH, OPT_BVH_LEAF_SIZE = 1, 2,
 OPT_SPLIT, OPT_SPLIT_FACTOR, OPT_PRIORITY, OPT_GRID_CUS, OPT_COOP, OPT_WQ_NODE_CAP, OPT_PROBE = 5, 6, 7, 8, 9, 10, 11
 OPT_FRAMES_PER_LAUNCH, OPT_OVERLAP, OPT_BUSY_SPLIT, OPT_BVH_WIDTH, OPT_WQ_NODE_RADIUS = 12, 13, 14, 15, 16
 OPT_COMM_TIMEOUT_MS, OPT_DEFER_COMBINE, OPT_FOLD_RECORDS = 17, 18, 19
+OPT_SKY_LANE = 20  # BUNDLE_WQ: sky items on trace_sky beside the main kernel (-1 auto, 0 off, 1 on)
 DEBUG_OPT_FAIL_ALLOC = 1001  # libhip_raytrace_debug.so only
 DEBUG_OPT_WQ_TRI_CAP = 1002  # libhip_raytrace_debug.so only
 DEBUG_OPT_GRAB_RUNS = 1003  # libhip_raytrace_debug.so only
@@ -165,7 +166,7 @@ EXPORTED_SYMBOLS = (
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
-    "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs",
+    "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_stream", "hrt_release_caches", "hrt_last_error", "hrt_comm_unique_id", "hrt_comm_init", "hrt_comm_init_all", "hrt_comm_info",
     "hrt_host_create_rays", "hrt_host_ray_grid", "hrt_host_view_matrix", "hrt_host_transform_meshes",
     "hrt_debug_bvh_build", "hrt_debug_bvh_wq_nodes",
@@ -246,6 +247,7 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_debug_timeline": (c_int32, [c_void_p, P, c_uint32, P]),
         "hrt_debug_band_records": (c_int32, [c_void_p, P, c_uint64, P, c_uint64, P, c_uint64, P]),
         "hrt_debug_tile_costs": (c_int32, [c_void_p, P, c_uint32]),
+        "hrt_debug_sky_units": (c_int32, [c_void_p, P]),
         "hrt_debug_bvh_build": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P, c_uint64, P, c_uint64, P,
                                           c_uint64, P, c_uint64, P, c_uint64]),
         "hrt_debug_bvh_wq_nodes": (c_int64, [P, c_uint32, P, c_uint32, c_uint32, c_uint32, P, c_uint64]),

@@ -294,6 +294,18 @@ extern "C" hrt_status hrt_debug_tile_costs(hrt_context* ctx, uint32_t* out, uint
   return HRT_OK;
 }
 
+// Test support: the work units (tile x frame) that trace_sky has run on this context since creation or
+// hrt_reset_stats -- a test of the sky lane proves with it that the side kernel rendered items.
+extern "C" hrt_status hrt_debug_sky_units(hrt_context* ctx, uint64_t* out) {
+  if (!ctx || !out) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = hrt_synchronize(ctx);
+  if (st != HRT_OK) return st;
+  unsigned long long v = 0;
+  HRT_HIP(ctx, hipMemcpy(&v, ctx->counters + hrt::kSkyUnitsCounter, sizeof v, hipMemcpyDeviceToHost));
+  *out = v;
+  return HRT_OK;
+}
+
 // Test support: the context's grazing-band structure as the device holds it -- the per-cell records
 // (band_records), the offsets and the entry words -- so a test can hold the device-built records to the
 // lists they summarise.  info = {cells, entries, wide (32-bit entries), records present}.
@@ -444,6 +456,10 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
     free_dev(ctx, l.tl_cache);
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.free) (void)hipEventDestroy(l.free);
+    if (l.sky_stream) (void)hipStreamSynchronize(l.sky_stream);
+    if (l.sky_fork) (void)hipEventDestroy(l.sky_fork);
+    if (l.sky_join) (void)hipEventDestroy(l.sky_join);
+    if (l.sky_stream) (void)hipStreamDestroy(l.sky_stream);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
   free_dev(ctx, ctx->accum);
@@ -726,6 +742,7 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   set_image(p, ctx, lane.trace);
   p.counters = ctx->counters_on ? ctx->counters : nullptr;
   p.diag = ctx->diag_on ? ctx->counters + 3 : nullptr;
+  p.sky_units = ctx->counters + hrt::kSkyUnitsCounter;
   p.tile_cycles = ctx->diag_on ? ctx->tile_cycles : nullptr;
   p.pc = *pc;
   p.local_rows = ctx->local_rows;
@@ -857,8 +874,47 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
     if (builds_camera_lists(ran)) p.cam_lists_ready = 1u;  // the probe built them
     if (persistent_kernel(ran)) p.tl_lists_ready = 1u;     // (and the tile lists)
   }
+  // The sky lane (HRT_OPT_SKY_LANE): BUNDLE_WQ's sky items on trace_sky beside the main kernel, forked from
+  // `stream` inside launch_trace and joined back into it there -- so the event pair below spans fork to join
+  // and everything that follows on `stream` (folds, reads, the lane's done event) follows the join.  Auto: launches
+  // of at least kSkyLaneUnits work units (tile x frame) per resident wave.  Measured on island 1080p:
+  // 158 units per wave (the whole frame, 20 frames) 5% faster with the lane; 79 and fewer (10, 5, 2 frames, one
+  // frame, a half or an eighth of the rows at 20 or 64 frames) 4-12% slower -- short launches end on the
+  // traversal's longest pixel chains, which the capped kernel runs slower, with no sky work left to hide.
+  // In the gap: 103 units per wave 3% slower, 127 units 7% faster (island), cave 79 slower, 127 and 158 2% faster.
+  // Island 4K at 16 spp and 12 bounces is slower with the lane at 253 and 506 units per wave (2% and 9%), so the
+  // rule also asks for the sample count it was measured to win at; everything else keeps the path without the lane.
+  // Lane 0 (hrt_compute_n's) warms the side stream with its first BUNDLE_WQ launch, whatever its size.
+  constexpr uint64_t kSkyLaneUnits = 128;
+  hrt::SkyLane sky{};
+  const bool sky_ok = resolved == HRT_KERNEL_BUNDLE_WQ && !ctx->diag_on && !ctx->timeline;
+  constexpr int32_t kSkyLaneSamples = 64;
+  const bool big = (uint64_t)ctx->num_tiles() * ev.frames >= kSkyLaneUnits * p.num_cus * 16u &&
+                   p.pc.num_samples >= kSkyLaneSamples;
+  const bool run_sky = sky_ok && (ctx->sky_lane > 0 || (ctx->sky_lane < 0 && big));
+  const bool want_sky = run_sky || (sky_ok && ctx->sky_lane < 0 && l == 0 && !lane.sky_stream);
+  if (want_sky) {
+    hipError_t se = hipSuccess;
+    // The side stream has the lowest stream priority: the runtime keeps a pool of hardware queues per priority,
+    // so trace_sky never shares a queue with a trace lane's or the context's stream, whatever other streams the
+    // process has made (streams of one priority share up to four queues in turn: with the main kernel's stream
+    // on the same queue trace_sky would start after it had ended, find the plan empty, and leave the capped
+    // main kernel to run alone -- seen in a process's second context, with hrt_debug_sky_units at 0).
+    if (!lane.sky_stream) {
+      int least = 0, greatest = 0;
+      se = hipDeviceGetStreamPriorityRange(&least, &greatest);
+      if (se == hipSuccess) se = hipStreamCreateWithPriority(&lane.sky_stream, hipStreamNonBlocking, least);
+    }
+    if (se == hipSuccess && !lane.sky_fork) se = hipEventCreateWithFlags(&lane.sky_fork, hipEventDisableTiming);
+    if (se == hipSuccess && !lane.sky_join) se = hipEventCreateWithFlags(&lane.sky_join, hipEventDisableTiming);
+    if (se != hipSuccess) {
+      ctx->event_pool.push_back(ev);
+      return hip_fail(ctx, se, "sky lane stream / events");
+    }
+    sky = hrt::SkyLane{lane.sky_stream, lane.sky_fork, lane.sky_join, run_sky};
+  }
   HRT_HIP(ctx, hipEventRecord(ev.start, stream));
-  hipError_t e = hrt::launch_trace(p, variant, stream, &ctx->last_kernel, &ctx->last_block);
+  hipError_t e = hrt::launch_trace(p, variant, stream, &ctx->last_kernel, &ctx->last_block, want_sky ? &sky : nullptr);
   if (e == hipSuccess) ctx->last_frames = ev.frames;
   // the persistent kernels recorded this trace's tile costs: the lane's next trace can follow a plan
   lane.plan_valid = e == hipSuccess && persistent_kernel(ctx->last_kernel);
@@ -1802,6 +1858,10 @@ extern "C" hrt_status hrt_set_option(hrt_context* ctx, uint32_t key, int64_t val
     case HRT_OPT_WQ_NODE_RADIUS:
       if (value < 0 || value > 2) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "wq node radius must be 0 (auto), 1 or 2");
       ctx->wq_node_radius = (uint32_t)value;
+      return HRT_OK;
+    case HRT_OPT_SKY_LANE:
+      if (value < -1 || value > 1) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "sky lane must be -1 (auto), 0 or 1");
+      ctx->sky_lane = (int32_t)value;
       return HRT_OK;
     case HRT_OPT_DEFER_COMBINE: {
       if (value < 0 || value > 1) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "defer combine must be 0 or 1");

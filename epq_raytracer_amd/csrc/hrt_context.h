@@ -30,7 +30,8 @@
 
 namespace hrt {
 
-constexpr int kNumCounters = 3 + HRT_NUM_DIAG;  // segments, triangle tests, wave steps, diagnostics
+constexpr int kSkyUnitsCounter = 3 + HRT_NUM_DIAG;  // work units run by trace_sky (hrt_debug_sky_units)
+constexpr int kNumCounters = 4 + HRT_NUM_DIAG;  // segments, triangle tests, wave steps, diagnostics, sky units
 #ifndef HRT_LANES
 #define HRT_LANES 3
 #endif
@@ -90,6 +91,9 @@ struct Lane {
   hipEvent_t done = nullptr;      // recorded on `stream` after each trace / clear of the lane
   hipEvent_t free = nullptr;      // recorded on the context stream after the lane's last reader
   bool done_set = false, free_set = false;
+  // the lane's sky lane (HRT_OPT_SKY_LANE, hrt_kernels.h SkyLane): created by the first launch that uses it
+  hipStream_t sky_stream = nullptr;
+  hipEvent_t sky_fork = nullptr, sky_join = nullptr;
 };
 
 // Multi-GPU framebuffer gather (hrt_comm.cpp).
@@ -139,6 +143,7 @@ struct hrt_context {
   uint32_t num_cus = 0;
   uint32_t bvh_leaf = 0;  // HRT_OPT_BVH_LEAF_SIZE for the next hrt_set_scene (0 = auto, hrt_bvh.h)
   uint32_t wq_node_radius = 0;  // HRT_OPT_WQ_NODE_RADIUS (0 = auto)
+  int32_t sky_lane = -1;        // HRT_OPT_SKY_LANE (-1 = auto)
   uint32_t bvh_width = 4;  // HRT_OPT_BVH_WIDTH (hrt_bvh.h kWqDefaultWidth) for the next hrt_set_scene
   int64_t debug_fail_alloc = 0;   // debug build: fail the n-th device allocation of the next hrt_set_scene
   uint32_t debug_grab_runs = 0;   // debug build: HRT_DEBUG_OPT_GRAB_RUNS

@@ -34,9 +34,10 @@ struct TraceParams {
   float4* cam_tris;              // 4 float4 per record: (ao, num_t) (e1, index bits) (e2, -) (n, -)
   float4* cam_cull;              // 5 float4 per record: bundle-cull linear forms + margins
   uint32_t sec_batch;            // bounce segments run once this many lanes of a wave wait (1..64)
-  // Persistent (LDS) variants' scheduler: sched[0] work counter, [1] item count, [2] heavy tiles,
+  // Persistent (LDS) variants' scheduler: sched[1] item count, [2] heavy tiles,
   // [3] first heavy cost bucket, [5] cooperative-item counter, [6..7] u64 sum of tile costs,
-  // [8..) planner histogram / offsets / cursors (kSchedWords in all); tile_cost per 8x8 tile (shader clocks / 16, this trace);
+  // [8..) planner histogram / offsets / cursors, [1000] the plan's trailing sky items, [1002..1003] the u64
+  // work queue word (kSchedWords in all); tile_cost per 8x8 tile (shader clocks / 16, this trace);
   // item_buf (tiles x 8) the planned items; items = item_buf when this trace follows a plan.
   uint32_t* sched;
   uint32_t* tile_cost;
@@ -93,13 +94,27 @@ struct TraceParams {
   uint32_t* tl_cache;
   uint32_t tl_lists_ready;  // tl_cache already holds this camera's lists (hrt_api.cpp launch_frames): no tile_lists
   uint32_t split_factor4;   // (host side, launch_trace) the heavy threshold in quarters of a wave's share; 0: split_factor
+  unsigned long long* sky_units;  // the work units (tile x frame) trace_sky has run (hrt_debug_sky_units)
+  uint32_t sky_lane;        // (launch_trace) this launch's plan ends in its sky items and trace_sky runs beside the main kernel
+};
+// The sky lane of a trace lane (HRT_OPT_SKY_LANE): the side stream trace_sky runs on and the events a
+// launch forks to it and joins it back with.
+struct SkyLane {
+  hipStream_t stream;
+  hipEvent_t fork, join;
+  bool run;  // false: the stream's first use -- an empty trace_sky launch only, so that its queue and scratch
+             // exist before the first launch that forks to it (a one-time cost of tens of ms)
 };
 constexpr uint32_t kTlRecWords = 136;
 
 // Per device, once: the dynamic-LDS limits of the persistent kernels (hipFuncSetAttribute).
 hipError_t ensure_kernel_attributes(int device);
 // Launches the trace kernel(s); *ran / *block receive the resolved hrt_kernel and workgroup size.
-hipError_t launch_trace(const TraceParams& p, int variant, hipStream_t stream, int* ran, int* block);
+// sky: BUNDLE_WQ's product kernels run a planned launch's sky items on trace_sky beside the main kernel
+// (forked from `stream` after the planner kernels, joined back into it before launch_trace returns);
+// nullptr: every item runs on the main kernel.
+hipError_t launch_trace(const TraceParams& p, int variant, hipStream_t stream, int* ran, int* block,
+                        const SkyLane* sky = nullptr);
 int resolve_variant(const TraceParams& p, int variant);  // the kernel an HRT_KERNEL_* request runs
 // Ray centres (first + px * x) + py * y for every pixel of a width x height image (hrt_generate_rays).
 hipError_t launch_make_rays(float4* rays, uint32_t width, uint32_t height, const float first[3], const float px[3],

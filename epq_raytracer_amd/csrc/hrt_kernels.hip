@@ -2491,7 +2491,25 @@ __device__ __forceinline__ void stage_tris(const TraceParams& P, float4* dst, ui
 // culled chunks, primary list entries, iterations; the same with or without cooperation) in
 // BUNDLE_CULL_LDS, shader clocks / 16 in BUNDLE_BVH_LDS.
 constexpr uint32_t kItemTileMask = (1u << 22) - 1u;  // planned traces need fewer than 2^22 tiles
-template <int BLOCK, bool CoopOk, class Body>
+// The work queue: one u64 word, the front cursor (tile_loop) in its low half and the back cursor
+// (trace_sky) in its high half, both in work units (item x frame) -- the back cursor counted down from
+// the plan's end n; sched[kSchedSky] = the number of sky items the plan ends in (plan_scan; 0 without a
+// sky lane), S = that x nf units.  Crossing rule: every claim is one atomic add on the word, so the claims
+// are totally ordered and each returns both cursors as they stood.
+//  - A front claim of g that returns (f, b) owns the units [f, f + g) below n - min(b, S): the units
+//    from there up belong to back claims made already.
+//  - A back claim of r that returns (f, b) with b < S owns [max(n - min(b + r, S), f), n - b): the units
+//    under f went to earlier front claims, whose bound was at least n - b (they saw at most b units
+//    claimed), and every later front claim sees at least b + r and stops at n - min(b + r, S) or below.
+//    With b >= S, or f >= n - b (the cursors have crossed: every lower unit is under f too), it owns
+//    nothing and the wave ends.  Back claims past S only raise a count that front claims clamp to S, so
+//    trace_sky never takes a unit below the sky items.
+// So every unit has exactly one owner whichever side arrives first, and either side finishes the other's end.
+constexpr uint32_t kSchedSky = 1000, kSchedQueue = 1002;
+static_assert(kSchedQueue + 2 <= kSchedWords && kSchedQueue % 2 == 0, "sched buffer");
+// Sky: the kernel may run beside trace_sky and makes front claims as above; otherwise nothing ever raises
+// the word's high half and the loop counts on its low half alone.
+template <int BLOCK, bool CoopOk, bool Sky = false, class Body>
 __device__ __forceinline__ void tile_loop(const TraceParams& P, unsigned long long* ex, uint32_t* s_item, Body&& body) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t tiles_x = (P.pc.width + 7) / 8, tiles = tiles_x * ((P.local_rows + 7) / 8);
@@ -2567,21 +2585,35 @@ __device__ __forceinline__ void tile_loop(const TraceParams& P, unsigned long lo
     const uint32_t g = (kargs()->grab_always ||
                         ((uint64_t)cur + (uint64_t)HRT_GRAB_TAIL * resident < n && cur >= heavy_end)) ? kGrab : 1u;
     uint32_t t = 0;
+    [[maybe_unused]] unsigned long long qw = 0;
     const KArgs K = kargs();  // (per work item: not held across the item's fused loop)
     if (lane == 0) {
       // a tile's cost: its items' summed clocks; the heavy threshold's sum counts an item by its
       // share of the tile's lanes (its work), so splitting does not raise the threshold (with summed
       // clocks there too, borderline tiles flipped between split and whole: 7.4 / 8.4 ms frames)
       if (prev_tile != 0xFFFFFFFFu) atomicAdd(&K->tile_cost[prev_tile], prev_cost);
-      if (refill) t = first + atomicAdd(&K->sched[0], g);
+      if (refill) {
+        if constexpr (Sky)
+          qw = atomicAdd(reinterpret_cast<unsigned long long*>(K->sched + kSchedQueue), (unsigned long long)g);
+        else
+          t = first + atomicAdd(&K->sched[kSchedQueue], g);
+      }
     }
     if (prev_tile != 0xFFFFFFFFu) cost_sum += prev_cost >> prev_lk;
     if (refill) {
-      cur = __builtin_amdgcn_readfirstlane(t);
-      end = cur + g;
+      if constexpr (Sky) {
+        // the front claim (kSchedQueue): bounded by the items trace_sky has taken from the plan's far end
+        cur = first + __builtin_amdgcn_readfirstlane((uint32_t)qw);
+        const uint32_t back = __builtin_amdgcn_readfirstlane((uint32_t)(qw >> 32));
+        const uint32_t sky = K->sky_lane ? min(back, __builtin_amdgcn_readfirstlane(K->sched[kSchedSky]) * nf) : 0u;
+        end = min(cur + g, n - sky);
+      } else {
+        cur = __builtin_amdgcn_readfirstlane(t);
+        end = cur + g;
+      }
     }
     t = cur;
-    if (t >= n) break;
+    if (t >= (Sky ? end : n)) break;  // (Sky: end <= n)
     const uint32_t ti = t / nf, tf = t - ti * nf;
     const uint32_t* items = K->items;
     const uint32_t item = items ? __builtin_amdgcn_readfirstlane(items[ti]) : 0u;
@@ -2660,15 +2692,26 @@ __device__ __forceinline__ uint32_t cost_bucket(unsigned long long c) {
 }
 // sched words: [8, 8 + B) histogram, [8 + B, 8 + 2B) bucket offsets, [8 + 2B, 8 + 3B) cursors
 constexpr uint32_t kSchedHist = 8, kSchedOff = 8 + kPlanBuckets, kSchedCur = 8 + 2 * kPlanBuckets;
-static_assert(kSchedCur + kPlanBuckets <= kSchedWords, "sched buffer");
+static_assert(kSchedCur + kPlanBuckets <= kSchedSky, "sched buffer");
+// A tile's bucket.  With a sky lane (tl_cache: the launch's tile_lists records, a scene without spheres)
+// bucket 0 holds exactly the tiles whose whole-tile item is a sky item (trace_fused_split's rule: list
+// ok and empty), whatever they cost, and no other tile: the descending scan puts them at the plan's far
+// end, where trace_sky takes them, and sched[kSchedHist] is their number.
+__device__ __forceinline__ uint32_t plan_bucket(const uint32_t* cost, const uint32_t* tl_cache, uint32_t i) {
+  const uint32_t b = cost_bucket(cost[i]);
+  if (!tl_cache) return b;
+  const uint32_t* rec = tl_cache + (size_t)i * kTlRecWords;
+  return (rec[128] == 0u && rec[129] != 0u) ? 0u : max(b, 1u);
+}
 // Both passes count in LDS first: a frame's tiles crowd a few buckets, and per-tile global atomics
 // on those few words serialize (0.3 ms per pass at 1080p).
-__global__ __launch_bounds__(256) void plan_hist(uint32_t* sched, const uint32_t* cost, uint32_t tiles) {
+__global__ __launch_bounds__(256) void plan_hist(uint32_t* sched, const uint32_t* cost, uint32_t tiles,
+                                                 const uint32_t* tl_cache) {
   __shared__ uint32_t h[kPlanBuckets];
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (threadIdx.x < kPlanBuckets) h[threadIdx.x] = 0;
   __syncthreads();
-  if (i < tiles) atomicAdd(&h[cost_bucket(cost[i])], 1u);
+  if (i < tiles) atomicAdd(&h[plan_bucket(cost, tl_cache, i)], 1u);
   __syncthreads();
   if (threadIdx.x < kPlanBuckets && h[threadIdx.x]) atomicAdd(&sched[kSchedHist + threadIdx.x], h[threadIdx.x]);
 }
@@ -2679,7 +2722,7 @@ __device__ __forceinline__ uint32_t bucket_items(uint32_t b, uint32_t hb, uint32
 }
 // factor4: the heavy threshold in quarters of a resident wave's share of the launch's work
 __global__ __launch_bounds__(64) void plan_scan(uint32_t* sched, uint32_t waves, uint32_t factor4, uint32_t kmax,
-                                                uint32_t prio) {
+                                                uint32_t prio, uint32_t sky) {
   if (threadIdx.x != 0) return;
   const unsigned long long sum = *reinterpret_cast<const unsigned long long*>(sched + 6);
   const uint32_t hb = cost_bucket((unsigned long long)factor4 * sum / (4ull * (waves ? waves : 1u)));
@@ -2695,17 +2738,20 @@ __global__ __launch_bounds__(64) void plan_scan(uint32_t* sched, uint32_t waves,
   sched[2] = heavy;
   sched[4] = heavy_items;  // the plan's first heavy_items items are the heavy tiles' (tile_loop grabs them singly)
   sched[3] = hb;
+  // the plan's last items are bucket 0's: the sky tiles, whole and light (not with a heavy bucket 0,
+  // whose tiles would be split)
+  sched[kSchedSky] = (sky && hb > 0 && prio <= 1) ? sched[kSchedHist] : 0u;
 }
 
 // Item word: tile | log2(items of the tile) << 22 | item index s << 25 | heavy << 31 (tile_loop).
 __global__ __launch_bounds__(256) void plan_fill(uint32_t* sched, const uint32_t* cost, uint32_t tiles, uint32_t kmax,
-                                                 uint32_t prio, uint32_t* items) {
+                                                 uint32_t prio, uint32_t* items, const uint32_t* tl_cache) {
   __shared__ uint32_t cnt[kPlanBuckets], base[kPlanBuckets];
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (threadIdx.x < kPlanBuckets) cnt[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t hb = sched[3];
-  const uint32_t b = i < tiles ? cost_bucket(cost[i]) : 0u;
+  const uint32_t b = i < tiles ? plan_bucket(cost, tl_cache, i) : 0u;
   const bool heavy = b >= hb;
   const uint32_t k = bucket_items(b, hb, kmax);
   const uint32_t local = i < tiles ? atomicAdd(&cnt[b], k) : 0u;
@@ -2747,7 +2793,7 @@ __global__ __launch_bounds__(BLOCK) void trace_bundle_cull_lds(TraceParams P) {
 // 1024-thread workgroups).  Dynamic LDS: [nodes x 48 B][16 x (64 slots x 8 B, wq_ncap + wq_tcap words)].
 // (one body, two kernels: a __device__ wrapper taking P by reference changes the island kernel's
 // register allocation and cost 0.6%)
-#define HRT_WQ_KERNEL_BODY(BOUNCE)                                                                              \
+#define HRT_WQ_KERNEL_BODY(BOUNCE, D, SKY)                                                                         \
   {                                                                                                             \
     const uint32_t nn = P.bvh_wq_n_nodes;                                                                       \
     float4* nodes = lds_tris;                                                                                   \
@@ -2758,16 +2804,139 @@ __global__ __launch_bounds__(BLOCK) void trace_bundle_cull_lds(TraceParams P) {
                    reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap};                            \
     __syncthreads();                                                                                            \
     const float4* T = reinterpret_cast<const float4*>(P.tris);                                                  \
-    tile_loop<1024, false>(P, nullptr, nullptr, [&](uint32_t x, uint32_t lr, Coop& co, uint32_t f, uint32_t nr) { \
+    tile_loop<1024, false, SKY>(P, nullptr, nullptr, [&](uint32_t x, uint32_t lr, Coop& co, uint32_t f, uint32_t nr) { \
       trace_fused_split<BOUNCE, D>(P, x, lr, CullGlobal{T, to_const(T)}, wq, nullptr, co, f, nr);               \
     });                                                                                                         \
   }
+// HRT_WQ_VGPR_CAP: the two kernels' VGPR budget.  Four of their waves per SIMD at 128 VGPRs fill the
+// 512-entry file; at 120 they leave 32 registers per lane for a wave of trace_sky beside them.  The cap
+// alone costs the traversal 5.7% on island and 1.7% on cave (36 spilled VGPRs against 14); with trace_sky
+// beside it the frame is 5.4% / 2.8% shorter than uncapped (112 + a 64-register trace_sky: the same on
+// island, the cap dearer on cave; 104: slower; DESIGN §18, profiles/sky_lane_step0.jsonl).
+// (amdgpu_num_vgpr counts in halves on gfx950: the compiler doubles it for the unified VGPR / AGPR file and
+// ignores a value whose double exceeds the launch bounds' 128.)
+#ifndef HRT_WQ_VGPR_CAP
+#define HRT_WQ_VGPR_CAP 120  // 0: the launch bounds' 128 (no room for trace_sky: HRT_OPT_SKY_LANE then only delays it)
+#endif
+// Only the <false> instantiations run beside trace_sky: the diagnostics / probe kernels keep the whole
+// budget and the plain work counter (explicit specialisations: the attribute takes no template argument).
+#if HRT_WQ_VGPR_CAP
+#define HRT_WQ_VGPRS __attribute__((amdgpu_num_vgpr(HRT_WQ_VGPR_CAP / 2)))
+#else
+#define HRT_WQ_VGPRS
+#endif
 template <bool D>
-__global__ __launch_bounds__(1024) void trace_bundle_wq(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq)
+__global__ void trace_bundle_wq(TraceParams P);
+template <>
+__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, true)
+template <>
+__global__ __launch_bounds__(1024) void trace_bundle_wq<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, true, false)
 // the same with per-member R in the node margins (TraceParams::bvh_node_r, HRT_OPT_WQ_NODE_RADIUS)
 template <bool D>
-__global__ __launch_bounds__(1024) void trace_bundle_wq_nr(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR)
+__global__ void trace_bundle_wq_nr(TraceParams P);
+template <>
+__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq_nr<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, true)
+template <>
+__global__ __launch_bounds__(1024) void trace_bundle_wq_nr<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, true, false)
+// The two kernels for product launches without a sky lane (unplanned launches, HRT_OPT_SKY_LANE off: the
+// per-frame loop by default): the whole register budget and the plain work counter -- the cap costs 5.7%
+// where no trace_sky wave uses the registers it frees.
+__global__ __launch_bounds__(1024) void trace_bundle_wq_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, false)
+__global__ __launch_bounds__(1024) void trace_bundle_wq_nr_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, false)
 #undef HRT_WQ_KERNEL_BODY
+
+// The sky lane (HRT_OPT_SKY_LANE): the plan's sky items on a lean kernel of their own, resident beside
+// the BUNDLE_WQ workgroups -- one more wave per SIMD, which the main kernel's register budget leaves room
+// for (HRT_WQ_VGPR_CAP) and which uses no LDS.  The sky loop is pure VALU work; the traversal's waves
+// leave issue slots empty while they wait on LDS and L2, and a sky wave in a slot of the main kernel would
+// take a traversal wave's place instead.  Each wave takes whole items (a sky tile's remaining frames of
+// the launch) from the plan's far end (kSchedQueue) and runs them exactly as trace_fused_split's sky
+// branch does: the same sky_samples, seeds, stores, counters and tile costs.  The items are whole-tile,
+// light and sky by construction (plan_bucket, plan_scan), so their tile_lists record has an empty list
+// and only its octant sums and aabb_ok are read.
+#ifndef HRT_SKY_VGPR_CAP
+#define HRT_SKY_VGPR_CAP 32
+#endif
+// Units per back claim: whole items (a tile's 20 frames in one claim) left trace_sky running 0.3 ms after
+// the main kernel of a 20-frame launch had ended, and made a rank of 8 slower than without the lane.
+#ifndef HRT_SKY_GRAB
+#define HRT_SKY_GRAB 4u
+#endif
+constexpr uint32_t kSkyGrab = HRT_SKY_GRAB;
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(HRT_SKY_VGPR_CAP / 2))) void trace_sky(TraceParams P) {
+  if (!P.sky_lane) return;  // (the side stream's warm-up launch, SkyLane::run)
+  const uint32_t lane = threadIdx.x & 63;
+  const hrt_push_constants& pc = P.pc;
+  const uint32_t tiles_x = (pc.width + 7) / 8;
+  const uint32_t nf = P.n_frames > 1 ? P.n_frames : 1u;
+  // (sky units <= n: bucket 0's tiles, one item each)
+  const uint32_t n = P.sched[1] * nf, sky_units = P.sched[kSchedSky] * nf;
+  unsigned long long acc_s = 0, acc_t = 0, acc_m = 0, cost_sum = 0;
+  uint32_t ran = 0;  // units this wave has run (TraceParams::sky_units)
+  __builtin_amdgcn_s_setprio(0);
+  uint32_t u = 0, hi = 0;  // the claimed units not yet run: [u, hi)
+  for (;;) {
+    if (u >= hi) {  // the back claim (kSchedQueue)
+      unsigned long long qw = 0;
+      if (lane == 0)
+        qw = atomicAdd(reinterpret_cast<unsigned long long*>(P.sched + kSchedQueue), (unsigned long long)kSkyGrab << 32);
+      const uint32_t front = __builtin_amdgcn_readfirstlane((uint32_t)qw);
+      const uint32_t back = __builtin_amdgcn_readfirstlane((uint32_t)(qw >> 32));
+      if (back >= sky_units) break;
+      hi = n - back;
+      u = max(n - min(back + kSkyGrab, sky_units), front);
+      if (u >= hi) break;  // the cursors have crossed
+    }
+    // a frame run: the claimed units of one item (a claim may end one item and begin the next)
+    const uint32_t item = u / nf, frame = u - item * nf, nrun = min(hi - u, nf - frame);
+    u += nrun;
+    ran += nrun;
+    const uint32_t tile = __builtin_amdgcn_readfirstlane(P.items[item]) & kItemTileMask;
+    const uint64_t t0 = __builtin_readcyclecounter();
+    const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const uint32_t x = tx * 8 + (lane & 7u), lr = ty * 8 + (lane >> 3);
+    const uint32_t y = global_row(lr, P);
+    const bool active = x < pc.width && lr < P.local_rows && y < pc.height;
+    const uint32_t id = active ? x + y * pc.width : 0u;
+    f3 centre = mk(0.0f, 0.0f, 0.0f);
+    if (active) {
+      const float4 rc = P.rays[id];
+      centre = mk(rc.x, rc.y, rc.z);
+    }
+    const uint32_t* rec = P.tl_cache + (size_t)tile * kTlRecWords;
+    TileList tl;
+    tl.v = 0;
+    tl.lds = nullptr;
+    tl.n = 0;
+    tl.ok = true;
+    tl.aabb = 0;
+    tl.tsum = rec[64 + lane];
+    tl.aabb_ok = __builtin_amdgcn_readfirstlane(rec[132]) != 0u;
+    uint32_t segs = 0, tests = 0;
+    f3 colour = mk(0.0f, 0.0f, 0.0f);
+    uint32_t state = (pc.rng_offset + frame) * 719393u + id;
+    for (uint32_t fr = 0;; ++fr) {
+      sky_samples(tl, active, centre, state, colour, segs, tests);
+      if (active) store_pixel(P, x, lr, div3(colour, (float)pc.num_samples), frame + fr);
+      if (fr + 1u >= nrun) break;
+      colour = mk(0.0f, 0.0f, 0.0f);
+      state = (pc.rng_offset + frame + fr + 1u) * 719393u + id;
+    }
+    unsigned long long s, t;
+    uint32_t mx;
+    wave_counters(segs, tests, s, t, mx);
+    acc_s += s;
+    acc_t += t;
+    acc_m += mx;
+    const uint64_t c = (__builtin_readcyclecounter() - t0) >> 4;  // the item's cost, as tile_loop records it
+    const uint32_t cost = __builtin_amdgcn_readfirstlane(c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c);
+    if (lane == 0) atomicAdd(&P.tile_cost[tile], cost);
+    cost_sum += cost;
+  }
+  if (lane == 0 && cost_sum) atomicAdd(reinterpret_cast<unsigned long long*>(P.sched + 6), cost_sum);
+  if (lane == 0 && ran && P.sky_units) atomicAdd(P.sky_units, (unsigned long long)ran);
+  add_counters(P, acc_s, acc_t, acc_m);
+}
 
 // BUNDLE_BVH with the hierarchy and the triangle image in LDS (persistent 1024-thread workgroups).
 // Dynamic LDS: [n_tris x 48 B triangles][nodes x 64 B][prims x 4 B entries][meshes x 4 B key bases].
@@ -3134,27 +3303,32 @@ static uint32_t tiles_of(const TraceParams& p) { return ((p.pc.width + 7) / 8) *
 // Persistent kernels: plan this trace from the last one's tile costs (when p.plan_valid and
 // splitting is on), then reset the counters the trace fills.  q.items = nullptr: plain tile order.
 static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
+  // (q.sky_lane: requested by launch_trace; kept only for a planned launch whose work indices and item
+  // count leave the queue word's halves apart)
+  const uint32_t nfr = q.n_frames > 1 ? q.n_frames : 1u;
   const uint32_t tiles = ((q.pc.width + 7) / 8) * ((q.local_rows + 7) / 8);
   // longest-first order whenever last trace's costs are known (and tile indices fit the item word)
   const bool plan = q.plan_valid && tiles > 0 && tiles <= kItemTileMask;
   q.items = plan ? q.item_buf : nullptr;
+  if (!plan || (uint64_t)tiles * 8u * nfr >= (1ull << 31)) q.sky_lane = 0;
+  const uint32_t* sky_cache = q.sky_lane ? q.tl_cache : nullptr;
   hipError_t e;
   if (plan) {
     if ((e = hipMemsetAsync(q.sched + kSchedHist, 0, 3 * kPlanBuckets * 4, stream)) != hipSuccess) return e;  // histogram, cursors
-    plan_hist<<<(tiles + 255) / 256, 256, 0, stream>>>(q.sched, q.tile_cost, tiles);
+    plan_hist<<<(tiles + 255) / 256, 256, 0, stream>>>(q.sched, q.tile_cost, tiles, sky_cache);
     // factor auto (-1): 3 when a resident wave gets more than 4 tiles, else 1 (profiles/r01k_schedule_sweep)
     // a launch of nf frames: a resident wave's fair share is nf frames' work, i.e. waves / nf per frame
     const uint32_t nf = q.n_frames > 1 ? q.n_frames : 1u;
     const uint32_t waves = std::max(1u, q.num_cus * 16u / nf);
     const uint32_t factor4 =
         q.split_factor4 ? q.split_factor4 : 4u * (q.split_factor >= 0 ? (uint32_t)q.split_factor : tiles > 4 * waves ? 3u : 1u);
-    plan_scan<<<1, 64, 0, stream>>>(q.sched, waves, factor4, q.split_k, q.split_prio);
+    plan_scan<<<1, 64, 0, stream>>>(q.sched, waves, factor4, q.split_k, q.split_prio, q.sky_lane);
     plan_fill<<<(tiles + 255) / 256, 256, 0, stream>>>(q.sched, q.tile_cost, tiles, q.split_k, q.split_prio,
-                                                       q.item_buf);
+                                                       q.item_buf, sky_cache);
   }
   if ((e = hipMemsetAsync(q.tile_cost, 0, (size_t)tiles * 4, stream)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(q.sched + 5, 0, 12, stream)) != hipSuccess) return e;  // coop counter, cost sum
-  return hipMemsetAsync(q.sched, 0, 4, stream);
+  return hipMemsetAsync(q.sched + kSchedQueue, 0, 8, stream);  // the work queue word
 }
 
 // The persistent kernels' dynamic-LDS limits, set once per device (hrt_create calls this for its device;
@@ -3175,7 +3349,9 @@ hipError_t ensure_kernel_attributes(int device) {
                             reinterpret_cast<const void*>(&trace_bundle_wq<false>),
                             reinterpret_cast<const void*>(&trace_bundle_wq<true>),
                             reinterpret_cast<const void*>(&trace_bundle_wq_nr<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_nr<true>)};
+                            reinterpret_cast<const void*>(&trace_bundle_wq_nr<true>),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_solo),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_nr_solo)};
   hipError_t e;
   for (const void* f : brute)
     if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsScene)) != hipSuccess)
@@ -3192,7 +3368,11 @@ hipError_t ensure_kernel_attributes(int device) {
   return hipSuccess;
 }
 
-hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, int* ran, int* block_out) {
+#ifndef HRT_SKY_GRID
+#define HRT_SKY_GRID 1u  // trace_sky workgroups per CU
+#endif
+hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, int* ran, int* block_out,
+                        const SkyLane* sky) {
   TraceParams p = p0;
   variant = resolve_variant(p, variant);
   *ran = variant;
@@ -3249,16 +3429,40 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
       const size_t lds = wq_lds_bytes(p, &q.wq_ncap, &q.wq_tcap);
       if (p.wq_ncap) q.wq_ncap = std::min(q.wq_ncap, std::max(128u, p.wq_ncap & ~63u));  // HRT_OPT_WQ_NODE_CAP
       if (p.wq_tcap) q.wq_tcap = std::min(q.wq_tcap, std::max(128u, p.wq_tcap & ~63u));  // HRT_DEBUG_OPT_WQ_TRI_CAP
+      // The sky lane: product kernels only (diagnostics, probes and timeline builds keep every item on the
+      // main kernel), a scene without spheres (trace_fused_split's sky rule) and a planned launch
+      // (prepare_schedule).  The side stream waits for the planner kernels; the main stream waits for
+      // trace_sky before anything that follows this launch.
+      q.sky_lane = sky && sky->run && !HRT_TIMELINE && HRT_TL_PREPASS && HRT_SKY_LOOP && !(p.diag || p.probe) && p.tl_cache &&
+                           p.pc.num_spheres == 0
+                       ? 1u
+                       : 0u;
       if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
+      if (q.sky_lane) {
+        if (hipError_t e = hipEventRecord(sky->fork, stream); e != hipSuccess) return e;
+        if (hipError_t e = hipStreamWaitEvent(sky->stream, sky->fork, 0); e != hipSuccess) return e;
+      }
       if (p.bvh_node_r) {
         if (p.diag || p.probe)
           trace_bundle_wq_nr<true><<<p.num_cus, 1024, lds, stream>>>(q);
-        else
+        else if (q.sky_lane)
           trace_bundle_wq_nr<false><<<p.num_cus, 1024, lds, stream>>>(q);
+        else
+          trace_bundle_wq_nr_solo<<<p.num_cus, 1024, lds, stream>>>(q);
       } else if (p.diag || p.probe) {
         trace_bundle_wq<true><<<p.num_cus, 1024, lds, stream>>>(q);
-      } else {
+      } else if (q.sky_lane) {
         trace_bundle_wq<false><<<p.num_cus, 1024, lds, stream>>>(q);
+      } else {
+        trace_bundle_wq_solo<<<p.num_cus, 1024, lds, stream>>>(q);
+      }
+      if (q.sky_lane) {
+        // (after the main kernel's launch: its workgroups take their CUs first, one sky workgroup fits beside each)
+        trace_sky<<<p.num_cus * HRT_SKY_GRID, 256, 0, sky->stream>>>(q);
+        if (hipError_t e = hipEventRecord(sky->join, sky->stream); e != hipSuccess) return e;
+        if (hipError_t e = hipStreamWaitEvent(stream, sky->join, 0); e != hipSuccess) return e;
+      } else if (sky && !sky->run) {
+        trace_sky<<<1, 256, 0, sky->stream>>>(q);  // (returns at once: q.sky_lane == 0; nothing to order)
       }
       *block_out = 1024;
       break;

@@ -41,7 +41,8 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): fold records -- hrt_fold_record, hrt_settle_rule,
+/* 6, additive (no bump: nothing existing changed): HRT_OPT_SKY_LANE, hrt_debug_sky_units.
+ * 6, additive (no bump: nothing existing changed): fold records -- hrt_fold_record, hrt_settle_rule,
  * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
  * 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
  * hrt_present_info, hrt_present, hrt_accumulate_present, hrt_present_done, hrt_present_wait.
@@ -362,6 +363,17 @@ typedef enum hrt_option {
    * hrt_stats are byte for byte the same either way.  On an hrt_comm_init_all group each member records
    * its own rows when its own option is set; there is no collective. */
   HRT_OPT_FOLD_RECORDS = 19,
+  /* BUNDLE_WQ: the sky lane.  1 = a planned launch's sky items (whole tiles whose primary list is empty, in
+   * a scene without spheres) run on a lean kernel of their own (trace_sky), resident beside the main
+   * kernel's workgroups as one more wave per SIMD and fed from the far end of the same work queue; 0 = every
+   * item on the main kernel; default -1 = auto: on where it was measured faster -- launches of at least 128
+   * work units (tile x frame) per resident wave at 64 or more samples per pixel: hrt_compute_n /
+   * hrt_compute_until launches of a whole 1080p frame from 17 frames up (island and cave) -- and off
+   * everywhere else, where it was measured slower (shorter launches, the per-frame loop, row-tile parts of
+   * 2 and 8, island 4K at 16 spp) or not measured at all (other sample counts and sizes): off is the
+   * code path without the lane, so auto never costs more than 0.  Diagnostics (HRT_OPT_COUNTERS = 2), probes and
+   * timeline builds always keep every item on the main kernel.  Results do not depend on it. */
+  HRT_OPT_SKY_LANE = 20,
   /* libhip_raytrace_debug.so only (tests): the value-th device allocation of the next hrt_set_scene
    * fails with HRT_ERR_OUT_OF_MEMORY (0 = off) */
   HRT_DEBUG_OPT_FAIL_ALLOC = 1001,
@@ -670,6 +682,9 @@ hrt_status hrt_debug_band_records(hrt_context* ctx, uint32_t* rec, uint64_t rec_
 /* Tuning support: trace lane 0's per-8x8-tile costs as the last persistent launch on it recorded them
  * (shader clocks / 16 summed over the launch's frames; the next launch's plan input), count <= tiles. */
 hrt_status hrt_debug_tile_costs(hrt_context* ctx, uint32_t* out, uint32_t count);
+/* Test support: the work units (tile x frame) that trace_sky, the sky lane's kernel (HRT_OPT_SKY_LANE), has run on
+ * this context since creation or hrt_reset_stats.  Blocking. */
+hrt_status hrt_debug_sky_units(hrt_context* ctx, uint64_t* out);
 /* HRT_TIMELINE builds: the last trace launch's item records (4 words each: start, tile list built, end,
  * item | frame << 32 | run << 40 | sky << 47 | wave << 48), at most cap of them copied; *count = the records the launch wrote (<= the
  * HRT_DEBUG_OPT_TIMELINE capacity).  Other builds: HRT_ERR_INVALID_ARGUMENT. */

@@ -32,6 +32,7 @@ def main():
     ap.add_argument("--leaf", type=int, default=0, help="> 0: BVH leaf size (HRT_OPT_BVH_LEAF_SIZE)")
     ap.add_argument("--width", type=int, default=0, help="> 0: BUNDLE_WQ group width (HRT_OPT_BVH_WIDTH)")
     ap.add_argument("--node-r", type=int, default=0, help="HRT_OPT_WQ_NODE_RADIUS (0 auto, 1 scene-wide R, 2 per node)")
+    ap.add_argument("--sky-lane", type=int, default=-1, help="HRT_OPT_SKY_LANE (-1 auto, 0 off, 1 on)")
     ap.add_argument("--batch", type=int, default=0,
                     help="> 0: each measurement is hrt_compute_n of this many frames (ms = per frame, wall incl. accumulates)")
     a = ap.parse_args()
@@ -45,6 +46,8 @@ def main():
                                 **({_lib.OPT_BVH_LEAF_SIZE: a.leaf} if a.leaf > 0 else {}),
                                 **({_lib.OPT_BVH_WIDTH: a.width} if a.width > 0 else {})},
                        debug=a.prio == 2)  # heavy tiles only: a libhip_raytrace_debug.so diagnostics mode
+    if hasattr(_lib, "OPT_SKY_LANE") and a.sky_lane != -1:
+        ctx.set_option(_lib.OPT_SKY_LANE, a.sky_lane)
     pc = case.push(1)
     ms = []
     if a.batch > 0:

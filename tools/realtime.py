@@ -32,11 +32,14 @@ def main():
                     help="traces only (the combine's cost and its waits left out: a lower bound)")
     ap.add_argument("--grid-cus", type=int, nargs="+", default=[0],
                     help="HRT_OPT_GRID_CUS values (libhip_raytrace_debug.so; 0 = every CU)")
+    ap.add_argument("--sky-lane", type=int, default=-1, help="HRT_OPT_SKY_LANE (-1 auto, 0 off, 1 on)")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.split("x"))
     case = SceneCase(a.scene, (W, H), a.spp, a.bounces)
     debug = a.grid_cus != [0]
     ctx = case.context(debug=debug)
+    if a.sky_lane != -1:
+        ctx.set_option(_lib.OPT_SKY_LANE, a.sky_lane)
     k = 1
     for r in range(a.rounds):
         for lanes, cus, bs, df, sp, fc in [(n, c, b, d, sp, fc) for n in a.lanes for c in a.grid_cus
