@@ -100,6 +100,7 @@ RGBA8_FREEZE_FRAME = 510     # HRT_RGBA8_FREEZE_FRAME
 RULE_ANY = 0xFFFFFFFF        # a settle-rule bound that is disabled
 
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
+TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
 STATUS_NAMES = {0: "HRT_OK", 1: "HRT_ERR_INVALID_ARGUMENT", 2: "HRT_ERR_NO_DEVICE", 3: "HRT_ERR_OUT_OF_MEMORY",
                 4: "HRT_ERR_NO_SCENE", 5: "HRT_ERR_HIP", 6: "HRT_ERR_IO", 7: "HRT_ERR_COMM"}
@@ -167,6 +168,7 @@ EXPORTED_SYMBOLS = (
     "hrt_import_external_memory", "hrt_release_external_memory",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
+    "hrt_debug_tile_lists",
     "hrt_stream", "hrt_release_caches", "hrt_last_error", "hrt_comm_unique_id", "hrt_comm_init", "hrt_comm_init_all", "hrt_comm_info",
     "hrt_host_create_rays", "hrt_host_ray_grid", "hrt_host_view_matrix", "hrt_host_transform_meshes",
     "hrt_debug_bvh_build", "hrt_debug_bvh_wq_nodes",
@@ -248,6 +250,7 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_debug_band_records": (c_int32, [c_void_p, P, c_uint64, P, c_uint64, P, c_uint64, P]),
         "hrt_debug_tile_costs": (c_int32, [c_void_p, P, c_uint32]),
         "hrt_debug_sky_units": (c_int32, [c_void_p, P]),
+        "hrt_debug_tile_lists": (c_int32, [c_void_p, POINTER(PushConstants), c_uint32, P, c_uint64, P]),
         "hrt_debug_bvh_build": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P, c_uint64, P, c_uint64, P,
                                           c_uint64, P, c_uint64, P, c_uint64]),
         "hrt_debug_bvh_wq_nodes": (c_int64, [P, c_uint32, P, c_uint32, c_uint32, c_uint32, P, c_uint64]),

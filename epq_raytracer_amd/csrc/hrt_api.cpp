@@ -1959,6 +1959,52 @@ extern "C" hrt_status hrt_debug_timeline(hrt_context* ctx, uint64_t* out, uint32
   return HRT_OK;
 }
 
+// Test support: the tile_lists kernel's records for a dispatch of pc, built into a buffer of the call's own
+// (the lanes' tl_cache records stay what the last launch made them) from lane 0's camera lists, which the
+// call rebuilds for pc's camera -- so lane 0's next trace rebuilds both.  Per tile: n, ok, then the listed
+// triangles' indices into the uploaded buffer (cam_tris[..][1].w of each entry's record).
+extern "C" hrt_status hrt_debug_tile_lists(hrt_context* ctx, const hrt_push_constants* pc, uint32_t refine,
+                                           uint32_t* out, uint64_t words, uint32_t info[2]) {
+  if (!ctx || !pc || !info) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if ((st = check_dispatch(ctx, pc, "hrt_debug_tile_lists")) != HRT_OK) return st;
+  constexpr uint32_t kWords = 66;
+  const uint32_t tiles = (uint32_t)ctx->num_tiles();
+  info[0] = tiles;
+  info[1] = (ctx->width + 7) / 8;
+  if (!out || words < (uint64_t)tiles * kWords) return HRT_OK;
+  if ((st = hrt_synchronize(ctx)) != HRT_OK) return st;
+  hrt::TraceParams p = make_params(ctx, pc, 0);
+  uint32_t* recs = nullptr;
+  HRT_HIP(ctx, hipMalloc((void**)&recs, (size_t)tiles * hrt::kTlRecWords * 4));
+  p.tl_cache = recs;
+  ctx->lane[0].cam_ready = ctx->lane[0].tl_ready = false;
+  hipError_t e = hrt::launch_tile_lists(p, refine, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  std::vector<uint32_t> host((size_t)tiles * hrt::kTlRecWords);
+  const size_t cap = ctx->scene.cam_capacity;
+  std::vector<float> cam(cap * 16);
+  if (e == hipSuccess) e = hipMemcpy(host.data(), recs, host.size() * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && cap) e = hipMemcpy(cam.data(), ctx->scene.cam_tris[0], cam.size() * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(recs);
+  if (e != hipSuccess) return hip_fail(ctx, e, "hrt_debug_tile_lists");
+  for (uint32_t t = 0; t < tiles; ++t) {
+    const uint32_t* rec = &host[(size_t)t * hrt::kTlRecWords];
+    uint32_t* o = out + (size_t)t * kWords;
+    const uint32_t n = std::min(rec[128], 64u);
+    o[0] = n;
+    o[1] = rec[129];
+    for (uint32_t i = 0; i < 64; ++i) {
+      const size_t k = rec[i] & 0x07FFFFFFu;
+      uint32_t idx = 0xFFFFFFFFu;
+      if (i < n && k < cap) std::memcpy(&idx, &cam[k * 16 + 7], 4);
+      o[2 + i] = idx;
+    }
+  }
+  return HRT_OK;
+}
+
 // Work the caller enqueues on the stream follows every accumulate so far: the deferred ones are folded.
 extern "C" void* hrt_stream(hrt_context* ctx) {
   if (!ctx || bind(ctx) != HRT_OK || hrt::flush_combines(ctx) != HRT_OK) return ctx ? (void*)ctx->stream : nullptr;

@@ -116,6 +116,9 @@ hipError_t ensure_kernel_attributes(int device);
 hipError_t launch_trace(const TraceParams& p, int variant, hipStream_t stream, int* ran, int* block,
                         const SkyLane* sky = nullptr);
 int resolve_variant(const TraceParams& p, int variant);  // the kernel an HRT_KERNEL_* request runs
+// hrt_debug_tile_lists: camera_lists, then tile_lists into p.tl_cache (tiles x kTlRecWords); refine 0: the
+// cap rule alone, else the product's lists (cap, then corner directions per tile and per pixel).
+hipError_t launch_tile_lists(const TraceParams& p, uint32_t refine, hipStream_t stream);
 // Ray centres (first + px * x) + py * y for every pixel of a width x height image (hrt_generate_rays).
 hipError_t launch_make_rays(float4* rays, uint32_t width, uint32_t height, const float first[3], const float px[3],
                             const float py[3], hipStream_t stream);

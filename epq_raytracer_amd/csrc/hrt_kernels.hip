@@ -885,23 +885,31 @@ __device__ __forceinline__ void aabb_truth_table(const TraceParams& P, TileList&
   t.tsum = len;
 }
 
-__device__ __forceinline__ Bundle tile_bundle(const hrt_push_constants& pc, bool active, f3 centre, bool& ok) {
+// normalize(M * v): a primary direction's arithmetic up to rounding (get_ray_dir forms the same sums with FMAs)
+__device__ __forceinline__ f3 box_dir(const hrt_push_constants& pc, f3 v) {
+  const float* M = pc.cam_alignment_mat;
+  return normalize(mk(M[0] * v.x + M[4] * v.y + M[8] * v.z, M[1] * v.x + M[5] * v.y + M[9] * v.z,
+                      M[2] * v.x + M[6] * v.y + M[10] * v.z));
+}
+__device__ __forceinline__ float jitter_reach(const hrt_push_constants& pc) { return fabsf(pc.jitter_size) * 1.0001f; }
+
+// cdir: lane l < 8 holds the unit direction of corner l of X (bit 0: x, bit 1: y, bit 2: z; hi when set);
+// flat: X has no extent in x (lo.x == hi.x), so corners l and l ^ 1 are the same direction.
+__device__ __forceinline__ Bundle tile_bundle(const hrt_push_constants& pc, bool active, f3 centre, bool& ok, f3& cdir,
+                                              bool& flat) {
   const float inf = __builtin_inff();
   const f3 lo = mk(wave_min_all(active ? centre.x : inf), wave_min_all(active ? centre.y : inf),
                    wave_min_all(active ? centre.z : inf));
   const f3 hi = mk(wave_max_all(active ? centre.x : -inf), wave_max_all(active ? centre.y : -inf),
                    wave_max_all(active ? centre.z : -inf));
-  const float j = fabsf(pc.jitter_size) * 1.0001f;
-  const float* M = pc.cam_alignment_mat;
-  auto dir = [&](f3 v) {
-    return normalize(mk(M[0] * v.x + M[4] * v.y + M[8] * v.z, M[1] * v.x + M[5] * v.y + M[9] * v.z,
-                        M[2] * v.x + M[6] * v.y + M[10] * v.z));
-  };
+  const float j = jitter_reach(pc);
   Bundle b;
-  b.a = dir(mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z));
+  b.a = box_dir(pc, mk(0.5f * lo.x + 0.5f * hi.x, 0.5f * lo.y + 0.5f * hi.y, 0.5f * lo.z + 0.5f * hi.z));
   const uint32_t lane = threadIdx.x & 63;
   const f3 corner = mk((lane & 1) ? hi.x : lo.x, (lane & 2) ? hi.y + j : lo.y - j, (lane & 4) ? hi.z + j : lo.z - j);
-  const float lam = lane < 8 ? dot(dir(corner), b.a) : 3.0f;
+  cdir = box_dir(pc, corner);
+  flat = lo.x == hi.x;
+  const float lam = lane < 8 ? dot(cdir, b.a) : 3.0f;
   b.c_lo = wave_min_all(lam) - 1e-5f;
   b.c_hi = 1.00001f;
   b.s_hi = __builtin_sqrtf(fmaxf(0.0f, 1.00002f - b.c_lo * b.c_lo)) * 1.00001f + 1e-6f;
@@ -910,9 +918,9 @@ __device__ __forceinline__ Bundle tile_bundle(const hrt_push_constants& pc, bool
   return b;
 }
 
-// Bundle rules R3-R5 of camera-list records [base, base + 64) against b (lane j: record base + j).
-__device__ __forceinline__ bool bundle_keep(const float4* __restrict__ cr, uint32_t k, const Bundle& b) {
-  const float4 C0 = cr[5 * k], C1 = cr[5 * k + 1], C2 = cr[5 * k + 2], C3 = cr[5 * k + 3], C4 = cr[5 * k + 4];
+// Bundle rules R1, R3-R5 of a cam_cull record (C0..C4) against the cap b.
+__device__ __forceinline__ bool bundle_keep(const float4& C0, const float4& C1, const float4& C2, const float4& C3,
+                                            const float4& C4, const Bundle& b) {
   const float na = dot(mk(C0.x, C0.y, C0.z), b.a), ua = dot(mk(C1.x, C1.y, C1.z), b.a);
   const float va = dot(mk(C2.x, C2.y, C2.z), b.a), wa = dot(mk(C3.x, C3.y, C3.z), b.a);
   const bool rej = (lin_lower(na, C4.x, b) > C0.w) | (lin_upper(ua, C4.y, b) < -C1.w) |
@@ -920,14 +928,101 @@ __device__ __forceinline__ bool bundle_keep(const float4* __restrict__ cr, uint3
   return !rej;
 }
 
-// Builds the wave's list (all 64 lanes active; the caller synchronises before reading it).
-__device__ __forceinline__ TileList build_tile_list(const TraceParams& P, bool active, f3 centre, uint32_t* lds) {
+// ---- corner rule ---------------------------------------------------------------------------------
+// The cap bound is loose twice over: its slope uses |e||ao| where |e x ao| would do (every edge that
+// points along the view ray: ground seen at a grazing angle), and each rule has to reject the whole cap
+// alone (acute screen-space vertices throw long wedges of false positives).  The same four forms
+// evaluated at the CORNER DIRECTIONS of a direction set remove the first cause, and doing so per pixel
+// cuts the wedges to pixel size (tools/tile_cull_model.py: island 1080p, 5,639 -> 2,854 tiles with a
+// list, 29,086 -> 12,651 entries, no hit tile lost).
+//
+// Soundness.  A set's primary directions are d = w / |w|, w = M nc, nc in a box B (tile: X above; pixel:
+// its own centre + {0} x [-j, j]^2, j = jitter_reach).  B's corners map to w_i = M nc_i with unit
+// directions c_i, and nc = sum l_i nc_i with l_i >= 0, sum l_i = 1, so w = sum l_i w_i.  Each form is
+// linear in w: if c_i.g < -m for every corner then w.g = sum l_i |w_i| c_i.g < -m sum l_i |w_i| <= -m |w|
+// (triangle inequality), i.e. d.g < -m for EVERY direction of the set; likewise c_i.g > m for all i gives
+// d.g > m.  So
+//   min_i c_i.n > m0,  max_i c_i.gu < -m1,  min_i c_i.h > m2,  min_i c_i.kw > m3
+// are R1, R3, R4, R5 with the margins unchanged.  The pixels' boxes cover the item's box, so a triangle
+// that every active pixel rejects -- each possibly by another rule -- is rejected for every primary of the
+// item by the per-rule argument, rule by rule, pixel by pixel.
+// Rounding.  c_i here and the lane's own d are float32 normalize(M nc) (products and sums rounded
+// separately here, FMAs in get_ray_dir; nc itself rounded twice): each is within ~6 x 2^-24 of the exact
+// unit vector, and a three-term dot product adds 3 x 2^-24 |g|, so a computed c_i.g and the lane's true
+// d.g are each off by < 2^-20 |g| ~ 1e-6 |g|.  Every margin is >= 1e-5 x (the product norm >= |g|), of which
+// the reference's own dot / cross sequence needs <= ~10 eps ~ 6e-7: the ~9e-6 |g| left cover both.  The
+// jitter reach j carries 1e-4 relative; what (c + t1) + t2's rounding can add beyond it (2^-24 |nc|) is a
+// direction change of the same 2^-24 order.
+// NaN.  A NaN form or margin makes its compare false (keep): the accumulations below start from the first
+// corner's value, so a NaN dot product is not skipped by fminf / fmaxf for a finite one; a lane whose own
+// corners are not finite keeps everything (the tile's corners are finite when tile_bundle says ok).
+struct FormSpan {
+  float n, u, h, w;  // min c.n, max c.gu, min c.h, min c.kw over the corners so far
+};
+__device__ __forceinline__ FormSpan span_at(f3 c, const float4& C0, const float4& C1, const float4& C2,
+                                            const float4& C3) {
+  return FormSpan{dot(c, mk(C0.x, C0.y, C0.z)), dot(c, mk(C1.x, C1.y, C1.z)), dot(c, mk(C2.x, C2.y, C2.z)),
+                  dot(c, mk(C3.x, C3.y, C3.z))};
+}
+__device__ __forceinline__ FormSpan span_join(const FormSpan& a, const FormSpan& b) {
+  return FormSpan{fminf(a.n, b.n), fmaxf(a.u, b.u), fminf(a.h, b.h), fminf(a.w, b.w)};
+}
+__device__ __forceinline__ bool span_reject(const FormSpan& s, const float4& C0, const float4& C1, const float4& C2,
+                                            const float4& C3) {
+  return (s.n > C0.w) | (s.u < -C1.w) | (s.h > C2.w) | (s.w > C3.w);
+}
+
+// Pixel stage: lane = pixel.  Each active lane holds the 4 corner directions of its own jitter box (one
+// pixel's box has no extent in x) and votes on every listed entry; an entry no active lane keeps leaves
+// the list, which stays in buffer order.
+__device__ __forceinline__ void refine_tile_list(const hrt_push_constants& pc, bool active, f3 centre,
+                                                 const float4* cam_cull, TileList& t) {
+  const uint32_t lane = threadIdx.x & 63;
+  const float j = jitter_reach(pc);
+  f3 c[4];
+  bool finite = true;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    c[q] = box_dir(pc, mk(centre.x, (q & 1) ? centre.y + j : centre.y - j, (q & 2) ? centre.z + j : centre.z - j));
+    finite &= fabsf(c[q].x) <= 2.0f && fabsf(c[q].y) <= 2.0f && fabsf(c[q].z) <= 2.0f;  // (NaN: false)
+  }
+  const kfloat* ck = to_const(cam_cull);
+  const uint32_t n = __builtin_amdgcn_readfirstlane(t.n);
+  uint32_t n2 = 0, v2 = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t e = t.lds ? __builtin_amdgcn_readfirstlane(lds_get(&t.lds[i]))
+                             : (uint32_t)__builtin_amdgcn_readlane((int)t.v, (int)i);
+    const uint32_t kk = e & 0x07FFFFFFu;
+    const float4 C0 = ldk(ck, 5 * kk), C1 = ldk(ck, 5 * kk + 1), C2 = ldk(ck, 5 * kk + 2), C3 = ldk(ck, 5 * kk + 3);
+    FormSpan s = span_at(c[0], C0, C1, C2, C3);
+#pragma unroll
+    for (int q = 1; q < 4; ++q) s = span_join(s, span_at(c[q], C0, C1, C2, C3));
+    const bool stay = active && !(finite && span_reject(s, C0, C1, C2, C3));
+    if (__any(stay)) {
+      if (t.lds) {
+        if (lane == 0) lds_put(&t.lds[n2], e);  // n2 <= i: behind the reads (a wave's LDS accesses are in order)
+      } else {
+        v2 = lane == n2 ? e : v2;
+      }
+      ++n2;
+    }
+  }
+  t.n = n2;
+  if (!t.lds) t.v = v2;
+}
+
+// Builds the wave's list (all 64 lanes active; the caller synchronises before reading it): the cap rule,
+// then the corner rule on the item's box (tile stage, lane = triangle) and per pixel (refine_tile_list).
+// refine false: the cap rule alone (hrt_debug_tile_lists' comparison lists; the trace kernels pass true).
+__device__ __forceinline__ TileList build_tile_list(const TraceParams& P, bool active, f3 centre, uint32_t* lds,
+                                                    bool refine = true) {
   const hrt_push_constants& pc = P.pc;
   TileList t{0u, lds, 0u, false, 0ull, false, 0u};
   const uint32_t cap = lds ? kTileCapLds : kTileCapVgpr;
   if (pc.num_meshes > 32 || !__any(active)) return t;
-  bool ok;
-  const Bundle b = tile_bundle(pc, active, centre, ok);
+  bool ok, flat;
+  f3 cdir;
+  const Bundle b = tile_bundle(pc, active, centre, ok, cdir, flat);
   if (!ok) return t;
   aabb_truth_table(P, t);
   const uint32_t lane = threadIdx.x & 63;
@@ -935,11 +1030,29 @@ __device__ __forceinline__ TileList build_tile_list(const TraceParams& P, bool a
   const uint32_t* cam_start = K->cam_start;
   const uint32_t* cam_count = K->cam_count;
   const float4* cam_cull = K->cam_cull;
+  const uint32_t cstep = __builtin_amdgcn_readfirstlane(flat ? 2u : 1u);  // (every lane holds the same lo, hi)
   for (int m = 0; m < pc.num_meshes; ++m) {
     const uint32_t k0 = cam_start[m], k1 = k0 + cam_count[m];
     for (uint32_t base = k0; base < k1; base += 64) {
       const uint32_t k = base + lane;
-      const bool keep = k < k1 && bundle_keep(cam_cull, k, b);
+      bool keep = false;
+      float4 C0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), C1 = C0, C2 = C0, C3 = C0;
+      if (k < k1) {
+        C0 = cam_cull[5 * k], C1 = cam_cull[5 * k + 1], C2 = cam_cull[5 * k + 2], C3 = cam_cull[5 * k + 3];
+        keep = bundle_keep(C0, C1, C2, C3, cam_cull[5 * k + 4], b);
+      }
+      // tile stage (only passes with a cap survivor: nearly no pass of a sky tile): the item's 8 corner
+      // directions, 4 when the box is flat in x, broadcast from the lanes that hold them
+      if (refine && __any(keep)) {
+        auto corner = [&](uint32_t i) {  // (wave-uniform: v_readlane)
+          return mk(bitsf((uint32_t)__builtin_amdgcn_readlane((int)fbits(cdir.x), (int)i)),
+                    bitsf((uint32_t)__builtin_amdgcn_readlane((int)fbits(cdir.y), (int)i)),
+                    bitsf((uint32_t)__builtin_amdgcn_readlane((int)fbits(cdir.z), (int)i)));
+        };
+        FormSpan s = span_at(corner(0u), C0, C1, C2, C3);
+        for (uint32_t i = cstep; i < 8u; i += cstep) s = span_join(s, span_at(corner(i), C0, C1, C2, C3));
+        keep = keep && !span_reject(s, C0, C1, C2, C3);
+      }
       unsigned long long mask = __ballot(keep);
       const uint32_t cnt = (uint32_t)__popcll(mask);
       if (t.n + cnt > cap) return t;  // ok stays false: per-iteration cull
@@ -956,6 +1069,7 @@ __device__ __forceinline__ TileList build_tile_list(const TraceParams& P, bool a
       }
     }
   }
+  if (refine && t.n) refine_tile_list(pc, active, centre, cam_cull, t);
   t.ok = true;
   wave_handoff();  // the list's entries (other lanes' stores) before the reads of world_hit_tile
   return t;
@@ -2962,7 +3076,7 @@ __global__ __launch_bounds__(1024) void trace_bundle_bvh_lds(TraceParams P) {
 // trace_fused_split's build_tile_list would for the tile's whole-tile items (the same pixels, the same
 // function) and stores it in the tile's record; the launch's items of the tile then read it back (every
 // frame of a multi-frame launch shares the camera and the camera lists).
-__global__ __launch_bounds__(256) void tile_lists(TraceParams P) {
+__global__ __launch_bounds__(256) void tile_lists(TraceParams P, uint32_t refine) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t tiles_x = (P.pc.width + 7) / 8, tiles = tiles_x * ((P.local_rows + 7) / 8);
   const uint32_t tile = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2976,7 +3090,7 @@ __global__ __launch_bounds__(256) void tile_lists(TraceParams P) {
     const float4 rc = P.rays[x + y * P.pc.width];
     centre = mk(rc.x, rc.y, rc.z);
   }
-  const TileList t = build_tile_list(P, active, centre, nullptr);
+  const TileList t = build_tile_list(P, active, centre, nullptr, refine != 0u);
   uint32_t* rec = P.tl_cache + (size_t)tile * kTlRecWords;
   rec[lane] = t.v;
   rec[64 + lane] = t.tsum;
@@ -3395,7 +3509,7 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
     }
     case HRT_KERNEL_BUNDLE_BVH_LDS: {
       if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p);
+      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
       TraceParams q = p;
       q.coop = 0;
       if (q.split_k == 0) q.split_k = 1;
@@ -3410,7 +3524,7 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
     }
     case HRT_KERNEL_BUNDLE_WQ: {
       if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p);
+      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
       TraceParams q = p;
       q.coop = 0;
       // auto: a pair step's work scales with the rays in the batch, so heavy tiles (> factor x a
@@ -3469,7 +3583,7 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
     }
     case HRT_KERNEL_BUNDLE_CULL_LDS: {
       if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p);
+      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
       TraceParams q = p;
       const uint32_t block = lds_block(p.n_tris);
       *block_out = (int)block;
@@ -3507,6 +3621,13 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
       trace_brute<<<grid, 256, 0, stream>>>(p);
       break;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_lists(const TraceParams& p, uint32_t refine, hipStream_t stream) {
+  if (!p.tl_cache) return hipErrorInvalidValue;
+  if (p.pc.num_meshes > 0) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
+  tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, refine);
   return hipGetLastError();
 }
 

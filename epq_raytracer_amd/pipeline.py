@@ -294,6 +294,17 @@ class HrtContext:
                     "hrt_debug_check_guards")
         return n.value, bad.value
 
+    def tile_lists(self, pc: _lib.PushConstants, refine: bool = True):
+        """hrt_debug_tile_lists: the 8x8 tiles' primary triangle lists for a dispatch of pc, as
+        (n[tiles], ok[tiles], entries[tiles, 64], tiles per row); entries are indices into the uploaded
+        triangle buffer in list order (0xFFFFFFFF past n).  refine=False: the cap rule alone."""
+        info = (ctypes.c_uint32 * 2)()
+        self._check(self.lib.hrt_debug_tile_lists(self.handle, ctypes.byref(pc), 0, None, 0, info), "hrt_debug_tile_lists")
+        out = np.zeros((info[0], _lib.TILE_LIST_WORDS), np.uint32)
+        self._check(self.lib.hrt_debug_tile_lists(self.handle, ctypes.byref(pc), 1 if refine else 0, _lib.ptr(out),
+                                                  out.size, info), "hrt_debug_tile_lists")
+        return out[:, 0].copy(), out[:, 1] != 0, out[:, 2:].copy(), int(info[1])
+
     # ---- multi-GPU framebuffer gather (hrt_comm_*) ----
 
     @staticmethod

@@ -41,7 +41,8 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): HRT_OPT_SKY_LANE, hrt_debug_sky_units.
+/* 6, additive (no bump: nothing existing changed): hrt_debug_tile_lists.
+ * 6, additive (no bump: nothing existing changed): HRT_OPT_SKY_LANE, hrt_debug_sky_units.
  * 6, additive (no bump: nothing existing changed): fold records -- hrt_fold_record, hrt_settle_rule,
  * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
  * 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
@@ -685,6 +686,16 @@ hrt_status hrt_debug_tile_costs(hrt_context* ctx, uint32_t* out, uint32_t count)
 /* Test support: the work units (tile x frame) that trace_sky, the sky lane's kernel (HRT_OPT_SKY_LANE), has run on
  * this context since creation or hrt_reset_stats.  Blocking. */
 hrt_status hrt_debug_sky_units(hrt_context* ctx, uint64_t* out);
+/* Test support: the primary triangle lists of the 8x8 tiles as the tile_lists kernel builds them for a
+ * dispatch of pc on this context (camera, ray centres, meshes), into a buffer of its own.  refine = 0: the
+ * cap rule alone; refine != 0: the product's lists (the cap rule, then the corner-direction rule per tile
+ * and per pixel).  Per tile 66 words: the list length n (<= 64), ok (0: the list overflowed and the
+ * kernels cull per iteration; n and the entries are then meaningless), then the n listed triangles in
+ * list order as indices into the uploaded triangle buffer (unused words 0xFFFFFFFF).
+ * info = {tiles, tiles per row}; a NULL out or words < tiles x 66 fills info only.
+ * Blocking; leaves trace lane 0's camera lists rebuilt (the next trace rebuilds its own). */
+hrt_status hrt_debug_tile_lists(hrt_context* ctx, const hrt_push_constants* pc, uint32_t refine, uint32_t* out,
+                                uint64_t words, uint32_t info[2]);
 /* HRT_TIMELINE builds: the last trace launch's item records (4 words each: start, tile list built, end,
  * item | frame << 32 | run << 40 | sky << 47 | wave << 48), at most cap of them copied; *count = the records the launch wrote (<= the
  * HRT_DEBUG_OPT_TIMELINE capacity).  Other builds: HRT_ERR_INVALID_ARGUMENT. */
