@@ -1615,6 +1615,9 @@ struct WqLds {
   uint32_t* ns;               // node-group stack: group word (fc | (count - 1) << 16) << 6 | ray
   uint32_t* ts;               // triangle-pair stack: leaf prim << 6 | ray
   uint32_t ncap;              // node stack capacity (>= 256)
+  bool capped;                // a kernel under HRT_WQ_VGPR_CAP: slot, ns, ts are wave-uniform (held in SGPRs),
+                              // and the wave-uniform values and addresses named at `capped` below stay out of
+                              // long-lived VGPRs; the uncapped kernels keep their parent's code
 };
 
 __device__ __forceinline__ f3 shfl3(f3 v, uint32_t r) {
@@ -1763,14 +1766,19 @@ __device__ __forceinline__ bool wq_tri_accept(const float4& A, const float4& B, 
 
 // closest-hit slot of ray (lane) r: seeded by its owner, lowered by any lane, read for pruning by any
 // lane (a stale value only prunes less: the slot never increases) and finally by its owner
-__device__ __forceinline__ void wq_slot_seed(unsigned long long* slot, uint32_t lane, unsigned long long v) {
-  lds_put(&slot[lane], v);
-}
 __device__ __forceinline__ void wq_slot_lower(unsigned long long* slot, uint32_t r, unsigned long long v) {
   __hip_atomic_fetch_min(&slot[r], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 __device__ __forceinline__ float wq_slot_t(const WqLds& wq, uint32_t r) {
   return __uint_as_float(lds_get(reinterpret_cast<const uint32_t*>(wq.slot) + (2 * r + 1)));
+}
+// The owner's slot.  Capped: its address is formed where it is used, from an opaque copy of the lane index
+// (one shift-add on the SGPR base): as an invariant of the item loop it sat in a VGPR, which the capped
+// kernels spilled -- a scratch reload and a full vector-memory wait before the seed and before the owner's
+// read of every bounce batch.
+__device__ __forceinline__ unsigned long long* wq_slot_own(const WqLds& wq, uint32_t lane) {
+  if (wq.capped) asm volatile("" : "+v"(lane));
+  return &wq.slot[lane];
 }
 // pair stacks: the lanes with `push` append v in lane order at the wave-uniform top n
 __device__ __forceinline__ void wq_push(uint32_t* st, uint32_t& n, bool push, uint32_t v) {
@@ -1910,7 +1918,7 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   uint32_t band_tests = 0, band_lmax = 0;
   // the ray's closest hit so far (spheres, the irregular list) seeds its slot
   const uint32_t id0 = c.kind == 2 ? ((c.mesh << 26) | c.idx) + 1u : 0u;
-  wq_slot_seed(wq.slot, lane, ((unsigned long long)__float_as_uint(c.t) << 32) | id0);
+  lds_put(wq_slot_own(wq, lane), ((unsigned long long)__float_as_uint(c.t) << 32) | id0);
   wave_handoff();  // seeds before any lane's read or lowering
   uint32_t tc = 0, tri_pairs = 0, steps = 0;
   // one step of 64 waiting triangle pairs (the band rounds' overflow guard)
@@ -1956,7 +1964,11 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
     const void* band = K->bvh_band;
     const uint32_t wide = K->bvh_band_wide;
     const float4* nhat = K->bvh_band_nhat;
-    uint8_t* const marks = reinterpret_cast<uint8_t*>(wq.ns);  // (the node stack's words: empty until the root is tested)
+    // (the node stack's words: empty until the root is tested.  Capped: their address is put in a VGPR for
+    // the rounds, by an opaque zero: the rounds otherwise read the uniform base back from a spill lane)
+    uint32_t vzero = 0;
+    if (wq.capped) asm volatile("" : "+v"(vzero));
+    uint8_t* const marks = reinterpret_cast<uint8_t*>(wq.ns) + vzero;
     // (with records, b0 of a list kept in its record is a half-word index of the records with bit 31 set,
     // band_cell: the delta keeps that flag and is taken mod 2^31)
     const uint32_t* rec = K->bvh_band_rec;
@@ -2161,7 +2173,7 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   }
   wave_handoff();  // every lowering before the owners' reads
   if (sec) {
-    const unsigned long long s = lds_get(&wq.slot[lane]);
+    const unsigned long long s = lds_get(wq_slot_own(wq, lane));
     const uint32_t id = (uint32_t)s;
     if (id != 0u) c = Closest{__uint_as_float((uint32_t)(s >> 32)), 2, (id - 1u) & 0x03FFFFFFu, (id - 1u) >> 26};
   }
@@ -2307,6 +2319,15 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     tl.aabb_ok = __builtin_amdgcn_readfirstlane(rec[132]) != 0u;
   } else {
     tl = build_tile_list(P, active, centre, list_lds);
+  }
+  // (both arms give wave-uniform n and aabb, but hipcc merges them per lane: three VGPRs held for the whole
+  // item, which the capped kernels spilled and reloaded from scratch on every primary trip)
+  if constexpr (is_wq(Bounce)) {
+    if (bsrc.capped) {
+      tl.n = __builtin_amdgcn_readfirstlane(tl.n);
+      tl.aabb = (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)tl.aabb) |
+                ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(tl.aabb >> 32)) << 32);
+    }
   }
 #else
   const TileList tl = build_tile_list(P, active, centre, list_lds);
@@ -2907,15 +2928,15 @@ __global__ __launch_bounds__(BLOCK) void trace_bundle_cull_lds(TraceParams P) {
 // 1024-thread workgroups).  Dynamic LDS: [nodes x 48 B][16 x (64 slots x 8 B, wq_ncap + wq_tcap words)].
 // (one body, two kernels: a __device__ wrapper taking P by reference changes the island kernel's
 // register allocation and cost 0.6%)
-#define HRT_WQ_KERNEL_BODY(BOUNCE, D, SKY)                                                                         \
+#define HRT_WQ_KERNEL_BODY(BOUNCE, D, SKY, CAPPED)                                                                 \
   {                                                                                                             \
     const uint32_t nn = P.bvh_wq_n_nodes;                                                                       \
     float4* nodes = lds_tris;                                                                                   \
     for (uint32_t k = threadIdx.x; k < 3 * nn; k += 1024) nodes[k] = P.bvh_wq_nodes[k];                         \
-    char* base =                                                                                                \
-        reinterpret_cast<char*>(nodes + 3 * nn) + (size_t)(threadIdx.x >> 6) * (512 + 4 * (P.wq_ncap + P.wq_tcap)); \
+    const uint32_t wave = CAPPED ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;         \
+    char* base = reinterpret_cast<char*>(nodes + 3 * nn) + (size_t)wave * (512 + 4 * (P.wq_ncap + P.wq_tcap));   \
     const WqLds wq{nodes, reinterpret_cast<unsigned long long*>(base), reinterpret_cast<uint32_t*>(base + 512),  \
-                   reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap};                            \
+                   reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap, CAPPED};                    \
     __syncthreads();                                                                                            \
     const float4* T = reinterpret_cast<const float4*>(P.tris);                                                  \
     tile_loop<1024, false, SKY>(P, nullptr, nullptr, [&](uint32_t x, uint32_t lr, Coop& co, uint32_t f, uint32_t nr) { \
@@ -2924,9 +2945,15 @@ __global__ __launch_bounds__(BLOCK) void trace_bundle_cull_lds(TraceParams P) {
   }
 // HRT_WQ_VGPR_CAP: the two kernels' VGPR budget.  Four of their waves per SIMD at 128 VGPRs fill the
 // 512-entry file; at 120 they leave 32 registers per lane for a wave of trace_sky beside them.  The cap
-// alone costs the traversal 5.7% on island and 1.7% on cave (36 spilled VGPRs against 14); with trace_sky
-// beside it the frame is 5.4% / 2.8% shorter than uncapped (112 + a 64-register trace_sky: the same on
-// island, the cap dearer on cave; 104: slower; DESIGN §18, profiles/sky_lane_step0.jsonl).
+// alone cost the traversal 5.7% on island and 1.7% on cave when it was set (36 spilled VGPRs against 14;
+// DESIGN §18, profiles/sky_lane_step0.jsonl: 112 + a 64-register trace_sky the same on island, the cap
+// dearer on cave; 104: slower), and 3.2% / 2.3% on the tree of DESIGN §20, whose register diet (CAPPED:
+// the wave's stack bases in SGPRs, the tile list's length and AABB word made uniform, two addresses formed
+// at their use) leaves 15 spilled VGPRs, none of them in the fused sample loop, the pair step, the band
+// round or the pool refill, and a cost of 0.4% / 0.4% (profiles/capped_diet_step0.jsonl).
+// The diet steers hipcc's allocator (readfirstlane, two empty asm copies) and is a property of the toolchain:
+// after a compiler change, run `make asm` and tools/isa_scratch.py and compare the four loops' scratch
+// columns with profiles/capped_diet_resources.txt.
 // (amdgpu_num_vgpr counts in halves on gfx950: the compiler doubles it for the unified VGPR / AGPR file and
 // ignores a value whose double exceeds the launch bounds' 128.)
 #ifndef HRT_WQ_VGPR_CAP
@@ -2942,21 +2969,22 @@ __global__ __launch_bounds__(BLOCK) void trace_bundle_cull_lds(TraceParams P) {
 template <bool D>
 __global__ void trace_bundle_wq(TraceParams P);
 template <>
-__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, true)
+__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, true, true)
 template <>
-__global__ __launch_bounds__(1024) void trace_bundle_wq<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, true, false)
+__global__ __launch_bounds__(1024) void trace_bundle_wq<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, true, false, false)
 // the same with per-member R in the node margins (TraceParams::bvh_node_r, HRT_OPT_WQ_NODE_RADIUS)
 template <bool D>
 __global__ void trace_bundle_wq_nr(TraceParams P);
 template <>
-__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq_nr<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, true)
+__global__ __launch_bounds__(1024) HRT_WQ_VGPRS void trace_bundle_wq_nr<false>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, true, true)
 template <>
-__global__ __launch_bounds__(1024) void trace_bundle_wq_nr<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, true, false)
+__global__ __launch_bounds__(1024) void trace_bundle_wq_nr<true>(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, true, false, false)
 // The two kernels for product launches without a sky lane (unplanned launches, HRT_OPT_SKY_LANE off: the
-// per-frame loop by default): the whole register budget and the plain work counter -- the cap costs 5.7%
-// where no trace_sky wave uses the registers it frees.
-__global__ __launch_bounds__(1024) void trace_bundle_wq_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, false)
-__global__ __launch_bounds__(1024) void trace_bundle_wq_nr_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, false)
+// per-frame loop by default): the whole register budget and the plain work counter -- the cap still costs
+// 0.4% where no trace_sky wave uses the registers it frees, and these two keep the code they had (with the
+// bases uniform their pair step reads one from a spill lane: 0.9% slower on island).
+__global__ __launch_bounds__(1024) void trace_bundle_wq_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWq, false, false, false)
+__global__ __launch_bounds__(1024) void trace_bundle_wq_nr_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, false, false)
 #undef HRT_WQ_KERNEL_BODY
 
 // The sky lane (HRT_OPT_SKY_LANE): the plan's sky items on a lean kernel of their own, resident beside
@@ -3288,7 +3316,7 @@ __global__ __launch_bounds__(64) void wq_protocol_check(uint32_t rounds, const u
   __shared__ unsigned long long slot[64];
   __shared__ uint32_t st[kProtoCap];
   const uint32_t lane = threadIdx.x & 63u;
-  wq_slot_seed(slot, lane, seed[lane]);
+  lds_put(&slot[lane], seed[lane]);
   wave_handoff();
   uint32_t n = 0;
   for (uint32_t r = 0; r < rounds; ++r) {
