@@ -99,6 +99,36 @@ FOLD_RECORD_RING = 1024      # HRT_FOLD_RECORD_RING
 RGBA8_FREEZE_FRAME = 510     # HRT_RGBA8_FREEZE_FRAME
 RULE_ANY = 0xFFFFFFFF        # a settle-rule bound that is disabled
 
+
+class RayQuery(ctypes.Structure):
+    """hrt_ray_query: one caller ray (32 bytes)."""
+
+    _fields_ = [("origin", c_float * 3), ("t_max", c_float), ("direction", c_float * 3), ("reserved", c_uint32)]
+
+
+class Hit(ctypes.Structure):
+    """hrt_hit: the closest hit of one ray (32 bytes)."""
+
+    _fields_ = [("t", c_float), ("kind", c_uint32), ("index", c_uint32), ("mesh", c_uint32), ("normal", c_float * 3),
+                ("reserved", c_uint32)]
+
+
+class QueryStats(ctypes.Structure):
+    """hrt_query_stats: what one hrt_intersect / hrt_intersect_primary call ran (24 bytes)."""
+
+    _fields_ = [("method_ran", c_uint32), ("reserved", c_uint32), ("scan_rays", c_uint64), ("tri_tests", c_uint64)]
+
+
+assert ctypes.sizeof(RayQuery) == 32 and ctypes.sizeof(Hit) == 32 and ctypes.sizeof(QueryStats) == 24
+RAY_QUERY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("mesh", "<u4"), ("normal", "<f4", 3),
+                      ("reserved", "<u4")])
+assert RAY_QUERY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+QUERY_AUTO, QUERY_SCAN, QUERY_BVH, QUERY_PAIRS = 0, 1, 2, 3  # hrt_query_method
+QUERY_NAMES = {0: "auto", 1: "scan", 2: "bvh", 3: "pairs"}
+HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # hrt_hit.kind
+HIT_NONE = 0xFFFFFFFF  # hrt_hit.index / mesh of a miss
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -162,7 +192,7 @@ SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh
 # Every symbol include/*.h declares (tests/test_abi.py checks the export table against this).
 EXPORTED_SYMBOLS = (
     "hrt_abi_version", "hrt_build_id", "hrt_debug_build", "hrt_debug_check_guards", "hrt_create", "hrt_destroy", "hrt_set_scene", "hrt_trace", "hrt_accumulate", "hrt_compute_n",
-    "hrt_compute_until", "hrt_get_fold_records",
+    "hrt_compute_until", "hrt_get_fold_records", "hrt_intersect", "hrt_intersect_primary",
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
@@ -222,6 +252,9 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_compute_until": (c_int32, [P, POINTER(PushConstants), c_uint32, POINTER(SettleRule), POINTER(c_uint32),
                                         POINTER(c_uint32)]),
         "hrt_get_fold_records": (c_int32, [P, P, c_uint32, POINTER(c_uint32), POINTER(c_uint64)]),
+        "hrt_intersect": (c_int32, [P, P, c_uint32, c_uint32, P, POINTER(QueryStats)]),
+        "hrt_intersect_primary": (c_int32, [P, POINTER(PushConstants), c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
+                                            P, POINTER(QueryStats)]),
         "hrt_read_image": (c_int32, [P, c_uint32, c_uint32, P, c_size_t]),
         "hrt_load_accumulator": (c_int32, [P, c_uint32, P, c_size_t]),
         "hrt_get_layout": (c_int32, [P, POINTER(Layout)]),

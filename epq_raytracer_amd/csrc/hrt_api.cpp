@@ -472,6 +472,9 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->ring);
   free_dev(ctx, ctx->fold_ring);
   free_dev(ctx, ctx->fold_scratch);
+  free_dev(ctx, ctx->query_rays);
+  free_dev(ctx, ctx->query_hits);
+  free_dev(ctx, ctx->query_stats);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -1020,6 +1023,138 @@ extern "C" hrt_status hrt_trace(hrt_context* ctx, const hrt_push_constants* pc) 
   ctx->cur_slot = slot;
   if (slot >= 0) ctx->ring_next = (uint32_t)(slot + 1) % ctx->ring_n;
   return end_lane(ctx, l);
+}
+
+// ---- ray queries ---------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t kQueryChunk = 1u << 16;   // rays per staged chunk (2 MiB of rays, 2 MiB of hits)
+constexpr uint32_t kQueryLaunch = 1u << 24;  // rays per launch when nothing is staged
+
+// Whether a kernel of this context reads / writes p directly: memory of its device or managed memory.
+// Anything else (pageable or registered host memory, another device's) goes through the staging buffers.
+bool query_direct(hrt_context* ctx, const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // (an unknown pointer is not a sticky error)
+    return false;
+  }
+  return (at.type == hipMemoryTypeDevice && at.device == ctx->device) || at.type == hipMemoryTypeManaged;
+}
+
+// n rays (rays, or, when rays is null, the primary rays k = 0 .. n - 1 of rect) -> hits, blocking.  Every
+// argument has been checked; p.pc holds the counts (and the camera).
+hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* rays, uint32_t n, const uint32_t rect[3],
+                     uint32_t method, hrt_hit* hits, hrt_query_stats* stats, const char* who) {
+  const bool primary = rays == nullptr;
+  // a query writes no image, counter or planner buffer of the context
+  p.img8 = nullptr;
+  p.img32 = nullptr;
+  p.counters = nullptr;
+  p.diag = nullptr;
+  p.tile_cycles = nullptr;
+  p.sky_units = nullptr;
+  p.timeline = nullptr;
+  p.timeline_count = nullptr;
+  const int ran = hrt::resolve_query_method(p, (int)method);
+  const bool rays_direct = primary || query_direct(ctx, rays), hits_direct = query_direct(ctx, hits);
+  if ((!primary && rays_direct && (uintptr_t)rays % 16 != 0) || (hits_direct && (uintptr_t)hits % 16 != 0))
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": device rays / hits must be 16-byte aligned");
+  auto ensure = [&](void** buf, size_t bytes) -> hrt_status {
+    if (*buf) return HRT_OK;
+    if (hrt::dev_alloc(ctx, buf, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, HRT_ERR_OUT_OF_MEMORY, std::string(who) + ": staging allocation failed");
+    }
+    return HRT_OK;
+  };
+  hrt_status st;
+  if (!rays_direct && (st = ensure(&ctx->query_rays, (size_t)kQueryChunk * sizeof(hrt_ray_query))) != HRT_OK) return st;
+  if (!hits_direct && (st = ensure(&ctx->query_hits, (size_t)kQueryChunk * sizeof(hrt_hit))) != HRT_OK) return st;
+  if (stats) {
+    if ((st = ensure(reinterpret_cast<void**>(&ctx->query_stats), 2 * sizeof(unsigned long long))) != HRT_OK) return st;
+    HRT_HIP(ctx, hipMemsetAsync(ctx->query_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  }
+  const uint32_t chunk = (rays_direct && hits_direct) ? kQueryLaunch : kQueryChunk;
+  for (uint32_t at = 0; at < n; at += std::min(chunk, n - at)) {
+    const uint32_t m = std::min(chunk, n - at);
+    hrt::QueryArgs q{};
+    if (!primary) {
+      if (rays_direct) {
+        q.rays = reinterpret_cast<const float4*>(rays + at);
+      } else {
+        HRT_HIP(ctx, hipMemcpyAsync(ctx->query_rays, rays + at, (size_t)m * sizeof(hrt_ray_query), hipMemcpyDefault,
+                                    ctx->stream));
+        q.rays = static_cast<const float4*>(ctx->query_rays);
+      }
+    }
+    q.hits = hits_direct ? reinterpret_cast<float4*>(hits + at) : static_cast<float4*>(ctx->query_hits);
+    q.stats = stats ? ctx->query_stats : nullptr;
+    q.n = m;
+    q.first = at;
+    q.x0 = rect[0];
+    q.y0 = rect[1];
+    q.w = rect[2];
+    HRT_HIP(ctx, hrt::launch_query(p, q, ran, primary, ctx->stream));
+    if (!hits_direct)
+      HRT_HIP(ctx, hipMemcpyAsync(hits + at, ctx->query_hits, (size_t)m * sizeof(hrt_hit), hipMemcpyDefault, ctx->stream));
+  }
+  unsigned long long counts[2] = {0, 0};
+  if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->query_stats, sizeof(counts), hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) *stats = hrt_query_stats{(uint32_t)ran, 0u, counts[0], counts[1]};
+  return HRT_OK;
+}
+
+bool known_query_method(uint32_t method) {
+  // the four methods of hrt_query_method
+  return method <= HRT_QUERY_PAIRS;
+}
+
+}  // namespace
+
+extern "C" hrt_status hrt_intersect(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n, uint32_t method,
+                                    hrt_hit* hits, hrt_query_stats* stats) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (!known_query_method(method)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect: unknown method");
+  if (!ctx->scene_set) return fail(ctx, HRT_ERR_NO_SCENE, "hrt_intersect: hrt_set_scene has not been called");
+  if (n > 0 && (!rays || !hits)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect: null rays or hits");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  hrt_push_constants pc{};
+  pc.width = ctx->width;
+  pc.height = ctx->height;
+  pc.num_spheres = (int32_t)ctx->scene.n_spheres;
+  pc.num_meshes = (int32_t)ctx->scene.n_meshes;
+  const hrt::TraceParams p = make_params(ctx, &pc, 0);
+  if (n == 0) {
+    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::resolve_query_method(p, (int)method), 0u, 0u, 0u};
+    return HRT_OK;
+  }
+  const uint32_t rect[3] = {0, 0, 1};
+  return run_query(ctx, p, rays, n, rect, method, hits, stats, "hrt_intersect");
+}
+
+extern "C" hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_constants* pc, uint32_t x0, uint32_t y0,
+                                            uint32_t w, uint32_t h, uint32_t method, hrt_hit* hits,
+                                            hrt_query_stats* stats) {
+  if (!ctx || !pc) return HRT_ERR_INVALID_ARGUMENT;
+  if (!known_query_method(method)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect_primary: unknown method");
+  hrt_status st = check_dispatch(ctx, pc, "hrt_intersect_primary");
+  if (st != HRT_OK) return st;
+  if (x0 > ctx->width || w > ctx->width - x0 || y0 > ctx->height || h > ctx->height - y0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect_primary: the rectangle lies outside the image");
+  const uint64_t n = (uint64_t)w * h;
+  if (n > 0xFFFFFFFFull) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect_primary: more than 2^32 - 1 pixels");
+  if (n > 0 && !hits) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_intersect_primary: null hits");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  const hrt::TraceParams p = make_params(ctx, pc, 0);
+  if (n == 0) {
+    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::resolve_query_method(p, (int)method), 0u, 0u, 0u};
+    return HRT_OK;
+  }
+  const uint32_t rect[3] = {x0, y0, w};
+  return run_query(ctx, p, nullptr, (uint32_t)n, rect, method, hits, stats, "hrt_intersect_primary");
 }
 
 // The frame stack's allocation (the debug build can make it fail above HRT_DEBUG_OPT_STACK_LIMIT bytes).

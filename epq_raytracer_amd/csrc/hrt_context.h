@@ -207,6 +207,11 @@ struct hrt_context {
   std::vector<uint32_t> fold_frame;
   uint64_t fold_total = 0;
   uint32_t fold_on = 0;
+  // Ray queries (hrt_intersect / hrt_intersect_primary): staging for host-side rays and hits (kQueryChunk
+  // records each) and the two statistics words, allocated by the first query
+  void* query_rays = nullptr;
+  void* query_hits = nullptr;
+  unsigned long long* query_stats = nullptr;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

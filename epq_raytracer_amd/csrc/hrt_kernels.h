@@ -139,6 +139,23 @@ hipError_t launch_wq_protocol_check(uint32_t rounds, const uint32_t* cnt, const 
 // BUNDLE_WQ's per-wave node-stack capacity for an image of n_nodes records with groups of `width` and
 // leaves of at most max_leaf triangles (0: does not fit the LDS)
 uint32_t wq_stack_cap(uint32_t n_nodes, uint32_t width, uint32_t max_leaf);
+// Ray queries (hrt_intersect / hrt_intersect_primary): the query kernels' own arguments,
+// passed after the TraceParams block (world_hit_bounce_wq reads its constants through the kernarg
+// segment's start).  One ray per lane: ray i of the launch is rays[2 i], rays[2 i + 1] (hrt_ray_query),
+// or, primary, the un-jittered ray of pixel (x0 + k % w, y0 + k / w) with k = first + i; its hit goes to
+// hits[2 i], hits[2 i + 1] (hrt_hit).
+struct QueryArgs {
+  const float4* rays;         // n hrt_ray_query records (nullptr: primary)
+  float4* hits;               // n hrt_hit records
+  unsigned long long* stats;  // [0] rays answered by the literal scan (non-finite), [1] triangle tests; or nullptr
+  uint32_t n;                 // rays of this launch
+  uint32_t first;             // primary: the rectangle index of ray 0
+  uint32_t x0, y0, w;         // primary: the rectangle's corner and width
+};
+// The method an hrt_query_method request runs on p's scene (AUTO resolved, fallbacks applied).
+int resolve_query_method(const TraceParams& p, int method);
+// Launches q.n rays with `method` (already resolved); p.pc holds the sphere / mesh counts (and, primary, the camera).
+hipError_t launch_query(const TraceParams& p, const QueryArgs& q, int method, bool primary, hipStream_t stream);
 constexpr uint32_t kAutoLeafWqStack = 512;  // auto leaf size: the smallest leaf whose image leaves this much
 
 }  // namespace hrt

@@ -3475,6 +3475,13 @@ static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
 
 // The persistent kernels' dynamic-LDS limits, set once per device (hrt_create calls this for its device;
 // the attribute is per device, so every device a context lives on gets its own call).
+// The ray queries' PAIRS kernel (defined at the end of the file).  Declared here so that the list below can
+// take its instantiations' addresses -- and keep it here: it also fixes where the compiler emits them.  With
+// the kernel first used at the end of the file, hipcc compiled the six trace_bundle_wq* kernels' triangle step
+// with one more address computation (profiles/query_resources.txt); instantiated from here, every
+// pre-existing kernel's code is what it is without the query kernels.
+template <bool Primary, bool NodeR>
+__global__ void query_pairs(TraceParams P, QueryArgs Q);
 hipError_t ensure_kernel_attributes(int device) {
   static std::mutex mu;
   static std::vector<char> done;
@@ -3493,7 +3500,11 @@ hipError_t ensure_kernel_attributes(int device) {
                             reinterpret_cast<const void*>(&trace_bundle_wq_nr<false>),
                             reinterpret_cast<const void*>(&trace_bundle_wq_nr<true>),
                             reinterpret_cast<const void*>(&trace_bundle_wq_solo),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_nr_solo)};
+                            reinterpret_cast<const void*>(&trace_bundle_wq_nr_solo),
+                            reinterpret_cast<const void*>(&query_pairs<false, false>),
+                            reinterpret_cast<const void*>(&query_pairs<false, true>),
+                            reinterpret_cast<const void*>(&query_pairs<true, false>),
+                            reinterpret_cast<const void*>(&query_pairs<true, true>)};
   hipError_t e;
   for (const void* f : brute)
     if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsScene)) != hipSuccess)
@@ -3704,6 +3715,205 @@ hipError_t launch_math_check_rng(unsigned long long* out, hipStream_t stream) {
 hipError_t launch_math_check(uint32_t n, uint32_t seed, unsigned long long* out, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   math_check<<<(n + 255) / 256, 256, 0, stream>>>(n, seed, out);
+  return hipGetLastError();
+}
+
+// ---- ray queries: closest hit of caller rays and of un-jittered primary rays -------------
+// One ray per lane.  A query is the reference's world_hit (raytracing.glsl:267-288) for one ray that did not
+// come from a pixel's sample chain; the three methods feed it to world_hit's three
+// implementations above and give the same bytes:
+//   SCAN   the statement-by-statement scan, its running closest seeded with the ray's t_max;
+//   BVH    world_hit_bounce_bvh on the global-memory hierarchy (irregular list and grazing band included);
+//   PAIRS  world_hit_bounce_wq, 64 rays per wave, the node image in LDS (persistent 1024-thread workgroups).
+// The traversals start their closest at FLT_MAX (spheres_first), so t_max is applied to their result: the
+// closest accepted hit overall, first in scan order among equals, is the seeded scan's answer when it lies
+// below t_max, and otherwise nothing the scan accepts does.  A ray whose origin or normalised direction is
+// not finite, or whose direction's squared length is zero, denormal or overflows (its quotient is then no
+// unit vector), is outside the traversals' analysis and takes the scan whatever the method.
+struct QueryRay {
+  f3 o, d;     // origin, S4-normalised direction
+  float best;  // min(t_max, FLT_MAX): where the running closest starts
+  bool live;   // a ray of the launch that is not a certain miss (t_max > 0.001, not NaN)
+  bool finite; // every component of o and d is finite and d is a unit vector (dot(v, v) normal and finite)
+};
+__device__ __forceinline__ bool finite3(f3 a) {
+  return fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff();
+}
+template <bool Primary>
+__device__ __forceinline__ QueryRay query_ray(const TraceParams& P, const QueryArgs& Q, uint32_t i) {
+  QueryRay r{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 1.0f), kFltMax, false, true};
+  if (i >= Q.n) return r;
+  float t_max = kFltMax;
+  f3 v;
+  if constexpr (Primary) {
+    const uint32_t k = Q.first + i, x = Q.x0 + k % Q.w, y = Q.y0 + k / Q.w;
+    const float4 rc = P.rays[x + (size_t)y * P.pc.width];
+    const float* M = P.pc.cam_alignment_mat;
+    // mat3(M) c, row-wise as get_ray_dir spells it
+    v = mk(__builtin_fmaf(M[8], rc.z, __builtin_fmaf(M[4], rc.y, M[0] * rc.x)),
+           __builtin_fmaf(M[9], rc.z, __builtin_fmaf(M[5], rc.y, M[1] * rc.x)),
+           __builtin_fmaf(M[10], rc.z, __builtin_fmaf(M[6], rc.y, M[2] * rc.x)));
+    r.o = mk(P.pc.cam_pos[0], P.pc.cam_pos[1], P.pc.cam_pos[2]);
+  } else {
+    const float4 a = Q.rays[2 * (size_t)i], b = Q.rays[2 * (size_t)i + 1];
+    r.o = mk(a.x, a.y, a.z);
+    t_max = a.w;
+    v = mk(b.x, b.y, b.z);
+  }
+  r.d = normalize(v);
+  r.live = t_max > 0.001f;  // (false for NaN)
+  r.best = t_max > kFltMax ? kFltMax : t_max;
+  // (a zero, denormal or overflowed dot(v, v) leaves a d that is finite at best, not a unit vector)
+  const float d2 = dot(v, v);
+  r.finite = finite3(r.o) && finite3(r.d) && d2 >= 0x1p-126f && d2 <= kFltMax;
+  return r;
+}
+
+// world_hit_literal with the running closest started at `best` and the given counts.
+__device__ __forceinline__ Closest world_hit_scan_from(const Scene& sc, int n_spheres, int n_meshes, f3 o, f3 d,
+                                                       float best, uint32_t& tests) {
+  Closest c{best, 0, 0u, 0u};
+  for (int i = 0; i < n_spheres; ++i) {
+    const float t = sphere_dist(sc.spheres[i], o, d);
+    if (t > 0.001f && t < c.t) c = Closest{t, 1, (uint32_t)i, 0u};
+  }
+  for (int m = 0; m < n_meshes; ++m) {
+    const hrt_mesh& mesh = sc.meshes[m];
+    if (!aabb_pass(mesh, o, d)) continue;
+    tests += mesh.len;
+    const uint32_t end = mesh.first_index + mesh.len;
+    for (uint32_t i = mesh.first_index; i < end; ++i) {
+      float t;
+      if (tri_accept_exact(sc.tris[i], o, d, c.t, t)) c = Closest{t, 2, i, (uint32_t)m};
+    }
+  }
+  return c;
+}
+
+// The hit record of ray i (two 16-byte vector stores) and the wave's share of the statistics.  ALL 64 lanes.
+__device__ __forceinline__ void query_store(const Scene& sc, const QueryArgs& Q, uint32_t i, const QueryRay& r,
+                                            const Closest& c, uint32_t tests) {
+  if (i < Q.n) {
+    float4 h0 = make_float4(kFltMax, bitsf(0u), bitsf(0xFFFFFFFFu), bitsf(0xFFFFFFFFu));
+    float4 h1 = make_float4(0.0f, 0.0f, 0.0f, bitsf(0u));
+    if (c.kind != 0) {
+      const HitRecord h = resolve_hit(sc, c, r.o, r.d);
+      h0 = make_float4(c.t, bitsf((uint32_t)c.kind), bitsf(c.idx), bitsf(c.kind == 2 ? c.mesh : 0xFFFFFFFFu));
+      h1 = make_float4(h.normal.x, h.normal.y, h.normal.z, bitsf(0u));
+    }
+    Q.hits[2 * (size_t)i] = h0;
+    Q.hits[2 * (size_t)i + 1] = h1;
+  }
+  if (Q.stats) {
+    unsigned long long s = (r.live && !r.finite) ? 1u : 0u, t = tests;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      s += __shfl_xor(s, off, 64);
+      t += __shfl_xor(t, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0 && (s | t)) {
+      if (s) atomicAdd(&Q.stats[0], s);
+      if (t) atomicAdd(&Q.stats[1], t);
+    }
+  }
+}
+
+template <bool Primary>
+__global__ __launch_bounds__(256) void query_scan(TraceParams P, QueryArgs Q) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const QueryRay r = query_ray<Primary>(P, Q, i);
+  uint32_t tests = 0;
+  Closest c{kFltMax, 0, 0u, 0u};
+  if (r.live) c = world_hit_scan_from(sc, P.pc.num_spheres, P.pc.num_meshes, r.o, r.d, r.best, tests);
+  query_store(sc, Q, i, r, c, tests);
+}
+
+// a traversal's result under t_max, or the literal scan of a ray outside the traversals' domain
+__device__ __forceinline__ void query_finish(const Scene& sc, const TraceParams& P, const QueryRay& r, bool trav,
+                                             Closest& c, uint32_t& tests) {
+  if (!trav || !(c.t < r.best)) c = Closest{kFltMax, 0, 0u, 0u};
+  if (r.live && !r.finite) c = world_hit_scan_from(sc, P.pc.num_spheres, P.pc.num_meshes, r.o, r.d, r.best, tests);
+}
+
+template <bool Primary>
+__global__ __launch_bounds__(256) void query_bvh(TraceParams P, QueryArgs Q) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const QueryRay r = query_ray<Primary>(P, Q, i);
+  const bool trav = r.live && r.finite;
+  const f3 o = trav ? r.o : mk(0.0f, 0.0f, 0.0f), d = trav ? r.d : mk(0.0f, 0.0f, 1.0f);
+  uint32_t tests = 0;
+  Closest c{kFltMax, 0, 0u, 0u};
+  Diag dg;
+  world_hit_bounce_bvh<false>(sc, P, BvhGlobal{P.bvh_nodes, P.bvh_prims}, trav, o, d, tests, c, dg);
+  query_finish(sc, P, r, trav, c, tests);
+  query_store(sc, Q, i, r, c, tests);
+}
+
+// PAIRS: the node image staged into LDS and the per-wave stacks carved as the BUNDLE_WQ kernels carve them;
+// each wave then takes 64 rays at a time (all 64 lanes enter the traversal, tail lanes as inactive rays).
+template <bool Primary, bool NodeR>
+__global__ __launch_bounds__(1024) void query_pairs(TraceParams P, QueryArgs Q) {
+  const uint32_t nn = P.bvh_wq_n_nodes;
+  float4* nodes = lds_tris;
+  for (uint32_t k = threadIdx.x; k < 3 * nn; k += 1024) nodes[k] = P.bvh_wq_nodes[k];
+  const uint32_t wave = threadIdx.x >> 6;
+  char* base = reinterpret_cast<char*>(nodes + 3 * nn) + (size_t)wave * (512 + 4 * (P.wq_ncap + P.wq_tcap));
+  const WqLds wq{nodes, reinterpret_cast<unsigned long long*>(base), reinterpret_cast<uint32_t*>(base + 512),
+                 reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap, false};
+  __syncthreads();
+  // (wave-uniform trip count: i - lane is the wave's first ray)
+  for (uint32_t w0 = blockIdx.x * 1024u + wave * 64u; w0 < Q.n; w0 += gridDim.x * 1024u) {
+    const uint32_t i = w0 + (threadIdx.x & 63u);
+    const QueryRay r = query_ray<Primary>(P, Q, i);
+    const bool trav = r.live && r.finite;
+    const f3 o = trav ? r.o : mk(0.0f, 0.0f, 0.0f), d = trav ? r.d : mk(0.0f, 0.0f, 1.0f);
+    uint32_t tests = 0;
+    Closest c{kFltMax, 0, 0u, 0u};
+    Diag dg;
+    world_hit_bounce_wq<false, NodeR>(kscene(), P, wq, trav, o, d, tests, c, dg);
+    const Scene sc = kscene();
+    query_finish(sc, P, r, trav, c, tests);
+    query_store(sc, Q, i, r, c, tests);
+  }
+}
+
+int resolve_query_method(const TraceParams& p, int method) {
+  if (method == HRT_QUERY_AUTO) method = HRT_QUERY_BVH;
+  // (the traversals keep a ray's mesh filter in 64 bits, as the trace kernels' fallbacks say)
+  if (method == HRT_QUERY_PAIRS && (wq_lds_bytes(p, nullptr, nullptr) == 0 || p.pc.num_meshes > 64)) method = HRT_QUERY_BVH;
+  if (method == HRT_QUERY_BVH && (!p.bvh_nodes || p.pc.num_meshes > 64)) method = HRT_QUERY_SCAN;
+  return method;
+}
+
+hipError_t launch_query(const TraceParams& p0, const QueryArgs& q, int method, bool primary, hipStream_t stream) {
+  if (q.n == 0) return hipSuccess;
+  const uint32_t blocks = (q.n + 255u) / 256u;
+  switch (method) {
+    case HRT_QUERY_SCAN:
+      primary ? query_scan<true><<<blocks, 256, 0, stream>>>(p0, q) : query_scan<false><<<blocks, 256, 0, stream>>>(p0, q);
+      break;
+    case HRT_QUERY_BVH:
+      primary ? query_bvh<true><<<blocks, 256, 0, stream>>>(p0, q) : query_bvh<false><<<blocks, 256, 0, stream>>>(p0, q);
+      break;
+    case HRT_QUERY_PAIRS: {
+      TraceParams p = p0;
+      const size_t lds = wq_lds_bytes(p0, &p.wq_ncap, &p.wq_tcap);
+      if (lds == 0) return hipErrorInvalidValue;
+      if (p0.wq_ncap) p.wq_ncap = std::min(p.wq_ncap, std::max(128u, p0.wq_ncap & ~63u));  // HRT_OPT_WQ_NODE_CAP
+      if (p0.wq_tcap) p.wq_tcap = std::min(p.wq_tcap, std::max(128u, p0.wq_tcap & ~63u));  // HRT_DEBUG_OPT_WQ_TRI_CAP
+      // (their dynamic-LDS limit: ensure_kernel_attributes)
+      void (*kernel)(TraceParams, QueryArgs) =
+          p.bvh_node_r ? (primary ? query_pairs<true, true> : query_pairs<false, true>)
+                       : (primary ? query_pairs<true, false> : query_pairs<false, false>);
+      const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
+      kernel<<<groups, 1024, lds, stream>>>(p, q);
+      break;
+    }
+    default:
+      return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

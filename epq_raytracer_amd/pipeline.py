@@ -287,6 +287,60 @@ class HrtContext:
         """Block until the present pass of `ticket` has finished."""
         self._check(self.lib.hrt_present_wait(self.handle, int(ticket)), "hrt_present_wait")
 
+    # ---- ray queries (hrt_intersect, hrt_intersect_primary) ----
+
+    @staticmethod
+    def ray_queries(origins, directions, t_max=None) -> np.ndarray:
+        """n hrt_ray_query records (_lib.RAY_QUERY_DTYPE) of origins[n, 3], directions[n, 3] (any length:
+        the library normalises them) and t_max (None: FLT_MAX; a scalar or n values)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        rays = np.zeros(len(o), dtype=_lib.RAY_QUERY_DTYPE)
+        rays["origin"], rays["direction"] = o, d
+        rays["t_max"] = np.finfo(np.float32).max if t_max is None else np.asarray(t_max, np.float32)
+        return rays
+
+    def intersect_into(self, rays_ptr: int, n: int, hits_ptr: int, method: int = _lib.QUERY_AUTO,
+                       with_stats: bool = False):
+        """hrt_intersect on caller memory: n hrt_ray_query records at rays_ptr -> n hrt_hit records at
+        hits_ptr (host pointers, or 16-byte aligned pointers into the context's device, e.g. a torch tensor's
+        data_ptr()).  Blocking.  Returns the call's _lib.QueryStats when with_stats, else None."""
+        st = _lib.QueryStats()
+        self._check(self.lib.hrt_intersect(self.handle, ctypes.c_void_p(rays_ptr), int(n), int(method),
+                                           ctypes.c_void_p(hits_ptr), ctypes.byref(st) if with_stats else None),
+                    "hrt_intersect")
+        return st if with_stats else None
+
+    def intersect(self, origins, directions, t_max=None, method: int = _lib.QUERY_AUTO, with_stats: bool = False):
+        """hrt_intersect: the closest hit of each ray (the reference's world_hit) as a
+        structured array (_lib.HIT_DTYPE: t, kind 0 miss / 1 sphere / 2 triangle, index, mesh, normal).
+        ``origins`` may also be a ready _lib.RAY_QUERY_DTYPE array (then ``directions`` is None).
+        with_stats=True returns (hits, _lib.QueryStats)."""
+        if directions is None:
+            rays = np.ascontiguousarray(origins, dtype=_lib.RAY_QUERY_DTYPE)
+        else:
+            rays = self.ray_queries(origins, directions, t_max)
+        hits = np.zeros(len(rays), dtype=_lib.HIT_DTYPE)
+        st = self.intersect_into(rays.ctypes.data if len(rays) else 0, len(rays), hits.ctypes.data if len(rays) else 0,
+                                 method, with_stats)
+        return (hits, st) if with_stats else hits
+
+    def intersect_primary(self, pc: _lib.PushConstants, rect=None, method: int = _lib.QUERY_AUTO,
+                          with_stats: bool = False):
+        """hrt_intersect_primary: the closest hit of the un-jittered primary ray of every pixel of rect =
+        (x0, y0, w, h) (None: the whole image), as an (h, w) structured array (_lib.HIT_DTYPE).  Rows are
+        trace-image rows (the present pass shows them flipped)."""
+        x0, y0, w, h = (0, 0, self.width, self.height) if rect is None else (int(v) for v in rect)
+        hits = np.zeros(max(w, 0) * max(h, 0), dtype=_lib.HIT_DTYPE)
+        st = _lib.QueryStats()
+        self._check(self.lib.hrt_intersect_primary(self.handle, ctypes.byref(pc), x0, y0, w, h, int(method),
+                                                   _lib.ptr(hits), ctypes.byref(st) if with_stats else None),
+                    "hrt_intersect_primary")
+        hits = hits.reshape(h, w)
+        return (hits, st) if with_stats else hits
+
     def check_guards(self):
         """libhip_raytrace_debug.so: (guarded device buffers, buffers whose guard bands were overwritten)."""
         n, bad = ctypes.c_uint32(), ctypes.c_uint32()
@@ -449,6 +503,18 @@ class RayTracePipeline:
 
     def compute(self, camera: Camera, rng_offset: int) -> None:
         self.ctx.trace(self.push_constants(camera, rng_offset, False))
+
+    def first_hits(self, camera: Camera, rect=None) -> np.ndarray:
+        """The first-hit buffer of a view: the closest hit (t, kind, index, mesh, normal; _lib.HIT_DTYPE) of
+        the un-jittered primary ray of every pixel of rect = (x0, y0, w, h) (None: the whole image), as an
+        (h, w) array in trace-image rows (hrt_intersect_primary)."""
+        return self.ctx.intersect_primary(self.push_constants(camera, 0, False), rect)
+
+    def pick(self, camera: Camera, x: int, y: int):
+        """What lies under pixel (x, y) of the view: one hit record (numpy.void of _lib.HIT_DTYPE).  x, y are
+        trace-image coordinates; the present pass flips rows, so a pixel of a presented height-H target is
+        row H - 1 - y here."""
+        return self.first_hits(camera, (int(x), int(y), 1, 1))[0, 0]
 
     def init(self) -> None:
         self.ctx.trace(self.push_constants(Camera(), 0, True))

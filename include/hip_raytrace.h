@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): hrt_debug_tile_lists.
+/* 6, additive (no bump: nothing existing changed): ray queries -- hrt_ray_query, hrt_hit, hrt_query_stats,
+ * hrt_query_method, hrt_intersect, hrt_intersect_primary.
+ * 6, additive (no bump: nothing existing changed): hrt_debug_tile_lists.
  * 6, additive (no bump: nothing existing changed): HRT_OPT_SKY_LANE, hrt_debug_sky_units.
  * 6, additive (no bump: nothing existing changed): fold records -- hrt_fold_record, hrt_settle_rule,
  * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
@@ -219,6 +221,37 @@ typedef struct hrt_settle_rule {
   uint32_t flags;              /* must be 0 */
 } hrt_settle_rule;
 
+/* ---- ray queries (hrt_intersect, hrt_intersect_primary) ---- */
+typedef struct hrt_ray_query {
+  float origin[3];
+  float t_max;        /* the running closest starts at min(t_max, FLT_MAX); NaN or <= 0.001: a certain miss */
+  float direction[3]; /* any length: normalised by S4 before the scan; t is along the normalised direction */
+  uint32_t reserved;  /* ignored */
+} hrt_ray_query;
+
+typedef struct hrt_hit {
+  float t;           /* the reference's hit_dist; FLT_MAX for a miss */
+  uint32_t kind;     /* 0 miss, 1 sphere, 2 triangle */
+  uint32_t index;    /* sphere index / index into the uploaded triangle buffer; 0xFFFFFFFF for a miss */
+  uint32_t mesh;     /* mesh index of a triangle hit; 0xFFFFFFFF otherwise */
+  float normal[3];   /* the reference's hit normal (unit, not flipped toward the ray); 0 for a miss */
+  uint32_t reserved; /* 0 */
+} hrt_hit;
+
+typedef struct hrt_query_stats {
+  uint32_t method_ran; /* hrt_query_method that ran: AUTO resolved, fallbacks applied */
+  uint32_t reserved;   /* 0 */
+  uint64_t scan_rays;  /* rays answered by the literal scan because their origin or normalised direction is not finite */
+  uint64_t tri_tests;  /* sum over rays of len of every mesh whose AABB test passes (hrt_stats.tri_tests per segment) */
+} hrt_query_stats;
+
+typedef enum hrt_query_method {
+  HRT_QUERY_AUTO = 0,  /* BVH when the hierarchy is built, else SCAN */
+  HRT_QUERY_SCAN = 1,  /* the reference's scan, statement by statement */
+  HRT_QUERY_BVH = 2,   /* per-lane traversal of the global-memory hierarchy (SCAN when it was not built) */
+  HRT_QUERY_PAIRS = 3  /* the pair traversal, 64 rays per wave (BVH when its node image does not fit) */
+} hrt_query_method;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -251,6 +284,15 @@ HRT_STATIC_ASSERT(sizeof(hrt_fold_record) == 24 && offsetof(hrt_fold_record, max
 HRT_STATIC_ASSERT(sizeof(hrt_settle_rule) == 16 && offsetof(hrt_settle_rule, quiet_frames) == 8 &&
                       offsetof(hrt_settle_rule, flags) == 12,
                   "hrt_settle_rule");
+HRT_STATIC_ASSERT(sizeof(hrt_ray_query) == 32 && offsetof(hrt_ray_query, t_max) == 12 &&
+                      offsetof(hrt_ray_query, direction) == 16 && offsetof(hrt_ray_query, reserved) == 28,
+                  "hrt_ray_query");
+HRT_STATIC_ASSERT(sizeof(hrt_hit) == 32 && offsetof(hrt_hit, kind) == 4 && offsetof(hrt_hit, index) == 8 &&
+                      offsetof(hrt_hit, mesh) == 12 && offsetof(hrt_hit, normal) == 16 && offsetof(hrt_hit, reserved) == 28,
+                  "hrt_hit");
+HRT_STATIC_ASSERT(sizeof(hrt_query_stats) == 24 && offsetof(hrt_query_stats, scan_rays) == 8 &&
+                      offsetof(hrt_query_stats, tri_tests) == 16,
+                  "hrt_query_stats");
 
 typedef struct hrt_context hrt_context;
 
@@ -485,6 +527,28 @@ hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame);
  * per-pixel sample chains of one frame run beside the other frames' work instead of ending each
  * frame alone; the combiner then folds the frames in order.  pc->init must be 0. */
 hrt_status hrt_compute_n(hrt_context* ctx, const hrt_push_constants* pc, uint32_t n);
+
+/* Closest hit of caller rays: hits[i] = the reference's world_hit (raytracing.glsl:267-288) of rays[i] against
+ * the uploaded scene (all its spheres and meshes), by DESIGN.md §2 S11: the direction normalised by S4, the
+ * running closest started at min(t_max, FLT_MAX), spheres first, then meshes in buffer order behind the
+ * reference's AABB test, a hit accepted iff dist > 0.001 and dist < the running closest.  Every method gives
+ * the same bytes.  BLOCKING; ordered on the context's stream after the work issued so far; touches no trace
+ * lane, image, hrt_stats, fold record or ticket.  rays / hits: host memory (staged in chunks) or memory of
+ * the context's device (then 16-byte aligned), each decided by hipPointerGetAttributes.  stats may be NULL.
+ * n == 0: OK, nothing done.  HRT_ERR_INVALID_ARGUMENT (unknown method, NULL rays / hits with n > 0, a
+ * misaligned device pointer) and HRT_ERR_NO_SCENE are decided before anything is enqueued. */
+hrt_status hrt_intersect(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n, uint32_t method, hrt_hit* hits,
+                         hrt_query_stats* stats);
+
+/* The same for the un-jittered primary rays of the pixels [x0, x0 + w) x [y0, y0 + h) (global pixel
+ * coordinates of pc's camera; trace-image rows: the present pass flips them): origin pc->cam_pos, direction
+ * normalize(mat3(pc->cam_alignment_mat) c) with c the context's ray centre of pixel x + y W (the row-wise
+ * product of get_ray_dir, zero jitter, no RNG draw), t_max = FLT_MAX, pc's sphere and mesh counts (validated
+ * as hrt_trace validates them).  hits receives w h records, row-major.  Works on any context (a row-tile part
+ * holds every ray centre); not a collective.  An empty rectangle: OK, nothing done; one outside the image:
+ * HRT_ERR_INVALID_ARGUMENT. */
+hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_constants* pc, uint32_t x0, uint32_t y0,
+                                 uint32_t w, uint32_t h, uint32_t method, hrt_hit* hits, hrt_query_stats* stats);
 
 /* The records of the newest min(cap, available) folds (HRT_OPT_FOLD_RECORDS = 1), oldest first; the ring
  * keeps the last HRT_FOLD_RECORD_RING.  Folds deferred combines and synchronizes the context, as

@@ -378,6 +378,20 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
     const hrt_push_constants pc = push_constants(Camera{}, 0u, true);
     check(hrt_trace(ctx_->get(), &pc), "hrt_trace", ctx_->get());
   }
+  // Ray queries (hrt_intersect_primary; not a reference feature).  The closest hit of the un-jittered primary
+  // ray of every pixel of the rectangle [x0, x0 + w) x [y0, y0 + h) (the whole image by default), row-major,
+  // in trace-image rows (the present pass shows them flipped).
+  std::vector<hrt_hit> first_hits(const Camera& camera, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                  uint32_t method = HRT_QUERY_AUTO) const {
+    const hrt_push_constants pc = push_constants(camera, 0u, false);
+    std::vector<hrt_hit> hits((size_t)w * h);
+    check(hrt_intersect_primary(ctx_->get(), &pc, x0, y0, w, h, method, hits.data(), nullptr), "hrt_intersect_primary",
+          ctx_->get());
+    return hits;
+  }
+  std::vector<hrt_hit> first_hits(const Camera& camera) const { return first_hits(camera, 0, 0, size_[0], size_[1]); }
+  // What lies under pixel (x, y) of the view (trace-image coordinates: row height - 1 - y of a presented target).
+  hrt_hit pick(const Camera& camera, uint32_t x, uint32_t y) const { return first_hits(camera, x, y, 1, 1)[0]; }
   Context& context() const { return *ctx_; }
   std::array<uint32_t, 2> image_size() const { return size_; }
 
