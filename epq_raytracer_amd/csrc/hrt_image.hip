@@ -48,10 +48,26 @@ __device__ __forceinline__ float4 combine_rgba32f(float4 p, float4 n, uint32_t f
 // Markstein's correction gives the correctly rounded quotient; a zero numerator gives +0 as the IEEE
 // division does).  The reference spelling is the oracle's (orc_accumulate_rgba8: unorm8((nc + prev * ff) /
 // ff1) per channel); tests/test_gpu_parity.py holds every accumulator to it.
+// Domain: every uint32_t frame.  ff1 is 0 or in [1, 2^32]: frames 1 .. 2^32 - 2 take the shared reciprocal
+// (tests/test_gpu_image_exhaustive.py enumerates all 65,536 channel pairs over frames 0 .. 1199 and the edges
+// 2^24 +- 1, 2^31, 2^32 - 3 .. 2^32 - 1 on the device).  At frame 2^32 - 1, frame + 1 wraps to 0 and
+// rcp_core(0) = fma(fma(-0, inf, 1), inf, inf) is NaN where the reference divides by zero (+inf, stored as
+// 255, for a nonzero numerator; NaN, stored as 0, for 0 / 0): that frame -- any ff1 outside rcp_core's
+// range -- takes the IEEE '/' spelling.  The branch is workgroup-uniform (frame is a kernel argument).
 __device__ __forceinline__ uint32_t combine_rgba8_fast(uint32_t pv, uint32_t nv, uint32_t frame, const float* tab) {
   if (frame == 0) return 255u << 24;
-  const float ff = (float)frame, ff1 = (float)(frame + 1u), y = rcp_core(ff1);
+  const float ff = (float)frame, ff1 = (float)(frame + 1u);
   uint32_t out = 255u << 24;
+  if (__builtin_expect(!(ff1 >= 0x1p-40f && ff1 <= 0x1p40f), 0)) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float prev = tab[(pv >> (8 * ch)) & 255u];
+      const float nc = tab[(nv >> (8 * ch)) & 255u];
+      out |= unorm8((nc + prev * ff) / ff1) << (8 * ch);
+    }
+    return out;
+  }
+  const float y = rcp_core(ff1);
 #pragma unroll
   for (int ch = 0; ch < 3; ++ch) {
     const float prev = tab[(pv >> (8 * ch)) & 255u];

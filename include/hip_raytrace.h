@@ -516,7 +516,10 @@ hrt_status hrt_set_scene(hrt_context* ctx, const hrt_ray* rays, uint32_t n_rays,
  * equal the context's; pc->num_spheres/num_meshes must not exceed the uploaded counts. */
 hrt_status hrt_trace(hrt_context* ctx, const hrt_push_constants* pc);
 
-/* One dispatch of image_combiner.glsl with next_image = this context's trace image. */
+/* One dispatch of image_combiner.glsl with next_image = this context's trace image.  Any uint32_t frame
+ * is folded as the shader's arithmetic folds it: frame 0 clears, and at frame 0xFFFFFFFF, whose frame + 1
+ * wraps to 0, the division is IEEE's division by zero (a channel with a nonzero numerator becomes 255,
+ * 0 / 0 becomes 0). */
 hrt_status hrt_accumulate(hrt_context* ctx, uint32_t frame);
 
 /* The frame loop of compute_n_then_render (src/raytracing_app.rs:198-227, without the present):
