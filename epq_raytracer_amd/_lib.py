@@ -146,6 +146,7 @@ OPT_SPLIT, OPT_SPLIT_FACTOR, OPT_PRIORITY, OPT_GRID_CUS, OPT_COOP, OPT_WQ_NODE_C
 OPT_FRAMES_PER_LAUNCH, OPT_OVERLAP, OPT_BUSY_SPLIT, OPT_BVH_WIDTH, OPT_WQ_NODE_RADIUS = 12, 13, 14, 15, 16
 OPT_COMM_TIMEOUT_MS, OPT_DEFER_COMBINE, OPT_FOLD_RECORDS = 17, 18, 19
 OPT_SKY_LANE = 20  # BUNDLE_WQ: sky items on trace_sky beside the main kernel (-1 auto, 0 off, 1 on)
+OPT_WQ_LDS_NODES = 21  # BUNDLE_WQ_L2: nodes of the breadth-first image kept in LDS (-1 auto, 0 none, n)
 DEBUG_OPT_FAIL_ALLOC = 1001  # libhip_raytrace_debug.so only
 DEBUG_OPT_WQ_TRI_CAP = 1002  # libhip_raytrace_debug.so only
 DEBUG_OPT_GRAB_RUNS = 1003  # libhip_raytrace_debug.so only
@@ -156,6 +157,7 @@ COMM_NONE, COMM_RCCL, COMM_RCCL_GROUP, COMM_DEVICE_COPY = 0, 1, 2, 3
 # hrt_kernel (include/hip_raytrace.h)
 KERNEL_AUTO, KERNEL_LITERAL, KERNEL_BRUTE, KERNEL_BRUTE_LDS, KERNEL_BUNDLE, KERNEL_BUNDLE_CULL = 0, 1, 2, 3, 4, 5
 KERNEL_BUNDLE_BVH, KERNEL_BUNDLE_CULL_LDS, KERNEL_BUNDLE_BVH_LDS, KERNEL_BUNDLE_WQ = 6, 7, 8, 9
+KERNEL_BUNDLE_WQ_L2 = 10  # BUNDLE_WQ with the node image in global memory / L2 (never picked by AUTO)
 # kernel symbol (as rocprofv3 names it) of a resolved hrt_kernel + workgroup size
 NODE_RADIUS_MARGIN_MILLI = 100  # auto HRT_OPT_WQ_NODE_RADIUS: per-node R above this bvh_margin_milli (hrt_bvh.h)
 
@@ -169,17 +171,19 @@ def kernel_symbol(kernel: int, block: int, diag: bool = False, node_r: bool = Fa
     d = "true" if diag else "false"
     if kernel == 9 and node_r:
         return f"void hrt::trace_bundle_wq_nr<{d}>(hrt::TraceParams)"
+    if kernel == 10 and node_r:
+        return f"void hrt::trace_bundle_wq_l2_nr<{d}>(hrt::TraceParams)"
     if kernel in (1, 2, 3):
         return "hrt::" + {1: "trace_literal", 2: "trace_brute", 3: "trace_brute_lds"}[kernel] + "(hrt::TraceParams)"
     if kernel == 7:
         return f"void hrt::trace_bundle_cull_lds<{block}, {d}>(hrt::TraceParams)"
     name = {4: "trace_bundle", 5: "trace_bundle_cull", 6: "trace_bundle_bvh", 8: "trace_bundle_bvh_lds",
-            9: "trace_bundle_wq"}.get(kernel, "?")
+            9: "trace_bundle_wq", 10: "trace_bundle_wq_l2"}.get(kernel, "?")
     return f"void hrt::{name}<{d}>(hrt::TraceParams)"
 
 
 KERNEL_NAMES = {0: "auto", 1: "literal", 2: "brute", 3: "brute_lds", 4: "bundle", 5: "bundle_cull", 6: "bundle_bvh",
-                7: "bundle_cull_lds", 8: "bundle_bvh_lds", 9: "bundle_wq"}
+                7: "bundle_cull_lds", 8: "bundle_bvh_lds", 9: "bundle_wq", 10: "bundle_wq_l2"}
 DIAG_NAMES = ("primary_iters", "primary_considered", "primary_survivors", "bounce_iters", "bounce_considered",
               "bounce_survivors", "bounce_lanes", "bvh_visits", "bvh_prim_tests", "bvh_band_tests", "primary_cycles", "bounce_cycles",
               "shade_cycles", "bounce_stage2", "bounce_front", "bvh_trips",
@@ -201,7 +205,7 @@ EXPORTED_SYMBOLS = (
     "hrt_debug_tile_lists",
     "hrt_stream", "hrt_release_caches", "hrt_last_error", "hrt_comm_unique_id", "hrt_comm_init", "hrt_comm_init_all", "hrt_comm_info",
     "hrt_host_create_rays", "hrt_host_ray_grid", "hrt_host_view_matrix", "hrt_host_transform_meshes",
-    "hrt_debug_bvh_build", "hrt_debug_bvh_wq_nodes",
+    "hrt_debug_bvh_build", "hrt_debug_bvh_wq_nodes", "hrt_debug_bvh_wq_nodes_bfs", "hrt_debug_wq_l2_plan",
     "hrt_obj_load", "hrt_obj_num_meshes", "hrt_obj_mesh", "hrt_obj_free",
 )
 
@@ -287,6 +291,8 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_debug_bvh_build": (c_int32, [P, c_uint32, P, c_uint32, c_uint32, P, P, c_uint64, P, c_uint64, P,
                                           c_uint64, P, c_uint64, P, c_uint64]),
         "hrt_debug_bvh_wq_nodes": (c_int64, [P, c_uint32, P, c_uint32, c_uint32, c_uint32, P, c_uint64]),
+        "hrt_debug_bvh_wq_nodes_bfs": (c_int64, [P, c_uint32, P, c_uint32, c_uint32, c_uint32, P, c_uint64]),
+        "hrt_debug_wq_l2_plan": (None, [c_uint32, c_uint32, c_uint32, c_int64, P]),
         "hrt_host_ray_grid": (c_uint32, [c_uint32, c_uint32, c_float, c_float, POINTER(c_float), POINTER(c_float),
                                          POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
         "hrt_set_option": (c_int32, [P, c_uint32, c_int64]),

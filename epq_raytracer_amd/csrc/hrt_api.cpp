@@ -236,6 +236,7 @@ void free_scene(hrt_context* ctx, SceneBufs& s, bool keep_rays) {
   free_dev(ctx, s.meshes);
   free_dev(ctx, s.bvh_nodes);
   free_dev(ctx, s.bvh_wq_nodes);
+  free_dev(ctx, s.bvh_wq_nodes_bfs);
   free_dev(ctx, s.bvh_prims);
   free_dev(ctx, s.bvh_irregular);
   free_dev(ctx, s.bvh_band_off);
@@ -258,6 +259,12 @@ using hrt::hip_fail;
 using hrt::bind;
 
 extern "C" uint32_t hrt_abi_version(void) { return HRT_ABI_VERSION; }
+
+// Host only: BUNDLE_WQ_L2's LDS plan (hrt_kernels.hip wq_l2_plan) with no stack-capacity requests.
+extern "C" void hrt_debug_wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes,
+                                     uint32_t out[4]) {
+  hrt::wq_l2_plan(n_nodes, width, max_leaf, lds_nodes, 0u, 0u, out);
+}
 
 extern "C" hrt_status hrt_debug_check_guards(hrt_context* ctx, uint32_t* buffers, uint32_t* corrupted) {
   if (!ctx || !buffers || !corrupted) return HRT_ERR_INVALID_ARGUMENT;
@@ -615,6 +622,12 @@ hrt_status build_scene(hrt_context* ctx, hrt::SceneBufs& s, const hrt_ray* rays,
     };
     if ((st = up(s.bvh_nodes, bvh.nodes, "bvh nodes")) != HRT_OK) return st;
     if (bvh.wq_ok && (st = up(s.bvh_wq_nodes, bvh.wq_nodes, "bvh wq nodes")) != HRT_OK) return st;
+    // BUNDLE_WQ_L2's image: on the device only for a context that has selected the variant (a later
+    // hrt_set_option uploads the host copy, upload_wq_bfs)
+    if (bvh.wq_ok && ctx->variant == HRT_KERNEL_BUNDLE_WQ_L2 && !bvh.wq_nodes_bfs.empty() &&
+        (st = up(s.bvh_wq_nodes_bfs, bvh.wq_nodes_bfs, "bvh wq nodes (breadth first)")) != HRT_OK)
+      return st;
+    if (bvh.wq_ok) s.wq_bfs_host = std::move(bvh.wq_nodes_bfs);
     if ((st = up(s.bvh_prims, bvh.prims, "bvh prims")) != HRT_OK ||
         (st = up(s.bvh_irregular, bvh.irregular, "bvh irregular")) != HRT_OK ||
         (st = up(s.bvh_band_off, bvh.band_off, "band offsets")) != HRT_OK ||
@@ -670,6 +683,27 @@ hrt_status build_scene(hrt_context* ctx, hrt::SceneBufs& s, const hrt_ray* rays,
   s.n_tris = n_tris;
   s.n_meshes = n_meshes;
   HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));  // host arrays are only borrowed
+  return HRT_OK;
+}
+
+// HRT_OPT_KERNEL_VARIANT = BUNDLE_WQ_L2 on a context whose scene is already set: the breadth-first image's upload.
+hrt_status upload_wq_bfs(hrt_context* ctx) {
+  hrt::SceneBufs& s = ctx->scene;
+  if (!ctx->scene_set || s.bvh_wq_nodes_bfs || s.wq_bfs_host.empty()) return HRT_OK;
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  void* dst = nullptr;
+  const size_t bytes = s.wq_bfs_host.size() * sizeof(float);
+  if (hipError_t e = hrt::dev_alloc(ctx, &dst, bytes); e != hipSuccess)
+    return hip_fail(ctx, e, "hrt_set_option: hipMalloc(bvh wq nodes, breadth first)");
+  st = stage_upload(ctx, dst, s.wq_bfs_host.data(), bytes);
+  if (st == HRT_OK && hipStreamSynchronize(ctx->stream) != hipSuccess)
+    st = fail(ctx, HRT_ERR_HIP, "hrt_set_option: upload of the breadth-first node image");
+  if (st != HRT_OK) {
+    hrt::dev_free(ctx, dst);
+    return st;
+  }
+  s.bvh_wq_nodes_bfs = static_cast<float4*>(dst);
   return HRT_OK;
 }
 
@@ -780,6 +814,8 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   p.bvh_wq_nodes = built ? s.bvh_wq_nodes : nullptr;
   p.bvh_wq_n_nodes = s.bvh_wq_n;
   p.bvh_wq_width = s.bvh_wq_width;
+  p.bvh_wq_nodes_bfs = built ? s.bvh_wq_nodes_bfs : nullptr;
+  p.wq_lds_nodes_opt = ctx->wq_lds_nodes;
   p.bvh_prims = s.bvh_prims;
   p.bvh_irregular = s.bvh_irregular;
   p.bvh_band_off = s.bvh_band_off;
@@ -809,7 +845,8 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
 }
 
 bool persistent_kernel(int k) {
-  return k == HRT_KERNEL_BUNDLE_WQ || k == HRT_KERNEL_BUNDLE_CULL_LDS || k == HRT_KERNEL_BUNDLE_BVH_LDS;
+  return k == HRT_KERNEL_BUNDLE_WQ || k == HRT_KERNEL_BUNDLE_WQ_L2 || k == HRT_KERNEL_BUNDLE_CULL_LDS ||
+         k == HRT_KERNEL_BUNDLE_BVH_LDS;
 }
 // The kernels whose launch (re)builds the lane's camera lists (launch_trace runs camera_lists before
 // them); LITERAL, BRUTE and BRUTE_LDS neither build nor read the lists.
@@ -1918,8 +1955,10 @@ extern "C" hrt_status hrt_set_option(hrt_context* ctx, uint32_t key, int64_t val
   if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
   switch (key) {
     case HRT_OPT_KERNEL_VARIANT:
-      if (value < HRT_KERNEL_AUTO || value > HRT_KERNEL_BUNDLE_WQ)
-        return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "kernel variant must be an hrt_kernel value (0..9)");
+      if (value < HRT_KERNEL_AUTO || value > HRT_KERNEL_BUNDLE_WQ_L2)
+        return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "kernel variant must be an hrt_kernel value (0..10)");
+      if (value == HRT_KERNEL_BUNDLE_WQ_L2)  // its node image, unless the scene's is already on the device
+        if (hrt_status st = upload_wq_bfs(ctx); st != HRT_OK) return st;
       ctx->variant = (int)value;
       return HRT_OK;
     case HRT_OPT_COUNTERS:
@@ -1993,6 +2032,11 @@ extern "C" hrt_status hrt_set_option(hrt_context* ctx, uint32_t key, int64_t val
     case HRT_OPT_WQ_NODE_RADIUS:
       if (value < 0 || value > 2) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "wq node radius must be 0 (auto), 1 or 2");
       ctx->wq_node_radius = (uint32_t)value;
+      return HRT_OK;
+    case HRT_OPT_WQ_LDS_NODES:
+      if (value < -1 || value > (1 << 20))
+        return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "wq lds nodes must be -1 (auto) or in [0, 2^20]");
+      ctx->wq_lds_nodes = (int32_t)value;
       return HRT_OK;
     case HRT_OPT_SKY_LANE:
       if (value < -1 || value > 1) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "sky lane must be -1 (auto), 0 or 1");

@@ -544,6 +544,47 @@ bool make_wq_nodes(const BvhHost& b, std::vector<float>& out, uint32_t width, ui
   return true;
 }
 
+bool make_wq_nodes_bfs(const std::vector<float>& in, uint32_t n, std::vector<float>& out) {
+  out.clear();
+  if (n == 0 || n >= 0x10000u || in.size() != (size_t)n * 12) return false;
+  auto word = [&](uint32_t k, int j) {
+    uint32_t u;
+    std::memcpy(&u, &in[(size_t)k * 12 + j], 4);
+    return u;
+  };
+  // old_of[new slot] = old slot, in breadth-first order of the groups; new_of is its inverse
+  std::vector<uint32_t> new_of(n, ~0u), old_of;
+  old_of.reserve(n);
+  new_of[0] = 0;
+  old_of.push_back(0);
+  for (size_t i = 0; i < old_of.size(); ++i) {
+    const uint32_t inf = word(old_of[i], 11);
+    if (inf >> 27) continue;  // leaf
+    const uint32_t fc = inf & 0xFFFFu, cnt = (inf >> 16) + 1u;
+    for (uint32_t j = 0; j < cnt; ++j) {
+      if (fc + j >= n || new_of[fc + j] != ~0u || old_of.size() >= n) return false;  // not a tree of n nodes
+      new_of[fc + j] = (uint32_t)old_of.size();
+      old_of.push_back(fc + j);
+    }
+  }
+  if (old_of.size() != n) return false;
+  out.resize((size_t)n * 12);
+  for (uint32_t s = 0; s < n; ++s) {
+    const uint32_t k = old_of[s];
+    std::memcpy(&out[(size_t)s * 12], &in[(size_t)k * 12], 48);
+    const uint32_t w10 = word(k, 10), esc = w10 >> 16, inf = word(k, 11);
+    if (esc != n && (esc > n || new_of[esc] == ~0u)) {
+      out.clear();
+      return false;
+    }
+    uint32_t u[2];
+    u[0] = (w10 & 0xFFFFu) | (esc == n ? n : new_of[esc]) << 16;
+    u[1] = (inf >> 27) ? inf : (new_of[inf & 0xFFFFu] | (inf & 0xFFFF0000u));
+    std::memcpy(&out[(size_t)s * 12 + 10], u, 8);
+  }
+  return true;
+}
+
 bool build_bvh(const hrt_triangle* tris, uint32_t n_tris, const hrt_mesh* meshes, uint32_t n_meshes,
                uint32_t leaf_size, BvhHost& out, uint32_t wq_width, float band_tau, bool bands) {
   out = BvhHost{};
@@ -655,6 +696,8 @@ bool build_bvh(const hrt_triangle* tris, uint32_t n_tris, const hrt_mesh* meshes
   out.abs_coef = round_up(2.1 * (4.2 * e + out.rho_max) * inv_tp * (1.0 + 1e-6));
   out.rel_t = round_up((2.1 * (3.2 * e + out.rho_max) * inv_tp + 4 * e) * (1.0 + 1e-6));
   out.wq_ok = make_wq_nodes(out, out.wq_nodes, wq_width, &out.wq_n_nodes, &out.wq_width);
+  // (host only, at most 3 MB: uploaded for the contexts that select BUNDLE_WQ_L2, hrt_api.cpp)
+  if (out.wq_ok && out.wq_n_nodes) make_wq_nodes_bfs(out.wq_nodes, out.wq_n_nodes, out.wq_nodes_bfs);
   return true;
 }
 
@@ -762,4 +805,18 @@ extern "C" int64_t hrt_debug_bvh_wq_nodes(const hrt_triangle* tris, uint32_t n_t
   if (!out || cap < b.wq_nodes.size()) return -1;
   std::memcpy(out, b.wq_nodes.data(), b.wq_nodes.size() * sizeof(float));
   return (int64_t)(b.wq_nodes.size() / 12);
+}
+
+// ... and the breadth-first image of the same hierarchy (BUNDLE_WQ_L2, make_wq_nodes_bfs)
+extern "C" int64_t hrt_debug_bvh_wq_nodes_bfs(const hrt_triangle* tris, uint32_t n_tris, const hrt_mesh* meshes,
+                                              uint32_t n_meshes, uint32_t leaf_size, uint32_t width, float* out,
+                                              uint64_t cap) {
+  hrt::BvhHost b;
+  // (without the grazing-band lists, most of a build's time: the image does not depend on them)
+  if (!hrt::build_bvh(tris, n_tris, meshes, n_meshes, leaf_size, b, width, hrt::kBandTau, false) || !b.wq_ok ||
+      b.wq_nodes_bfs.empty())
+    return 0;
+  if (!out || cap < b.wq_nodes_bfs.size()) return -1;
+  std::memcpy(out, b.wq_nodes_bfs.data(), b.wq_nodes_bfs.size() * sizeof(float));
+  return (int64_t)(b.wq_nodes_bfs.size() / 12);
 }

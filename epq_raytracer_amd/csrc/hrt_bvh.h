@@ -50,6 +50,7 @@ struct BvhHost {
   bool wq_ok = false;               // the image exists (fewer than 65536 nodes)
   uint32_t wq_n_nodes = 0;          // its nodes (the binary nodes a group collapse keeps)
   uint32_t wq_width = 2;            // its largest group (children tested per node pop)
+  std::vector<float> wq_nodes_bfs;  // the same image with its groups allocated level by level (make_wq_nodes_bfs)
   uint32_t n_nodes = 0, n_prims = 0, n_irregular = 0, n_never = 0;  // never = zero normal (dn == 0)
   double rho_max = 0.0;
   float abs_coef = 0.0f, rel_t = 0.0f;  // box-test t-slack: [-abs_coef R, best (1 + rel_t) + abs_coef R]
@@ -125,6 +126,13 @@ constexpr float kWqAxisErr = 5e-4f;  // >= sqrt(3) 2^-12: bound on |d.axis_16 - 
 constexpr uint32_t kWqMaxWidth = 4;  // widest group an image may have (HRT_OPT_BVH_WIDTH; the kernel's slots)
 constexpr uint32_t kWqDefaultWidth = 4;
 bool make_wq_nodes(const BvhHost& b, std::vector<float>& out, uint32_t width, uint32_t* n_out, uint32_t* w_out);
+// BUNDLE_WQ_L2's image: the records and groups of an image of n nodes made by make_wq_nodes, with the groups
+// allocated breadth first (in the order their parents are stored, the root's group first), so that the
+// slots below any L are the nodes nearest the root -- the ones the kernel keeps in LDS while the rest is
+// read from global memory.  A group stays contiguous, the root stays at 0, words 0..9 and the sin^2
+// half-word are copied, and the child (word 11 of an inner node) and escape (word 10 >> 16) slots are
+// rewritten; the escape of the walk's end stays n.  False (out empty) when `in` is not a whole image.
+bool make_wq_nodes_bfs(const std::vector<float>& in, uint32_t n, std::vector<float>& out);
 
 // Builds the hierarchy over every (mesh, triangle) entry of the scene.  Returns false (and leaves
 // `out` empty) when the scene has more than kBvhMaxMeshes meshes, kBvhMaxEntries entries or 2^26

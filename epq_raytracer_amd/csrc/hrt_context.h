@@ -51,6 +51,10 @@ struct SceneBufs {
   hrt_mesh* meshes = nullptr;
   float4* bvh_nodes = nullptr;     // BUNDLE_BVH hierarchy (hrt_bvh.h)
   float4* bvh_wq_nodes = nullptr;  // its 48 B node image for BUNDLE_WQ (nullptr above 65535 nodes)
+  // BUNDLE_WQ_L2's breadth-first image: kept on the host (at most 3 MB) and uploaded only for a context that
+  // selects the variant -- by hrt_set_scene when the option is already set, else by the hrt_set_option that sets it
+  float4* bvh_wq_nodes_bfs = nullptr;
+  std::vector<float> wq_bfs_host;
   float4* bvh_prims = nullptr;
   float4* bvh_irregular = nullptr;
   uint32_t* bvh_band_off = nullptr;
@@ -143,6 +147,7 @@ struct hrt_context {
   uint32_t num_cus = 0;
   uint32_t bvh_leaf = 0;  // HRT_OPT_BVH_LEAF_SIZE for the next hrt_set_scene (0 = auto, hrt_bvh.h)
   uint32_t wq_node_radius = 0;  // HRT_OPT_WQ_NODE_RADIUS (0 = auto)
+  int32_t wq_lds_nodes = -1;    // HRT_OPT_WQ_LDS_NODES (-1 = auto)
   int32_t sky_lane = -1;        // HRT_OPT_SKY_LANE (-1 = auto)
   uint32_t bvh_width = 4;  // HRT_OPT_BVH_WIDTH (hrt_bvh.h kWqDefaultWidth) for the next hrt_set_scene
   int64_t debug_fail_alloc = 0;   // debug build: fail the n-th device allocation of the next hrt_set_scene

@@ -96,6 +96,12 @@ struct TraceParams {
   uint32_t split_factor4;   // (host side, launch_trace) the heavy threshold in quarters of a wave's share; 0: split_factor
   unsigned long long* sky_units;  // the work units (tile x frame) trace_sky has run (hrt_debug_sky_units)
   uint32_t sky_lane;        // (launch_trace) this launch's plan ends in its sky items and trace_sky runs beside the main kernel
+  // BUNDLE_WQ_L2: the breadth-first node image (hrt_bvh.h make_wq_nodes_bfs; bvh_wq_n_nodes records), uploaded for
+  // the contexts that select the variant, else nullptr; the HRT_OPT_WQ_LDS_NODES request (-1: auto); and the slots
+  // the launch keeps in LDS (launch_trace, wq_l2_plan)
+  const float4* bvh_wq_nodes_bfs;
+  int32_t wq_lds_nodes_opt;
+  uint32_t wq_lds_nodes;
 };
 // The sky lane of a trace lane (HRT_OPT_SKY_LANE): the side stream trace_sky runs on and the events a
 // launch forks to it and joins it back with.
@@ -139,6 +145,9 @@ hipError_t launch_wq_protocol_check(uint32_t rounds, const uint32_t* cnt, const 
 // BUNDLE_WQ's per-wave node-stack capacity for an image of n_nodes records with groups of `width` and
 // leaves of at most max_leaf triangles (0: does not fit the LDS)
 uint32_t wq_stack_cap(uint32_t n_nodes, uint32_t width, uint32_t max_leaf);
+// BUNDLE_WQ_L2's LDS plan (hrt_kernels.hip): out = {nodes kept in LDS, node pair stack, triangle pair stack, bytes}
+void wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes, uint32_t ncap_req,
+                uint32_t tcap_req, uint32_t out[4]);
 // Ray queries (hrt_intersect / hrt_intersect_primary): the query kernels' own arguments,
 // passed after the TraceParams block (world_hit_bounce_wq reads its constants through the kernarg
 // segment's start).  One ray per lane: ray i of the launch is rays[2 i], rays[2 i + 1] (hrt_ray_query),

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "hip_raytrace.h"
@@ -1636,6 +1637,37 @@ __device__ __forceinline__ uint32_t wq_info(const float4* nodes, uint32_t k) {  
 __device__ __forceinline__ uint32_t wq_escape(const float4* nodes, uint32_t k) {
   return __builtin_bit_cast(uint32_t, nodes[3 * k + 2].z) >> 16;
 }
+
+// The traversal's node source.  BUNDLE_WQ (WqLds): every record in the LDS copy.  BUNDLE_WQ_L2 (WqL2): the
+// breadth-first image (hrt_bvh.h make_wq_nodes_bfs), slots below nl -- the top of the tree -- in the LDS
+// copy, the others read from global memory (one XCD's L2 holds the whole 3 MB of the largest image).  The
+// choice is per node: a group may straddle nl.  The global image is addressed as address space 1, so its
+// records are fetched with global_load_dwordx4 / global_load_dword (a generic pointer, or one selected
+// between the two sources, would make every node read a flat load; profiles/wq_l2_resources.txt).
+typedef float wq_v4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) wq_v4* WqGlobalNodes;
+typedef const __attribute__((address_space(1))) uint32_t* WqGlobalWords;
+struct WqL2 : WqLds {
+  WqGlobalNodes gnodes;  // TraceParams::bvh_wq_nodes_bfs
+  uint32_t nl;           // slots kept in LDS (TraceParams::wq_lds_nodes; 0: none)
+};
+struct WqRec {
+  float4 a, b, c;
+};
+__device__ __forceinline__ float4 wq_f4(wq_v4 v) { return make_float4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ WqRec wq_rec(const WqL2& wq, uint32_t k) {
+  if (k < wq.nl) {
+    const float4* p = wq.nodes + 3 * k;
+    return WqRec{p[0], p[1], p[2]};
+  }
+  const WqGlobalNodes p = wq.gnodes + 3 * k;
+  return WqRec{wq_f4(p[0]), wq_f4(p[1]), wq_f4(p[2])};
+}
+__device__ __forceinline__ uint32_t wq_word(const WqL2& wq, uint32_t k, uint32_t j) {  // word j of slot k's record
+  if (k < wq.nl) return __builtin_bit_cast(uint32_t, reinterpret_cast<const float*>(wq.nodes)[12 * k + j]);
+  return reinterpret_cast<WqGlobalWords>(wq.gnodes)[12 * k + j];
+}
+__device__ __forceinline__ uint32_t wq_escape(const WqL2& wq, uint32_t k) { return wq_word(wq, k, 10u) >> 16; }
 // compare-exchange of two pushed-child slots: the smaller key (the farther child) first
 __device__ __forceinline__ void wq_order(float& ka, uint32_t& ea, float& kb, uint32_t& eb) {
   const bool sw = kb < ka;
@@ -1878,9 +1910,12 @@ __device__ __forceinline__ void band_cell(const KArgs K, f3 d, uint32_t& b0, uin
   }
 }
 
-template <bool D, bool NodeR>
-__device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const TraceParams& P, const WqLds& wq, bool sec,
+template <bool D, bool NodeR, class Src>
+__device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const TraceParams& P, const Src& wq, bool sec,
                                                     f3 o, f3 d, uint32_t& tests, Closest& c, Diag& dg) {
+  // (every node read below has two arms: the LDS image's statements as they were -- BUNDLE_WQ's kernels are
+  // the code they were before the second source -- and the source's accessors)
+  constexpr bool kL2 = std::is_same<Src, WqL2>::value;
   const hrt_push_constants& pc = P.pc;
   const uint32_t lane = threadIdx.x & 63;
   // the batch's constants, read here (kargs): live for the batch only
@@ -1909,7 +1944,15 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
     if (sec) bvh_prim_test(irr, k, mask, o, d, c, bkey, best_k);
   float R;
   {  // farthest root-box corner from the origin, rounded up
-    const float4 R0 = wq.nodes[0], R1 = wq.nodes[1];
+    float4 R0, R1;
+    if constexpr (kL2) {
+      const WqRec rr = wq_rec(wq, 0);
+      R0 = rr.a;
+      R1 = rr.b;
+    } else {
+      R0 = wq.nodes[0];
+      R1 = wq.nodes[1];
+    }
     const float fx = fmaxf(fabsf(o.x - R0.x), fabsf(R1.x - o.x)), fy = fmaxf(fabsf(o.y - R0.y), fabsf(R1.y - o.y));
     const float fz = fmaxf(fabsf(o.z - R0.z), fabsf(R1.z - o.z));
     R = __builtin_amdgcn_sqrtf(fx * fx + fy * fy + fz * fz) * 1.0001f;  // 1 ulp, inside the x1.0001
@@ -2013,8 +2056,14 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   bool rvis = false;
   if (sec && mask) {
     float tn;
-    rinfo = wq_info(wq.nodes, 0);
-    rvis = wq_node_visit(wq.nodes, o, d, inv, R, abs_t, c.t * (1.0f + rel_t) + abs_t, tn);
+    if constexpr (kL2) {
+      const WqRec rr = wq_rec(wq, 0);
+      rinfo = __builtin_bit_cast(uint32_t, rr.c.w);
+      rvis = wq_node_visit_r(rr.a, rr.b, rr.c, o, d, inv, R, abs_t, c.t * (1.0f + rel_t) + abs_t, tn);
+    } else {
+      rinfo = wq_info(wq.nodes, 0);
+      rvis = wq_node_visit(wq.nodes, o, d, inv, R, abs_t, c.t * (1.0f + rel_t) + abs_t, tn);
+    }
   }
   const uint32_t rcnt = rvis ? rinfo >> 27 : 0u;
   const unsigned long long rb = __ballot(rvis && rcnt == 0u);
@@ -2076,9 +2125,15 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
         // the first member pair's records are requested before the slot read: that read is an atomic
         // (lds_get), which the scheduler keeps every other memory access on its side of, so requested
         // after it they waited for the ray shuffles and the slot before being issued
-        const float4* na0 = wq.nodes + 3 * fc;
-        const float4* nb0 = wq.nodes + 3 * (fc + min(1u, gcnt - 1u));
-        const float4 A00 = na0[0], A01 = na0[1], A02 = na0[2], B00 = nb0[0], B01 = nb0[1], B02 = nb0[2];
+        float4 A00, A01, A02, B00, B01, B02;
+        if constexpr (kL2) {
+          const WqRec ra0 = wq_rec(wq, fc), rb0 = wq_rec(wq, fc + min(1u, gcnt - 1u));
+          A00 = ra0.a, A01 = ra0.b, A02 = ra0.c, B00 = rb0.a, B01 = rb0.b, B02 = rb0.c;
+        } else {
+          const float4* na0 = wq.nodes + 3 * fc;
+          const float4* nb0 = wq.nodes + 3 * (fc + min(1u, gcnt - 1u));
+          A00 = na0[0], A01 = na0[1], A02 = na0[2], B00 = nb0[0], B01 = nb0[1], B02 = nb0[2];
+        }
         // (both pairs up front: 24 more live VGPRs, scratch 92 -> 160 B with spills in the fused loop)
         const float t_hi = wq_slot_t(wq, r) * (1.0f + rel_t) + rabs;
         auto member = [&](const float4& N0, const float4& N1, const float4& N2, int k, bool valid = true) {
@@ -2102,9 +2157,15 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
             member(B00, B01, B02, 1);
             continue;
           }
-          const float4* na = wq.nodes + 3 * (fc + min(2u * h, gcnt - 1u));
-          const float4* nb = wq.nodes + 3 * (fc + min(2u * h + 1u, gcnt - 1u));
-          const float4 A0 = na[0], A1 = na[1], A2 = na[2], B0 = nb[0], B1 = nb[1], B2 = nb[2];
+          float4 A0, A1, A2, B0, B1, B2;
+          if constexpr (kL2) {
+            const WqRec ra = wq_rec(wq, fc + min(2u * h, gcnt - 1u)), rb = wq_rec(wq, fc + min(2u * h + 1u, gcnt - 1u));
+            A0 = ra.a, A1 = ra.b, A2 = ra.c, B0 = rb.a, B1 = rb.b, B2 = rb.c;
+          } else {
+            const float4* na = wq.nodes + 3 * (fc + min(2u * h, gcnt - 1u));
+            const float4* nb = wq.nodes + 3 * (fc + min(2u * h + 1u, gcnt - 1u));
+            A0 = na[0], A1 = na[1], A2 = na[2], B0 = nb[0], B1 = nb[1], B2 = nb[2];
+          }
           member(A0, A1, A2, 2 * h, h == 0 || 2u * h < gcnt);
           member(B0, B1, B2, 2 * h + 1, h == 0 || 2u * h + 1u < gcnt);
         }
@@ -2114,18 +2175,37 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
 #pragma unroll
           for (int k = st - 1; k + st < (int)kWqSlots; k += 2 * st) wq_order(pk[k], pe[k], pk[k + st], pe[k + st]);
       } else {  // finish the group's subtrees with a stackless walk (escape links)
-        const uint32_t end = wq_escape(wq.nodes, fc + gcnt - 1u);
+        uint32_t end;
+        if constexpr (kL2)
+          end = wq_escape(wq, fc + gcnt - 1u);
+        else
+          end = wq_escape(wq.nodes, fc + gcnt - 1u);
         uint32_t cur = fc;
         while (cur != end) {
-          const uint32_t inf = wq_info(wq.nodes, cur), cnt = inf >> 27;
+          uint32_t inf;
+          WqRec rc;
+          if constexpr (kL2) {
+            rc = wq_rec(wq, cur);
+            inf = __builtin_bit_cast(uint32_t, rc.c.w);
+          } else {
+            inf = wq_info(wq.nodes, cur);
+          }
+          const uint32_t cnt = inf >> 27;
           float tnear;
           const float t_hi = wq_slot_t(wq, r) * (1.0f + rel_t) + rabs;
-          const bool v = wq_node_visit(wq.nodes + 3 * cur, ro, rd, rinv, rR, rabs, t_hi, tnear);
+          bool v;
+          if constexpr (kL2)
+            v = wq_node_visit_r(rc.a, rc.b, rc.c, ro, rd, rinv, rR, rabs, t_hi, tnear);
+          else
+            v = wq_node_visit(wq.nodes + 3 * cur, ro, rd, rinv, rR, rabs, t_hi, tnear);
           if (v && cnt) {
             const uint32_t first = inf & 0x07FFFFFFu;
             for (uint32_t k = first; k < first + cnt; ++k) wq_leaf_prim(prims, wq, k, r, rm, ro, rd);
           }
-          cur = (v && !cnt) ? (inf & 0xFFFFu) : wq_escape(wq.nodes, cur);  // inner: its first child
+          if constexpr (kL2)  // (the escape from the record just read)
+            cur = (v && !cnt) ? (inf & 0xFFFFu) : __builtin_bit_cast(uint32_t, rc.c.z) >> 16;
+          else
+            cur = (v && !cnt) ? (inf & 0xFFFFu) : wq_escape(wq.nodes, cur);  // inner: its first child
         }
       }
     }
@@ -2275,8 +2355,18 @@ __device__ __forceinline__ void sky_samples(const TileList& tl, bool active, f3 
 #define HRT_BOUNCE_PRIO 1
 #endif
 // kBounceWqR: BUNDLE_WQ with node margins from each member's own R (HRT_OPT_WQ_NODE_RADIUS = 2)
-enum BounceMode { kBounceBrute = 0, kBounceCull = 1, kBounceBvh = 2, kBounceWq = 3, kBounceWqR = 4 };
-constexpr bool is_wq(int b) { return b == kBounceWq || b == kBounceWqR; }
+// kBounceWqL2 / kBounceWqL2R: the same two with the node source of BUNDLE_WQ_L2 (WqL2)
+enum BounceMode {
+  kBounceBrute = 0,
+  kBounceCull = 1,
+  kBounceBvh = 2,
+  kBounceWq = 3,
+  kBounceWqR = 4,
+  kBounceWqL2 = 5,
+  kBounceWqL2R = 6
+};
+constexpr bool is_wq(int b) { return b == kBounceWq || b == kBounceWqR || b == kBounceWqL2 || b == kBounceWqL2R; }
+constexpr bool is_wq_node_r(int b) { return b == kBounceWqR || b == kBounceWqL2R; }
 
 #ifndef HRT_PIXEL_POOL
 #define HRT_PIXEL_POOL 1
@@ -2463,7 +2553,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (run_sec) {
       if (HRT_BOUNCE_PRIO && !co.hot) __builtin_amdgcn_s_setprio(HRT_BOUNCE_PRIO);
       if constexpr (is_wq(Bounce)) {
-        world_hit_bounce_wq<D, Bounce == kBounceWqR>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
+        world_hit_bounce_wq<D, is_wq_node_r(Bounce)>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
                                                      c, dg);
       } else if constexpr (Bounce == kBounceBvh) {
         world_hit_bounce_bvh<D>(sc, P, bsrc, sec, p.pos, p.dir, tests, c, dg);
@@ -2987,6 +3077,32 @@ __global__ __launch_bounds__(1024) void trace_bundle_wq_solo(TraceParams P) HRT_
 __global__ __launch_bounds__(1024) void trace_bundle_wq_nr_solo(TraceParams P) HRT_WQ_KERNEL_BODY(kBounceWqR, false, false, false)
 #undef HRT_WQ_KERNEL_BODY
 
+// BUNDLE_WQ_L2: the same traversal for hierarchies that do not fit the LDS.  The breadth-first
+// image stays in global memory; its first P.wq_lds_nodes slots (the top of the tree: wq_l2_plan) are staged
+// into LDS before the stacks.  Dynamic LDS: [wq_lds_nodes x 48 B][16 x (64 slots x 8 B, wq_ncap + wq_tcap words)].
+// No sky lane: the _solo shape (the whole register budget, the plain work counter).
+#define HRT_WQ_L2_KERNEL_BODY(BOUNCE, D)                                                                         \
+  {                                                                                                             \
+    const uint32_t nl = P.wq_lds_nodes;                                                                         \
+    float4* nodes = lds_tris;                                                                                   \
+    for (uint32_t k = threadIdx.x; k < 3 * nl; k += 1024) nodes[k] = P.bvh_wq_nodes_bfs[k];                     \
+    const uint32_t wave = threadIdx.x >> 6;                                                                     \
+    char* base = reinterpret_cast<char*>(nodes + 3 * nl) + (size_t)wave * (512 + 4 * (P.wq_ncap + P.wq_tcap));   \
+    const WqL2 wq{{nodes, reinterpret_cast<unsigned long long*>(base), reinterpret_cast<uint32_t*>(base + 512),  \
+                   reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap, false},                      \
+                  (WqGlobalNodes)P.bvh_wq_nodes_bfs, nl};                                                       \
+    __syncthreads();                                                                                            \
+    const float4* T = reinterpret_cast<const float4*>(P.tris);                                                  \
+    tile_loop<1024, false, false>(P, nullptr, nullptr, [&](uint32_t x, uint32_t lr, Coop& co, uint32_t f, uint32_t nr) { \
+      trace_fused_split<BOUNCE, D>(P, x, lr, CullGlobal{T, to_const(T)}, wq, nullptr, co, f, nr);               \
+    });                                                                                                         \
+  }
+template <bool D>
+__global__ __launch_bounds__(1024) void trace_bundle_wq_l2(TraceParams P) HRT_WQ_L2_KERNEL_BODY(kBounceWqL2, D)
+template <bool D>
+__global__ __launch_bounds__(1024) void trace_bundle_wq_l2_nr(TraceParams P) HRT_WQ_L2_KERNEL_BODY(kBounceWqL2R, D)
+#undef HRT_WQ_L2_KERNEL_BODY
+
 // The sky lane (HRT_OPT_SKY_LANE): the plan's sky items on a lean kernel of their own, resident beside
 // the BUNDLE_WQ workgroups -- one more wave per SIMD, which the main kernel's register budget leaves room
 // for (HRT_WQ_VGPR_CAP) and which uses no LDS.  The sky loop is pure VALU work; the traversal's waves
@@ -3412,6 +3528,45 @@ size_t wq_lds_bytes(const TraceParams& p, uint32_t* ncap, uint32_t* tcap) {
   return (size_t)p.bvh_wq_n_nodes * 48 + 16 * (512 + 4 * ((size_t)n + t));
 }
 
+// BUNDLE_WQ_L2's LDS plan for a breadth-first image of n_nodes records: out = {L, ncap, tcap, bytes} -- the
+// slots kept in LDS, the per-wave node / triangle pair stack capacities and the dynamic LDS bytes
+// L x 48 + 16 x (512 + 4 x (ncap + tcap)); bytes = 0 (all four 0): no fit (the stacks alone do not fit, or
+// the image's shape is not the kernel's).  lds_nodes (HRT_OPT_WQ_LDS_NODES) < 0, auto: the stacks get
+// their BUNDLE_WQ maximum first (1024 node pairs, wq_tri_cap triangle pairs; lower when ncap_req / tcap_req,
+// the HRT_OPT_WQ_NODE_CAP / HRT_DEBUG_OPT_WQ_TRI_CAP requests, ask for less) and the nodes what is left.
+// lds_nodes >= 0: L = min(lds_nodes, n_nodes, what fits beside stacks of the minimum 128 node pairs), and
+// the node stacks what is left of the 160 KiB, up to the same maximum.
+void wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes, uint32_t ncap_req,
+                uint32_t tcap_req, uint32_t out[4]) {
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (n_nodes == 0 || n_nodes >= 0x10000u || max_leaf == 0 || max_leaf > 4 || width > kWqSlots || width < 2) return;
+  size_t t = wq_tri_cap(max_leaf), nmax = 1024;
+  if (ncap_req) nmax = std::min<size_t>(nmax, std::max(128u, ncap_req & ~63u));
+  if (tcap_req) t = std::min<size_t>(t, std::max(128u, tcap_req & ~63u));
+  auto stacks = [&](size_t ncap) { return 16 * (512 + 4 * (ncap + t)); };
+  if (stacks(128) > kMaxLdsScene) return;
+  size_t L, ncap;
+  if (lds_nodes < 0) {
+    ncap = nmax;
+    while (stacks(ncap) > kMaxLdsScene) ncap -= 64;  // (ends at 128 at the latest)
+    L = std::min<size_t>(n_nodes, (kMaxLdsScene - stacks(ncap)) / 48);
+  } else {
+    L = std::min<size_t>({(size_t)lds_nodes, (size_t)n_nodes, (kMaxLdsScene - stacks(128)) / 48});
+    const size_t per_wave = (kMaxLdsScene - L * 48) / 16;
+    ncap = std::min(nmax, ((per_wave - 512 - 4 * t) / 4) & ~(size_t)63);
+  }
+  out[0] = (uint32_t)L;
+  out[1] = (uint32_t)ncap;
+  out[2] = (uint32_t)t;
+  out[3] = (uint32_t)(L * 48 + stacks(ncap));
+}
+static size_t wq_l2_lds_bytes(const TraceParams& p, uint32_t plan[4]) {
+  plan[0] = plan[1] = plan[2] = plan[3] = 0;
+  if (!p.bvh_nodes || !p.bvh_wq_nodes_bfs) return 0;
+  wq_l2_plan(p.bvh_wq_n_nodes, p.bvh_wq_width, p.bvh_max_leaf, p.wq_lds_nodes_opt, p.wq_ncap, p.wq_tcap, plan);
+  return plan[3];
+}
+
 int resolve_variant(const TraceParams& p, int variant) {
   if (variant == HRT_KERNEL_AUTO) {
     // profiles/r01g_*: island 21.4 (LDS) vs 23.7 ms, cave 112 vs 120 ms; BVH from ~4K triangles.
@@ -3434,8 +3589,16 @@ int resolve_variant(const TraceParams& p, int variant) {
   if (variant == HRT_KERNEL_BUNDLE_CULL_LDS && lds_block(p.n_tris) == 0) variant = HRT_KERNEL_BUNDLE_CULL;
   if (variant == HRT_KERNEL_BUNDLE_WQ && (wq_lds_bytes(p, nullptr, nullptr) == 0 || p.pc.num_meshes > 64))
     variant = HRT_KERNEL_BUNDLE_BVH_LDS;
+  // BUNDLE_WQ_L2: the image exists (and is uploaded: this context selected the variant) and the stacks fit
+  uint32_t l2_plan[4];
+  if (variant == HRT_KERNEL_BUNDLE_WQ_L2 && (wq_l2_lds_bytes(p, l2_plan) == 0 || p.pc.num_meshes > 64))
+    variant = HRT_KERNEL_BUNDLE_BVH_LDS;
   if (variant == HRT_KERNEL_BUNDLE_BVH_LDS && !bvh_lds_fits(p)) variant = HRT_KERNEL_BUNDLE_BVH;
   if (variant == HRT_KERNEL_BUNDLE_BVH_LDS && (!p.bvh_nodes || p.pc.num_meshes > 64)) variant = HRT_KERNEL_BUNDLE_CULL;
+  // (the end of the chain BUNDLE_WQ / BUNDLE_WQ_L2 -> BUNDLE_BVH_LDS -> BUNDLE_BVH: without a hierarchy
+  // bvh_lds_fits is false too, and the line above no longer sees BUNDLE_BVH_LDS -- BUNDLE_BVH then ran with no
+  // nodes and faulted on a scene of more than 64 meshes)
+  if (variant == HRT_KERNEL_BUNDLE_BVH && (!p.bvh_nodes || p.pc.num_meshes > 64)) variant = HRT_KERNEL_BUNDLE_CULL;
   if (p.pc.max_bounces < 0) variant = HRT_KERNEL_LITERAL;  // the fused loops assume >= 1 segment per path
   return variant;
 }
@@ -3501,6 +3664,10 @@ hipError_t ensure_kernel_attributes(int device) {
                             reinterpret_cast<const void*>(&trace_bundle_wq_nr<true>),
                             reinterpret_cast<const void*>(&trace_bundle_wq_solo),
                             reinterpret_cast<const void*>(&trace_bundle_wq_nr_solo),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_l2<false>),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_l2<true>),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_l2_nr<false>),
+                            reinterpret_cast<const void*>(&trace_bundle_wq_l2_nr<true>),
                             reinterpret_cast<const void*>(&query_pairs<false, false>),
                             reinterpret_cast<const void*>(&query_pairs<false, true>),
                             reinterpret_cast<const void*>(&query_pairs<true, false>),
@@ -3534,7 +3701,8 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
   // (profiles/r01q_sec_batch_sweep.jsonl, frames in 16-frame launches); 36 for the per-node-radius
   // kernel, whose scenes bounce far more (cave 20 / 28 / 36 / 44 / 56: 7.43 / 7.38 / 7.31 / 7.32 /
   // 7.45 ms; island stays best at 28: profiles/r02v_ab.txt)
-  if (p.sec_batch == 0) p.sec_batch = variant == HRT_KERNEL_BUNDLE_WQ ? (p.bvh_node_r ? 36u : 28u) : 48u;
+  if (p.sec_batch == 0)
+    p.sec_batch = variant == HRT_KERNEL_BUNDLE_WQ || variant == HRT_KERNEL_BUNDLE_WQ_L2 ? (p.bvh_node_r ? 36u : 28u) : 48u;
   *block_out = variant == HRT_KERNEL_BRUTE_LDS ? 1024 : 256;
   const dim3 grid((p.pc.width + 15) / 16, (p.local_rows + 15) / 16, 1);
   switch (variant) {
@@ -3617,6 +3785,34 @@ hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, 
       } else if (sky && !sky->run) {
         trace_sky<<<1, 256, 0, sky->stream>>>(q);  // (returns at once: q.sky_lane == 0; nothing to order)
       }
+      *block_out = 1024;
+      break;
+    }
+    case HRT_KERNEL_BUNDLE_WQ_L2: {
+      // BUNDLE_WQ's launch without the sky lane: the same planner, heavy-tile splitting and frame runs
+      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
+      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
+      TraceParams q = p;
+      q.coop = 0;
+      if (q.split_k == 0) q.split_k = 8;
+      if (q.split_factor < 0 && p.n_frames > 1)
+        q.split_factor4 = 5;
+      else if (q.split_factor < 0)
+        q.split_factor = (uint64_t)tiles_of(p) * std::max(1u, p.n_frames) > 6ull * p.num_cus * 16u ? 2 : 3;
+      uint32_t plan[4];
+      const size_t lds = wq_l2_lds_bytes(p, plan);  // (non-zero: resolve_variant)
+      q.wq_lds_nodes = plan[0];
+      q.wq_ncap = plan[1];
+      q.wq_tcap = plan[2];
+      q.sky_lane = 0;
+      if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
+      const bool d = p.diag || p.probe;
+      if (p.bvh_node_r)
+        d ? trace_bundle_wq_l2_nr<true><<<p.num_cus, 1024, lds, stream>>>(q)
+          : trace_bundle_wq_l2_nr<false><<<p.num_cus, 1024, lds, stream>>>(q);
+      else
+        d ? trace_bundle_wq_l2<true><<<p.num_cus, 1024, lds, stream>>>(q)
+          : trace_bundle_wq_l2<false><<<p.num_cus, 1024, lds, stream>>>(q);
       *block_out = 1024;
       break;
     }

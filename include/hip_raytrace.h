@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): ray queries -- hrt_ray_query, hrt_hit, hrt_query_stats,
+/* 6, additive (no bump: nothing existing changed): HRT_KERNEL_BUNDLE_WQ_L2, HRT_OPT_WQ_LDS_NODES,
+ * hrt_debug_bvh_wq_nodes_bfs, hrt_debug_wq_l2_plan.
+ * 6, additive (no bump: nothing existing changed): ray queries -- hrt_ray_query, hrt_hit, hrt_query_stats,
  * hrt_query_method, hrt_intersect, hrt_intersect_primary.
  * 6, additive (no bump: nothing existing changed): hrt_debug_tile_lists.
  * 6, additive (no bump: nothing existing changed): HRT_OPT_SKY_LANE, hrt_debug_sky_units.
@@ -315,10 +317,23 @@ typedef enum hrt_kernel {
                                     workgroups; falls back to BUNDLE_CULL above ~3,300 triangles) */
   HRT_KERNEL_BUNDLE_BVH_LDS = 8,  /* BUNDLE_BVH with the hierarchy and triangles in LDS (1024-thread
                                     workgroups; falls back to BUNDLE_BVH when they exceed 160 KiB) */
-  HRT_KERNEL_BUNDLE_WQ = 9        /* bounce segments through the hierarchy as (ray, node) / (ray, triangle)
+  HRT_KERNEL_BUNDLE_WQ = 9,       /* bounce segments through the hierarchy as (ray, node) / (ray, triangle)
                                     pairs on per-wave LDS stacks, 64 pairs per step (1024-thread
                                     persistent workgroups, nodes in LDS; falls back to BUNDLE_BVH_LDS when
                                     they do not fit or leaves exceed 4 triangles) */
+  HRT_KERNEL_BUNDLE_WQ_L2 = 10,   /* BUNDLE_WQ for hierarchies that do not fit the LDS: the same pair traversal
+                                    with the node image (breadth first, up to 65,535 nodes = 3 MB) read from
+                                    global memory / L2 and only the top of the tree (HRT_OPT_WQ_LDS_NODES)
+                                    in the LDS the pair stacks leave free; no sky lane.  Runs when the image
+                                    exists (fewer than 65,536 nodes, leaves of at most 4 triangles, at most
+                                    64 meshes) and the stacks fit; else falls back as BUNDLE_WQ does.
+                                    HRT_KERNEL_AUTO does not pick it yet: scenes past BUNDLE_WQ's limit keep
+                                    BUNDLE_BVH.  A later change of AUTO will rest on the measurements of
+                                    DESIGN.md 22 (profiles/wq_l2_ab.txt; 1080p, 64 spp, 8 bounces, ms per
+                                    frame against BUNDLE_BVH): island@2 2.73 against 20.75, cave@2 9.93
+                                    against 219.96, island@4 9.57 against 52.70, island@8 98.5 against 229.9
+                                    (bound by its band lists; at 320x180 no win is established there).  A
+                                    scene that fits BUNDLE_WQ runs 14% slower on this variant. */
 } hrt_kernel;
 
 /* Option keys for hrt_set_option. */
@@ -417,6 +432,12 @@ typedef enum hrt_option {
    * code path without the lane, so auto never costs more than 0.  Diagnostics (HRT_OPT_COUNTERS = 2), probes and
    * timeline builds always keep every item on the main kernel.  Results do not depend on it. */
   HRT_OPT_SKY_LANE = 20,
+  /* BUNDLE_WQ_L2: nodes of the breadth-first image (the top of the tree) kept in LDS.  -1 (default) = auto:
+   * the pair stacks get their BUNDLE_WQ capacities first (1,024 node pairs, or the HRT_OPT_WQ_NODE_CAP
+   * request) and the nodes what is left of the 160 KiB (about 1,100 at leaves of 4); 0 = none, every node
+   * is read from global memory; n = min(n, the image's nodes, what fits beside node stacks of 128 pairs),
+   * the node stacks then taking what is left.  Results do not depend on it; the other kernels ignore it. */
+  HRT_OPT_WQ_LDS_NODES = 21,
   /* libhip_raytrace_debug.so only (tests): the value-th device allocation of the next hrt_set_scene
    * fails with HRT_ERR_OUT_OF_MEMORY (0 = off) */
   HRT_DEBUG_OPT_FAIL_ALLOC = 1001,
@@ -740,6 +761,11 @@ hrt_status hrt_debug_band_flatten(int device, const uint32_t n[64], const uint32
 hrt_status hrt_debug_wq_protocol(int device, uint32_t rounds, const uint32_t* cnt, const uint32_t* take,
                                  const uint32_t* tgt, const uint64_t* val, const uint64_t seed[64], uint32_t* popped,
                                  uint64_t* seen, uint64_t slots[64], uint32_t* depth);
+/* Test support, host only: BUNDLE_WQ_L2's LDS plan for an image of n_nodes records with groups of up to
+ * `width` and leaves of at most max_leaf triangles, lds_nodes as HRT_OPT_WQ_LDS_NODES and no stack-capacity
+ * requests.  out = {L, ncap, tcap, bytes}: the nodes kept in LDS, the per-wave node / triangle pair stack
+ * capacities, and the dynamic LDS bytes L x 48 + 16 x (512 + 4 x (ncap + tcap)); all four 0: no fit. */
+void hrt_debug_wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes, uint32_t out[4]);
 /* Test support: the context's grazing-band structure as the device holds it (hrt_set_scene): the 32 B
  * per-cell records of BUNDLE_WQ (8 words: list start, length, first 12 entries as half-words; rec_words >=
  * 8 x cells), the offsets (off_words >= cells + 1) and the entry words (16-bit entries two to a word unless

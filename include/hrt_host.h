@@ -52,6 +52,12 @@ int hrt_debug_bvh_build(const hrt_triangle* tris, uint32_t n_tris, const hrt_mes
 int64_t hrt_debug_bvh_wq_nodes(const hrt_triangle* tris, uint32_t n_tris, const hrt_mesh* meshes, uint32_t n_meshes,
                                uint32_t leaf_size, uint32_t width, float* out, uint64_t cap);
 
+/* Host-only: the same hierarchy's breadth-first image, which BUNDLE_WQ_L2 reads from global memory (hrt_bvh.h
+ * make_wq_nodes_bfs): the same records and groups, the groups allocated level by level so that the slots
+ * below any L are the nodes nearest the root, child and escape slots rewritten.  Returns as above. */
+int64_t hrt_debug_bvh_wq_nodes_bfs(const hrt_triangle* tris, uint32_t n_tris, const hrt_mesh* meshes,
+                                   uint32_t n_meshes, uint32_t leaf_size, uint32_t width, float* out, uint64_t cap);
+
 /* Column-major mat4 for push_constants.cam_alignment_mat: columns = normalised direction,
  * new_y, new_z (so mat3(M) * (1,0,0) = direction / |direction|), 4th column (0,0,0,1). */
 void hrt_host_view_matrix(const float direction[3], const float up[3], float out[16]);

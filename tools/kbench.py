@@ -76,7 +76,7 @@ def main():
                 same[(v, sb, k)] = None if ref is None else bool(np.array_equal(ctx.read(_lib.IMG_TRACE), ref))
     if a.diag:
         for v in a.variants:
-            if v in (0, 4, 5, 6, 7, 8, 9):
+            if v in (0, 4, 5, 6, 7, 8, 9, 10):
                 ctx.set_option(_lib.OPT_KERNEL_VARIANT, v)
                 ctx.set_option(_lib.OPT_COUNTERS, 2)
                 ctx.reset_stats()
