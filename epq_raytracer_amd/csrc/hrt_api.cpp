@@ -260,7 +260,7 @@ using hrt::bind;
 
 extern "C" uint32_t hrt_abi_version(void) { return HRT_ABI_VERSION; }
 
-// Host only: BUNDLE_WQ_L2's LDS plan (hrt_kernels.hip wq_l2_plan) with no stack-capacity requests.
+// Host only: BUNDLE_WQ_L2's LDS plan (hrt_launch_plan.h wq_l2_plan) with no stack-capacity requests.
 extern "C" void hrt_debug_wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes,
                                      uint32_t out[4]) {
   hrt::wq_l2_plan(n_nodes, width, max_leaf, lds_nodes, 0u, 0u, out);
@@ -801,7 +801,7 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   p.split_factor = ctx->split_factor;
   p.split_prio = ctx->split_prio;
   p.coop = ctx->coop;
-  p.wq_ncap = ctx->wq_node_cap;  // request; launch_trace sizes the stacks
+  p.wq_ncap = ctx->wq_node_cap;  // request; plan_trace sizes the stacks
   p.wq_tcap = ctx->debug_wq_tri_cap;  // (debug) request
   p.grab_always = ctx->debug_grab_runs;  // (debug) frame runs at any size
   p.timeline = ctx->timeline;
@@ -844,23 +844,15 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   return p;
 }
 
-bool persistent_kernel(int k) {
-  return k == HRT_KERNEL_BUNDLE_WQ || k == HRT_KERNEL_BUNDLE_WQ_L2 || k == HRT_KERNEL_BUNDLE_CULL_LDS ||
-         k == HRT_KERNEL_BUNDLE_BVH_LDS;
-}
-// The kernels whose launch (re)builds the lane's camera lists (launch_trace runs camera_lists before
-// them); LITERAL, BRUTE and BRUTE_LDS neither build nor read the lists.
-bool builds_camera_lists(int k) {
-  return persistent_kernel(k) || k == HRT_KERNEL_BUNDLE || k == HRT_KERNEL_BUNDLE_CULL || k == HRT_KERNEL_BUNDLE_BVH;
-}
-
 // One trace launch of p.n_frames frames on `stream` with lane l's planner buffers (timed by a HIP
 // event pair counted as that many traces).
 hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stream, int l) {
   if (ctx->diag_on)
     HRT_HIP(ctx, hipMemsetAsync(ctx->tile_cycles, 0, ctx->num_tiles() * 4 * sizeof(unsigned long long), stream));
   if (ctx->timeline) HRT_HIP(ctx, hipMemsetAsync(ctx->timeline_count, 0, sizeof(uint32_t), stream));  // this launch's
-  const int variant = ctx->variant;
+  // this launch's plan (hrt_launch_plan.h), shared with its probe: the kernel, and what the host knows of it
+  const hrt::LaunchPlan plan = hrt::plan_trace(hrt::plan_scene(p), ctx->variant);
+  const hrt::KernelTraits& kernel = hrt::kernel_traits(plan.kernel);
   if (ctx->pending.size() >= kMaxPending) {
     hrt_status st = harvest_one(ctx);
     if (st != HRT_OK) return st;
@@ -875,10 +867,6 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
   }
   ev.frames = p.n_frames > 1 ? p.n_frames : 1u;
   hrt::Lane& lane = ctx->lane[l];
-  // First trace of a persistent kernel on this lane (no tile costs yet): a 1-sample probe trace into the
-  // lane's own image (fully overwritten by the trace that follows on the same stream) measures the
-  // tiles' relative costs so that this trace already follows a plan (HRT_OPT_PROBE).
-  const int resolved = hrt::resolve_variant(p, variant);
   // camera lists: rebuilt only when the lane's were built for another position (or scene)
   uint32_t key[4];
   std::memcpy(key, p.pc.cam_pos, 12);
@@ -896,7 +884,10 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
   tkey[13] = p.pc.num_meshes;
   p.tl_lists_ready = lane.tl_ready && std::memcmp(tkey, lane.tl_key, sizeof tkey) == 0 ? 1u : 0u;
   lane.tl_ready = false;
-  if (ctx->probe && !lane.plan_valid && ctx->num_tiles() >= 1024 && persistent_kernel(resolved)) {
+  // First trace of a persistent kernel on this lane (no tile costs yet): a 1-sample probe trace into the
+  // lane's own image (fully overwritten by the trace that follows on the same stream) measures the
+  // tiles' relative costs so that this trace already follows a plan (HRT_OPT_PROBE).
+  if (ctx->probe && !lane.plan_valid && ctx->num_tiles() >= 1024 && kernel.persistent) {
     hrt::TraceParams q = p;
     q.pc.num_samples = 1;
     q.n_frames = 1;
@@ -905,14 +896,13 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
     q.diag = nullptr;
     q.tile_cycles = nullptr;
     q.probe = 1u;
-    int ran = 0, blk = 0;
-    if (hipError_t pe = hrt::launch_trace(q, variant, stream, &ran, &blk); pe != hipSuccess) {
+    if (hipError_t pe = hrt::launch_trace(q, plan, stream); pe != hipSuccess) {
       ctx->event_pool.push_back(ev);
       return hip_fail(ctx, pe, "probe trace launch");
     }
     p.plan_valid = 1u;
-    if (builds_camera_lists(ran)) p.cam_lists_ready = 1u;  // the probe built them
-    if (persistent_kernel(ran)) p.tl_lists_ready = 1u;     // (and the tile lists)
+    if (kernel.camera_lists) p.cam_lists_ready = 1u;  // the probe built them
+    p.tl_lists_ready = 1u;                            // (and the tile lists)
   }
   // The sky lane (HRT_OPT_SKY_LANE): BUNDLE_WQ's sky items on trace_sky beside the main kernel, forked from
   // `stream` inside launch_trace and joined back into it there -- so the event pair below spans fork to join
@@ -927,7 +917,7 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
   // Lane 0 (hrt_compute_n's) warms the side stream with its first BUNDLE_WQ launch, whatever its size.
   constexpr uint64_t kSkyLaneUnits = 128;
   hrt::SkyLane sky{};
-  const bool sky_ok = resolved == HRT_KERNEL_BUNDLE_WQ && !ctx->diag_on && !ctx->timeline;
+  const bool sky_ok = kernel.sky_lane && !ctx->diag_on && !ctx->timeline;
   constexpr int32_t kSkyLaneSamples = 64;
   const bool big = (uint64_t)ctx->num_tiles() * ev.frames >= kSkyLaneUnits * p.num_cus * 16u &&
                    p.pc.num_samples >= kSkyLaneSamples;
@@ -954,17 +944,19 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
     sky = hrt::SkyLane{lane.sky_stream, lane.sky_fork, lane.sky_join, run_sky};
   }
   HRT_HIP(ctx, hipEventRecord(ev.start, stream));
-  hipError_t e = hrt::launch_trace(p, variant, stream, &ctx->last_kernel, &ctx->last_block, want_sky ? &sky : nullptr);
+  ctx->last_kernel = plan.kernel;
+  ctx->last_block = (int)plan.block;
+  hipError_t e = hrt::launch_trace(p, plan, stream, want_sky ? &sky : nullptr);
   if (e == hipSuccess) ctx->last_frames = ev.frames;
   // the persistent kernels recorded this trace's tile costs: the lane's next trace can follow a plan
-  lane.plan_valid = e == hipSuccess && persistent_kernel(ctx->last_kernel);
+  lane.plan_valid = e == hipSuccess && kernel.persistent;
   // (only a kernel that built the lists leaves them valid: a LITERAL / BRUTE trace from this position
   // followed by a bundle kernel must rebuild them)
-  if (e == hipSuccess && builds_camera_lists(ctx->last_kernel)) {
+  if (e == hipSuccess && kernel.camera_lists) {
     lane.cam_ready = true;
     std::memcpy(lane.cam_key, key, sizeof key);
   }
-  if (e == hipSuccess && persistent_kernel(ctx->last_kernel)) {
+  if (e == hipSuccess && kernel.persistent) {
     lane.tl_ready = true;
     std::memcpy(lane.tl_key, tkey, sizeof tkey);
   }
@@ -1093,7 +1085,7 @@ hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* 
   p.sky_units = nullptr;
   p.timeline = nullptr;
   p.timeline_count = nullptr;
-  const int ran = hrt::resolve_query_method(p, (int)method);
+  const hrt::QueryPlan plan = hrt::plan_query(hrt::plan_scene(p), (int)method);
   const bool rays_direct = primary || query_direct(ctx, rays), hits_direct = query_direct(ctx, hits);
   if ((!primary && rays_direct && (uintptr_t)rays % 16 != 0) || (hits_direct && (uintptr_t)hits % 16 != 0))
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": device rays / hits must be 16-byte aligned");
@@ -1132,14 +1124,14 @@ hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* 
     q.x0 = rect[0];
     q.y0 = rect[1];
     q.w = rect[2];
-    HRT_HIP(ctx, hrt::launch_query(p, q, ran, primary, ctx->stream));
+    HRT_HIP(ctx, hrt::launch_query(p, q, plan, primary, ctx->stream));
     if (!hits_direct)
       HRT_HIP(ctx, hipMemcpyAsync(hits + at, ctx->query_hits, (size_t)m * sizeof(hrt_hit), hipMemcpyDefault, ctx->stream));
   }
   unsigned long long counts[2] = {0, 0};
   if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->query_stats, sizeof(counts), hipMemcpyDefault, ctx->stream));
   HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (stats) *stats = hrt_query_stats{(uint32_t)ran, 0u, counts[0], counts[1]};
+  if (stats) *stats = hrt_query_stats{(uint32_t)plan.method, 0u, counts[0], counts[1]};
   return HRT_OK;
 }
 
@@ -1165,7 +1157,7 @@ extern "C" hrt_status hrt_intersect(hrt_context* ctx, const hrt_ray_query* rays,
   pc.num_meshes = (int32_t)ctx->scene.n_meshes;
   const hrt::TraceParams p = make_params(ctx, &pc, 0);
   if (n == 0) {
-    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::resolve_query_method(p, (int)method), 0u, 0u, 0u};
+    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::plan_query(hrt::plan_scene(p), (int)method).method, 0u, 0u, 0u};
     return HRT_OK;
   }
   const uint32_t rect[3] = {0, 0, 1};
@@ -1187,7 +1179,7 @@ extern "C" hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_con
   if ((st = bind(ctx)) != HRT_OK) return st;
   const hrt::TraceParams p = make_params(ctx, pc, 0);
   if (n == 0) {
-    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::resolve_query_method(p, (int)method), 0u, 0u, 0u};
+    if (stats) *stats = hrt_query_stats{(uint32_t)hrt::plan_query(hrt::plan_scene(p), (int)method).method, 0u, 0u, 0u};
     return HRT_OK;
   }
   const uint32_t rect[3] = {x0, y0, w};
@@ -1256,7 +1248,8 @@ hrt_status begin_batch(hrt_context* ctx, const hrt_push_constants* pc, uint32_t 
   const size_t np = ctx->npix(), px_bytes = ctx->px_bytes();
   const uint32_t cap = (uint32_t)std::max<size_t>(
       1, std::min<size_t>(std::min(ctx->frames_per_launch, bound), ((size_t)1 << 30) / std::max<size_t>(np * px_bytes, 1)));
-  const bool batch = persistent_kernel(hrt::resolve_variant(b->p, ctx->variant)) && cap > 1 && n > 1;
+  const hrt::LaunchPlan plan = hrt::plan_trace(hrt::plan_scene(b->p), ctx->variant);
+  const bool batch = hrt::kernel_traits(plan.kernel).persistent && cap > 1 && n > 1;
   if (batch && (st = grow_frame_stack(ctx, cap, n, np, px_bytes)) != HRT_OK) return st;
   b->lcap = batch ? std::max(1u, std::min(cap, ctx->frame_stack_frames)) : 1;  // (no stack at all: per frame)
   return HRT_OK;

@@ -134,7 +134,7 @@ struct hrt_context {
   void* scratch = nullptr;  // format conversion for hrt_read_image
   unsigned long long* counters = nullptr;
   unsigned long long* tile_cycles = nullptr;  // diagnostics: shader clocks per 8x8 tile of the last trace
-  uint32_t split_k = 0, split_prio = 1;  // split 0: auto (per kernel, launch_trace)
+  uint32_t split_k = 0, split_prio = 1;  // split 0: auto (per kernel, hrt_launch_plan.h)
   int32_t split_factor = -1;  // auto
   uint32_t grid_cus = 0;  // HRT_OPT_GRID_CUS (debug build; 0: every CU)
   uint32_t coop = 1;      // HRT_OPT_COOP
@@ -161,7 +161,7 @@ struct hrt_context {
   int variant = 0;
   bool counters_on = true;
   bool diag_on = false;
-  uint32_t sec_batch = 0;  // HRT_OPT_SECONDARY_BATCH (0 = auto per kernel, launch_trace)
+  uint32_t sec_batch = 0;  // HRT_OPT_SECONDARY_BATCH (0 = auto per kernel, hrt_launch_plan.h)
   int last_kernel = 0, last_block = 0;  // what the last hrt_trace launched (hrt_stats)
   uint32_t last_frames = 0;             // ... and the frames that launch held
 

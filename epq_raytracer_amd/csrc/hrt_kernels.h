@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "hip_raytrace.h"
+#include "hrt_launch_plan.h"
 
 namespace hrt {
 
@@ -73,7 +74,7 @@ struct TraceParams {
   uint32_t bvh_n_nodes, bvh_n_irregular, bvh_n_prims, bvh_n_meshes;
   float bvh_abs_coef, bvh_rel_t;  // box-test t-slack (hrt_bvh.h)
   uint32_t bvh_max_leaf;         // largest leaf triangle count of the hierarchy
-  uint32_t wq_ncap, wq_tcap;     // BUNDLE_WQ: per-wave node / triangle pair stack capacities (launch_trace)
+  uint32_t wq_ncap, wq_tcap;     // BUNDLE_WQ: per-wave node / triangle pair stack capacities (plan_trace)
   // Frames per launch (persistent variants, hrt_compute_n): frame f (0 <= f < n_frames) uses
   // rng_offset + f and writes img8 / img32 + f * frame_stride pixels.  0 or 1: one frame.
   uint32_t n_frames;
@@ -98,7 +99,7 @@ struct TraceParams {
   uint32_t sky_lane;        // (launch_trace) this launch's plan ends in its sky items and trace_sky runs beside the main kernel
   // BUNDLE_WQ_L2: the breadth-first node image (hrt_bvh.h make_wq_nodes_bfs; bvh_wq_n_nodes records), uploaded for
   // the contexts that select the variant, else nullptr; the HRT_OPT_WQ_LDS_NODES request (-1: auto); and the slots
-  // the launch keeps in LDS (launch_trace, wq_l2_plan)
+  // the launch keeps in LDS (plan_trace, wq_l2_plan)
   const float4* bvh_wq_nodes_bfs;
   int32_t wq_lds_nodes_opt;
   uint32_t wq_lds_nodes;
@@ -115,13 +116,14 @@ constexpr uint32_t kTlRecWords = 136;
 
 // Per device, once: the dynamic-LDS limits of the persistent kernels (hipFuncSetAttribute).
 hipError_t ensure_kernel_attributes(int device);
-// Launches the trace kernel(s); *ran / *block receive the resolved hrt_kernel and workgroup size.
+// What a launch's plan reads of p: plan_trace(plan_scene(p), variant) is the kernel an HRT_KERNEL_* request
+// runs with its workgroups and LDS, plan_query(plan_scene(p), method) a query's (hrt_launch_plan.h).
+PlanScene plan_scene(const TraceParams& p);
+// Launches the trace kernel(s) of p's plan.
 // sky: BUNDLE_WQ's product kernels run a planned launch's sky items on trace_sky beside the main kernel
 // (forked from `stream` after the planner kernels, joined back into it before launch_trace returns);
 // nullptr: every item runs on the main kernel.
-hipError_t launch_trace(const TraceParams& p, int variant, hipStream_t stream, int* ran, int* block,
-                        const SkyLane* sky = nullptr);
-int resolve_variant(const TraceParams& p, int variant);  // the kernel an HRT_KERNEL_* request runs
+hipError_t launch_trace(const TraceParams& p, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky = nullptr);
 // hrt_debug_tile_lists: camera_lists, then tile_lists into p.tl_cache (tiles x kTlRecWords); refine 0: the
 // cap rule alone, else the product's lists (cap, then corner directions per tile and per pixel).
 hipError_t launch_tile_lists(const TraceParams& p, uint32_t refine, hipStream_t stream);
@@ -142,12 +144,6 @@ hipError_t launch_wq_protocol_check(uint32_t rounds, const uint32_t* cnt, const 
                                     const unsigned long long* val, const unsigned long long* seed, uint32_t* popped,
                                     unsigned long long* seen, unsigned long long* slots, uint32_t* depth,
                                     hipStream_t stream);
-// BUNDLE_WQ's per-wave node-stack capacity for an image of n_nodes records with groups of `width` and
-// leaves of at most max_leaf triangles (0: does not fit the LDS)
-uint32_t wq_stack_cap(uint32_t n_nodes, uint32_t width, uint32_t max_leaf);
-// BUNDLE_WQ_L2's LDS plan (hrt_kernels.hip): out = {nodes kept in LDS, node pair stack, triangle pair stack, bytes}
-void wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes, uint32_t ncap_req,
-                uint32_t tcap_req, uint32_t out[4]);
 // Ray queries (hrt_intersect / hrt_intersect_primary): the query kernels' own arguments,
 // passed after the TraceParams block (world_hit_bounce_wq reads its constants through the kernarg
 // segment's start).  One ray per lane: ray i of the launch is rays[2 i], rays[2 i + 1] (hrt_ray_query),
@@ -161,10 +157,7 @@ struct QueryArgs {
   uint32_t first;             // primary: the rectangle index of ray 0
   uint32_t x0, y0, w;         // primary: the rectangle's corner and width
 };
-// The method an hrt_query_method request runs on p's scene (AUTO resolved, fallbacks applied).
-int resolve_query_method(const TraceParams& p, int method);
-// Launches q.n rays with `method` (already resolved); p.pc holds the sphere / mesh counts (and, primary, the camera).
-hipError_t launch_query(const TraceParams& p, const QueryArgs& q, int method, bool primary, hipStream_t stream);
-constexpr uint32_t kAutoLeafWqStack = 512;  // auto leaf size: the smallest leaf whose image leaves this much
+// Launches q.n rays as p's plan_query says; p.pc holds the sphere / mesh counts (and, primary, the camera).
+hipError_t launch_query(const TraceParams& p, const QueryArgs& q, const QueryPlan& plan, bool primary, hipStream_t stream);
 
 }  // namespace hrt

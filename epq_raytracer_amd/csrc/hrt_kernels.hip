@@ -1608,7 +1608,7 @@ __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const Trac
 // profiles/r02j_wq_groups_ab.jsonl): 8 slots ran the 4-wide image 9% slower (registers), and the
 // triangle stack of an 8-wide image does not fit the LDS; fully ordering the 4 slots (5
 // compare-exchanges, HRT_WQ_FULLSORT) instead of only putting the nearest last (3) was 0.9% slower.
-constexpr uint32_t kWqSlots = 4;
+// (kWqSlots = 4: hrt_launch_plan.h, whose stack sizing reads it too)
 
 struct WqLds {
   const float4* nodes;        // BVH nodes (LDS copy)
@@ -3486,121 +3486,12 @@ __global__ __launch_bounds__(256) void math_check(uint32_t n, uint32_t seed, uns
 // ---- launch wrappers (host) ----------------------------------------------------------------------
 namespace hrt {
 
-constexpr size_t kMaxLdsScene = 160 * 1024 - 64;  // dynamic LDS per CU, leaving room for the kernels' static LDS
-constexpr uint32_t kAutoCullTris = 256;   // BUNDLE_CULL from this many mesh triangles, BUNDLE below
-constexpr uint32_t kAutoBvhTris = 4096;   // BUNDLE_BVH from this many (profiles/r01d_bvh_scaling.log)
-constexpr uint32_t kAutoWqStack = 384;    // BUNDLE_WQ when its per-wave node stacks hold this many entries
-
-// BUNDLE_BVH_LDS footprint: triangles + nodes + entries + key bases.
-size_t bvh_lds_bytes(const TraceParams& p) {
-  return (size_t)p.n_tris * 48 + (size_t)p.bvh_n_nodes * 64 + (size_t)p.bvh_n_prims * 4 + (size_t)p.bvh_n_meshes * 4;
-}
-bool bvh_lds_fits(const TraceParams& p) { return p.bvh_nodes && p.bvh_entries && bvh_lds_bytes(p) <= kMaxLdsScene; }
-
-// BUNDLE_CULL_LDS workgroup size for a scene of n triangles (0 = does not fit): two 512-thread
-// workgroups per CU when twice the footprint fits the 160 KiB, else one of 1024.
-constexpr size_t kCoopLds = 3 * 64 * 8;  // cooperative-tile exchange slots
-uint32_t lds_block(uint32_t n) {
-  const size_t tri = (size_t)n * 48 + kCoopLds;
-  return tri <= kMaxLdsScene / 2 ? 512u : tri <= kMaxLdsScene ? 1024u : 0u;
-}
-
-// BUNDLE_WQ per-wave pair stacks: triangle stack 64 x (1 + 2 x largest leaf), node stack what is left of
-// the 160 KiB after the nodes (at most 1024 pairs, at least 128).  Returns the LDS bytes, 0 = no fit.
-// Triangle stack: 64 x (1 + 2 x largest leaf) pairs -- a node step's pushes onto < 64 waiting ones
-// when each lane keeps at most two leaves; a larger burst of a grouped step is tested in place.
-constexpr uint32_t wq_tri_cap(uint32_t max_leaf) { return 64u * (1u + 2u * max_leaf); }
-uint32_t wq_stack_cap(uint32_t n_nodes, uint32_t width, uint32_t max_leaf) {
-  if (max_leaf > 4 || width > kWqSlots || width < 2) return 0;
-  const size_t nodes = (size_t)n_nodes * 48, t = wq_tri_cap(max_leaf);
-  if (nodes + 16 * (512 + 4 * (t + 128)) > kMaxLdsScene) return 0;
-  const size_t per_wave = (kMaxLdsScene - nodes) / 16;
-  return (uint32_t)std::min<size_t>(1024, ((per_wave - 512 - 4 * t) / 4) & ~(size_t)63);
-}
-
-size_t wq_lds_bytes(const TraceParams& p, uint32_t* ncap, uint32_t* tcap) {
-  if (!p.bvh_nodes || !p.bvh_wq_nodes) return 0;
-  const uint32_t n = wq_stack_cap(p.bvh_wq_n_nodes, p.bvh_wq_width, p.bvh_max_leaf);
-  if (n == 0) return 0;
-  const size_t t = wq_tri_cap(p.bvh_max_leaf);
-  if (ncap) *ncap = n;
-  if (tcap) *tcap = (uint32_t)t;
-  return (size_t)p.bvh_wq_n_nodes * 48 + 16 * (512 + 4 * ((size_t)n + t));
-}
-
-// BUNDLE_WQ_L2's LDS plan for a breadth-first image of n_nodes records: out = {L, ncap, tcap, bytes} -- the
-// slots kept in LDS, the per-wave node / triangle pair stack capacities and the dynamic LDS bytes
-// L x 48 + 16 x (512 + 4 x (ncap + tcap)); bytes = 0 (all four 0): no fit (the stacks alone do not fit, or
-// the image's shape is not the kernel's).  lds_nodes (HRT_OPT_WQ_LDS_NODES) < 0, auto: the stacks get
-// their BUNDLE_WQ maximum first (1024 node pairs, wq_tri_cap triangle pairs; lower when ncap_req / tcap_req,
-// the HRT_OPT_WQ_NODE_CAP / HRT_DEBUG_OPT_WQ_TRI_CAP requests, ask for less) and the nodes what is left.
-// lds_nodes >= 0: L = min(lds_nodes, n_nodes, what fits beside stacks of the minimum 128 node pairs), and
-// the node stacks what is left of the 160 KiB, up to the same maximum.
-void wq_l2_plan(uint32_t n_nodes, uint32_t width, uint32_t max_leaf, int64_t lds_nodes, uint32_t ncap_req,
-                uint32_t tcap_req, uint32_t out[4]) {
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (n_nodes == 0 || n_nodes >= 0x10000u || max_leaf == 0 || max_leaf > 4 || width > kWqSlots || width < 2) return;
-  size_t t = wq_tri_cap(max_leaf), nmax = 1024;
-  if (ncap_req) nmax = std::min<size_t>(nmax, std::max(128u, ncap_req & ~63u));
-  if (tcap_req) t = std::min<size_t>(t, std::max(128u, tcap_req & ~63u));
-  auto stacks = [&](size_t ncap) { return 16 * (512 + 4 * (ncap + t)); };
-  if (stacks(128) > kMaxLdsScene) return;
-  size_t L, ncap;
-  if (lds_nodes < 0) {
-    ncap = nmax;
-    while (stacks(ncap) > kMaxLdsScene) ncap -= 64;  // (ends at 128 at the latest)
-    L = std::min<size_t>(n_nodes, (kMaxLdsScene - stacks(ncap)) / 48);
-  } else {
-    L = std::min<size_t>({(size_t)lds_nodes, (size_t)n_nodes, (kMaxLdsScene - stacks(128)) / 48});
-    const size_t per_wave = (kMaxLdsScene - L * 48) / 16;
-    ncap = std::min(nmax, ((per_wave - 512 - 4 * t) / 4) & ~(size_t)63);
-  }
-  out[0] = (uint32_t)L;
-  out[1] = (uint32_t)ncap;
-  out[2] = (uint32_t)t;
-  out[3] = (uint32_t)(L * 48 + stacks(ncap));
-}
-static size_t wq_l2_lds_bytes(const TraceParams& p, uint32_t plan[4]) {
-  plan[0] = plan[1] = plan[2] = plan[3] = 0;
-  if (!p.bvh_nodes || !p.bvh_wq_nodes_bfs) return 0;
-  wq_l2_plan(p.bvh_wq_n_nodes, p.bvh_wq_width, p.bvh_max_leaf, p.wq_lds_nodes_opt, p.wq_ncap, p.wq_tcap, plan);
-  return plan[3];
-}
-
-int resolve_variant(const TraceParams& p, int variant) {
-  if (variant == HRT_KERNEL_AUTO) {
-    // profiles/r01g_*: island 21.4 (LDS) vs 23.7 ms, cave 112 vs 120 ms; BVH from ~4K triangles.
-    // BUNDLE_WQ when its node stacks get >= kAutoWqStack entries (r02, node groups: island 2.84 vs
-    // ~15 ms for BUNDLE_CULL_LDS; cave 17.3 ms at 384-entry stacks vs 20.2, profiles/r02p_cave_wq.txt)
-    // A poor hierarchy (large overlapping triangles, HRT_SCENE_BVH_SAH_MILLI > 100) is left to the
-    // wave-level culls: triangle soups of 256 / 1K / 4K / 16K run 2.5-5x faster culled
-    // (profiles/r01p_soup_sweep.log).
-    uint32_t ncap = 0;
-    const bool good_bvh = p.bvh_nodes && p.bvh_sah_milli <= 100;
-    const bool wq = good_bvh && wq_lds_bytes(p, &ncap, nullptr) && ncap >= kAutoWqStack && p.pc.num_meshes <= 64;
-    variant = p.cam_list_capacity < kAutoCullTris                   ? HRT_KERNEL_BUNDLE
-              : wq                                                 ? HRT_KERNEL_BUNDLE_WQ
-              : p.cam_list_capacity >= kAutoBvhTris && good_bvh    ? HRT_KERNEL_BUNDLE_BVH
-              : lds_block(p.n_tris) != 0                ? HRT_KERNEL_BUNDLE_CULL_LDS
-                                                                 : HRT_KERNEL_BUNDLE_CULL;
-  }
-  if (variant == HRT_KERNEL_BRUTE_LDS && (size_t)p.n_tris * 48 > kMaxLdsScene) variant = HRT_KERNEL_BRUTE;
-  if (variant == HRT_KERNEL_BUNDLE_BVH && (!p.bvh_nodes || p.pc.num_meshes > 64)) variant = HRT_KERNEL_BUNDLE_CULL;
-  if (variant == HRT_KERNEL_BUNDLE_CULL_LDS && lds_block(p.n_tris) == 0) variant = HRT_KERNEL_BUNDLE_CULL;
-  if (variant == HRT_KERNEL_BUNDLE_WQ && (wq_lds_bytes(p, nullptr, nullptr) == 0 || p.pc.num_meshes > 64))
-    variant = HRT_KERNEL_BUNDLE_BVH_LDS;
-  // BUNDLE_WQ_L2: the image exists (and is uploaded: this context selected the variant) and the stacks fit
-  uint32_t l2_plan[4];
-  if (variant == HRT_KERNEL_BUNDLE_WQ_L2 && (wq_l2_lds_bytes(p, l2_plan) == 0 || p.pc.num_meshes > 64))
-    variant = HRT_KERNEL_BUNDLE_BVH_LDS;
-  if (variant == HRT_KERNEL_BUNDLE_BVH_LDS && !bvh_lds_fits(p)) variant = HRT_KERNEL_BUNDLE_BVH;
-  if (variant == HRT_KERNEL_BUNDLE_BVH_LDS && (!p.bvh_nodes || p.pc.num_meshes > 64)) variant = HRT_KERNEL_BUNDLE_CULL;
-  // (the end of the chain BUNDLE_WQ / BUNDLE_WQ_L2 -> BUNDLE_BVH_LDS -> BUNDLE_BVH: without a hierarchy
-  // bvh_lds_fits is false too, and the line above no longer sees BUNDLE_BVH_LDS -- BUNDLE_BVH then ran with no
-  // nodes and faulted on a scene of more than 64 meshes)
-  if (variant == HRT_KERNEL_BUNDLE_BVH && (!p.bvh_nodes || p.pc.num_meshes > 64)) variant = HRT_KERNEL_BUNDLE_CULL;
-  if (p.pc.max_bounces < 0) variant = HRT_KERNEL_LITERAL;  // the fused loops assume >= 1 segment per path
-  return variant;
+// What a launch's plan reads of its parameters (hrt_launch_plan.h: kernel choice, LDS sizes, splitting).
+PlanScene plan_scene(const TraceParams& p) {
+  return PlanScene{p.n_tris, p.cam_list_capacity, p.pc.num_meshes, p.pc.max_bounces, p.bvh_nodes != nullptr,
+                   p.bvh_entries != nullptr, p.bvh_wq_nodes != nullptr, p.bvh_wq_nodes_bfs != nullptr, p.bvh_sah_milli,
+                   p.bvh_n_nodes, p.bvh_n_prims, p.bvh_n_meshes, p.bvh_wq_n_nodes, p.bvh_wq_width, p.bvh_max_leaf,
+                   p.bvh_node_r, p.wq_lds_nodes_opt, p.wq_ncap, p.wq_tcap};
 }
 
 static uint32_t tiles_of(const TraceParams& p) { return ((p.pc.width + 7) / 8) * ((p.local_rows + 7) / 8); }
@@ -3610,23 +3501,19 @@ static uint32_t tiles_of(const TraceParams& p) { return ((p.pc.width + 7) / 8) *
 static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
   // (q.sky_lane: requested by launch_trace; kept only for a planned launch whose work indices and item
   // count leave the queue word's halves apart)
-  const uint32_t nfr = q.n_frames > 1 ? q.n_frames : 1u;
-  const uint32_t tiles = ((q.pc.width + 7) / 8) * ((q.local_rows + 7) / 8);
+  const uint32_t nf = q.n_frames > 1 ? q.n_frames : 1u;
+  const uint32_t tiles = tiles_of(q);
   // longest-first order whenever last trace's costs are known (and tile indices fit the item word)
   const bool plan = q.plan_valid && tiles > 0 && tiles <= kItemTileMask;
   q.items = plan ? q.item_buf : nullptr;
-  if (!plan || (uint64_t)tiles * 8u * nfr >= (1ull << 31)) q.sky_lane = 0;
+  if (!plan || (uint64_t)tiles * 8u * nf >= (1ull << 31)) q.sky_lane = 0;
   const uint32_t* sky_cache = q.sky_lane ? q.tl_cache : nullptr;
   hipError_t e;
   if (plan) {
     if ((e = hipMemsetAsync(q.sched + kSchedHist, 0, 3 * kPlanBuckets * 4, stream)) != hipSuccess) return e;  // histogram, cursors
     plan_hist<<<(tiles + 255) / 256, 256, 0, stream>>>(q.sched, q.tile_cost, tiles, sky_cache);
-    // factor auto (-1): 3 when a resident wave gets more than 4 tiles, else 1 (profiles/r01k_schedule_sweep)
-    // a launch of nf frames: a resident wave's fair share is nf frames' work, i.e. waves / nf per frame
-    const uint32_t nf = q.n_frames > 1 ? q.n_frames : 1u;
-    const uint32_t waves = std::max(1u, q.num_cus * 16u / nf);
-    const uint32_t factor4 =
-        q.split_factor4 ? q.split_factor4 : 4u * (q.split_factor >= 0 ? (uint32_t)q.split_factor : tiles > 4 * waves ? 3u : 1u);
+    const uint32_t waves = plan_waves(q.num_cus, nf);
+    const uint32_t factor4 = plan_factor4(tiles, waves, SplitFactor{q.split_factor, q.split_factor4});
     plan_scan<<<1, 64, 0, stream>>>(q.sched, waves, factor4, q.split_k, q.split_prio, q.sky_lane);
     plan_fill<<<(tiles + 255) / 256, 256, 0, stream>>>(q.sched, q.tile_cost, tiles, q.split_k, q.split_prio,
                                                        q.item_buf, sky_cache);
@@ -3651,37 +3538,22 @@ hipError_t ensure_kernel_attributes(int device) {
   std::lock_guard<std::mutex> lock(mu);
   if (device < 0) return hipErrorInvalidDevice;
   if ((size_t)device < done.size() && done[(size_t)device]) return hipSuccess;
-  const void* brute[] = {reinterpret_cast<const void*>(&trace_brute_lds)};
-  const void* half_cu[] = {reinterpret_cast<const void*>(&trace_bundle_cull_lds<512, false>),
-                           reinterpret_cast<const void*>(&trace_bundle_cull_lds<512, true>)};
-  const void* whole_cu[] = {reinterpret_cast<const void*>(&trace_bundle_cull_lds<1024, false>),
-                            reinterpret_cast<const void*>(&trace_bundle_cull_lds<1024, true>),
-                            reinterpret_cast<const void*>(&trace_bundle_bvh_lds<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_bvh_lds<true>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq<true>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_nr<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_nr<true>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_solo),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_nr_solo),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_l2<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_l2<true>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_l2_nr<false>),
-                            reinterpret_cast<const void*>(&trace_bundle_wq_l2_nr<true>),
-                            reinterpret_cast<const void*>(&query_pairs<false, false>),
-                            reinterpret_cast<const void*>(&query_pairs<false, true>),
-                            reinterpret_cast<const void*>(&query_pairs<true, false>),
-                            reinterpret_cast<const void*>(&query_pairs<true, true>)};
-  hipError_t e;
-  for (const void* f : brute)
-    if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsScene)) != hipSuccess)
-      return e;
-  for (const void* f : half_cu)
-    if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kMaxLdsScene / 2))) !=
-        hipSuccess)
-      return e;
-  for (const void* f : whole_cu)
-    if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxLdsScene)) != hipSuccess)
+  // (BUNDLE_CULL_LDS at 512 threads runs two workgroups per CU: lds_block)
+  constexpr int kWhole = (int)kMaxLdsScene, kHalf = (int)(kMaxLdsScene / 2);
+  const auto fn = [](auto* kernel) { return reinterpret_cast<const void*>(kernel); };
+  const std::pair<const void*, int> limits[] = {{fn(&trace_brute_lds), kWhole},
+                {fn(&trace_bundle_cull_lds<512, false>), kHalf}, {fn(&trace_bundle_cull_lds<512, true>), kHalf},
+                {fn(&trace_bundle_cull_lds<1024, false>), kWhole}, {fn(&trace_bundle_cull_lds<1024, true>), kWhole},
+                {fn(&trace_bundle_bvh_lds<false>), kWhole}, {fn(&trace_bundle_bvh_lds<true>), kWhole},
+                {fn(&trace_bundle_wq<false>), kWhole}, {fn(&trace_bundle_wq<true>), kWhole},
+                {fn(&trace_bundle_wq_nr<false>), kWhole}, {fn(&trace_bundle_wq_nr<true>), kWhole},
+                {fn(&trace_bundle_wq_solo), kWhole}, {fn(&trace_bundle_wq_nr_solo), kWhole},
+                {fn(&trace_bundle_wq_l2<false>), kWhole}, {fn(&trace_bundle_wq_l2<true>), kWhole},
+                {fn(&trace_bundle_wq_l2_nr<false>), kWhole}, {fn(&trace_bundle_wq_l2_nr<true>), kWhole},
+                {fn(&query_pairs<false, false>), kWhole}, {fn(&query_pairs<false, true>), kWhole},
+                {fn(&query_pairs<true, false>), kWhole}, {fn(&query_pairs<true, true>), kWhole}};
+  for (const auto& [f, bytes] : limits)
+    if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); e != hipSuccess)
       return e;
   if (done.size() <= (size_t)device) done.resize((size_t)device + 1, 0);
   done[(size_t)device] = 1;
@@ -3691,170 +3563,68 @@ hipError_t ensure_kernel_attributes(int device) {
 #ifndef HRT_SKY_GRID
 #define HRT_SKY_GRID 1u  // trace_sky workgroups per CU
 #endif
-hipError_t launch_trace(const TraceParams& p0, int variant, hipStream_t stream, int* ran, int* block_out,
-                        const SkyLane* sky) {
+hipError_t launch_trace(const TraceParams& p0, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky) {
   TraceParams p = p0;
-  variant = resolve_variant(p, variant);
-  *ran = variant;
-  // bounce batch threshold, auto: the pair traversal's step cost scales with its rays, so BUNDLE_WQ
-  // batches earlier (28 of 64 lanes); the cull kernels test every survivor for the whole wave (48)
-  // (profiles/r01q_sec_batch_sweep.jsonl, frames in 16-frame launches); 36 for the per-node-radius
-  // kernel, whose scenes bounce far more (cave 20 / 28 / 36 / 44 / 56: 7.43 / 7.38 / 7.31 / 7.32 /
-  // 7.45 ms; island stays best at 28: profiles/r02v_ab.txt)
-  if (p.sec_batch == 0)
-    p.sec_batch = variant == HRT_KERNEL_BUNDLE_WQ || variant == HRT_KERNEL_BUNDLE_WQ_L2 ? (p.bvh_node_r ? 36u : 28u) : 48u;
-  *block_out = variant == HRT_KERNEL_BRUTE_LDS ? 1024 : 256;
-  const dim3 grid((p.pc.width + 15) / 16, (p.local_rows + 15) / 16, 1);
-  switch (variant) {
-    case HRT_KERNEL_LITERAL:
-      trace_literal<<<grid, 256, 0, stream>>>(p);
-      break;
-    case HRT_KERNEL_BRUTE_LDS: {
-      const dim3 g32((p.pc.width + 31) / 32, (p.local_rows + 31) / 32, 1);
-      trace_brute_lds<<<g32, 1024, (size_t)p.n_tris * 48, stream>>>(p);
-      break;
-    }
-    case HRT_KERNEL_BUNDLE_BVH_LDS: {
-      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
-      TraceParams q = p;
-      q.coop = 0;
-      if (q.split_k == 0) q.split_k = 1;
-      const size_t lds = bvh_lds_bytes(p);
-      if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
-      if (p.diag || p.probe)
-        trace_bundle_bvh_lds<true><<<p.num_cus, 1024, lds, stream>>>(q);
-      else
-        trace_bundle_bvh_lds<false><<<p.num_cus, 1024, lds, stream>>>(q);
-      *block_out = 1024;
-      break;
-    }
-    case HRT_KERNEL_BUNDLE_WQ: {
-      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
-      TraceParams q = p;
-      q.coop = 0;
-      // auto: a pair step's work scales with the rays in the batch, so heavy tiles (> factor x a
-      // resident wave's fair share of the work) run as 2, 4 or 8 items by cost; factor 2 when a
-      // resident wave gets more than 6 tiles (the full frame), else 3 (row partitions at N > 1)
-      // (profiles/r01o_lane_weighted_sum_factor_sweep.jsonl)
-      if (q.split_k == 0) q.split_k = 8;
-      // A launch of several frames (hrt_compute_n) splits a tile from 1.25 x a wave's share of the launch:
-      // a rank of 8 holds 1/8 of the rows but the same pixel chains, and one cave tile's frame took 18 ms
-      // against a 15 ms share, unsplit at 2 x (profiles/r06/r06aa/).  Cave's slowest rank of 8 0.88 ->
-      // 0.80 ms per frame; island, 2 and 4 ranks and whole frames within noise (r06ac, r06ad).
-      if (q.split_factor < 0 && p.n_frames > 1)
-        q.split_factor4 = 5;
-      else if (q.split_factor < 0)
-        q.split_factor = (uint64_t)tiles_of(p) * std::max(1u, p.n_frames) > 6ull * p.num_cus * 16u ? 2 : 3;
-      const size_t lds = wq_lds_bytes(p, &q.wq_ncap, &q.wq_tcap);
-      if (p.wq_ncap) q.wq_ncap = std::min(q.wq_ncap, std::max(128u, p.wq_ncap & ~63u));  // HRT_OPT_WQ_NODE_CAP
-      if (p.wq_tcap) q.wq_tcap = std::min(q.wq_tcap, std::max(128u, p.wq_tcap & ~63u));  // HRT_DEBUG_OPT_WQ_TRI_CAP
-      // The sky lane: product kernels only (diagnostics, probes and timeline builds keep every item on the
-      // main kernel), a scene without spheres (trace_fused_split's sky rule) and a planned launch
-      // (prepare_schedule).  The side stream waits for the planner kernels; the main stream waits for
-      // trace_sky before anything that follows this launch.
-      q.sky_lane = sky && sky->run && !HRT_TIMELINE && HRT_TL_PREPASS && HRT_SKY_LOOP && !(p.diag || p.probe) && p.tl_cache &&
-                           p.pc.num_spheres == 0
-                       ? 1u
-                       : 0u;
-      if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
-      if (q.sky_lane) {
-        if (hipError_t e = hipEventRecord(sky->fork, stream); e != hipSuccess) return e;
-        if (hipError_t e = hipStreamWaitEvent(sky->stream, sky->fork, 0); e != hipSuccess) return e;
-      }
-      if (p.bvh_node_r) {
-        if (p.diag || p.probe)
-          trace_bundle_wq_nr<true><<<p.num_cus, 1024, lds, stream>>>(q);
-        else if (q.sky_lane)
-          trace_bundle_wq_nr<false><<<p.num_cus, 1024, lds, stream>>>(q);
-        else
-          trace_bundle_wq_nr_solo<<<p.num_cus, 1024, lds, stream>>>(q);
-      } else if (p.diag || p.probe) {
-        trace_bundle_wq<true><<<p.num_cus, 1024, lds, stream>>>(q);
-      } else if (q.sky_lane) {
-        trace_bundle_wq<false><<<p.num_cus, 1024, lds, stream>>>(q);
-      } else {
-        trace_bundle_wq_solo<<<p.num_cus, 1024, lds, stream>>>(q);
-      }
-      if (q.sky_lane) {
-        // (after the main kernel's launch: its workgroups take their CUs first, one sky workgroup fits beside each)
-        trace_sky<<<p.num_cus * HRT_SKY_GRID, 256, 0, sky->stream>>>(q);
-        if (hipError_t e = hipEventRecord(sky->join, sky->stream); e != hipSuccess) return e;
-        if (hipError_t e = hipStreamWaitEvent(stream, sky->join, 0); e != hipSuccess) return e;
-      } else if (sky && !sky->run) {
-        trace_sky<<<1, 256, 0, sky->stream>>>(q);  // (returns at once: q.sky_lane == 0; nothing to order)
-      }
-      *block_out = 1024;
-      break;
-    }
-    case HRT_KERNEL_BUNDLE_WQ_L2: {
-      // BUNDLE_WQ's launch without the sky lane: the same planner, heavy-tile splitting and frame runs
-      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
-      TraceParams q = p;
-      q.coop = 0;
-      if (q.split_k == 0) q.split_k = 8;
-      if (q.split_factor < 0 && p.n_frames > 1)
-        q.split_factor4 = 5;
-      else if (q.split_factor < 0)
-        q.split_factor = (uint64_t)tiles_of(p) * std::max(1u, p.n_frames) > 6ull * p.num_cus * 16u ? 2 : 3;
-      uint32_t plan[4];
-      const size_t lds = wq_l2_lds_bytes(p, plan);  // (non-zero: resolve_variant)
-      q.wq_lds_nodes = plan[0];
-      q.wq_ncap = plan[1];
-      q.wq_tcap = plan[2];
-      q.sky_lane = 0;
-      if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
-      const bool d = p.diag || p.probe;
-      if (p.bvh_node_r)
-        d ? trace_bundle_wq_l2_nr<true><<<p.num_cus, 1024, lds, stream>>>(q)
-          : trace_bundle_wq_l2_nr<false><<<p.num_cus, 1024, lds, stream>>>(q);
-      else
-        d ? trace_bundle_wq_l2<true><<<p.num_cus, 1024, lds, stream>>>(q)
-          : trace_bundle_wq_l2<false><<<p.num_cus, 1024, lds, stream>>>(q);
-      *block_out = 1024;
-      break;
-    }
-    case HRT_KERNEL_BUNDLE_CULL_LDS: {
-      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
-      TraceParams q = p;
-      const uint32_t block = lds_block(p.n_tris);
-      *block_out = (int)block;
-      const size_t lds = (size_t)p.n_tris * 48 + kCoopLds;
-      if (q.split_k == 0) q.split_k = 1;  // auto: cooperative heavy tiles instead
-      q.coop = p.coop && q.split_k == 1 && p.pc.num_meshes <= 62 ? 1u : 0u;
-      if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
-      if (block == 512) {
-        if (p.diag || p.probe)
-          trace_bundle_cull_lds<512, true><<<2 * p.num_cus, 512, lds, stream>>>(q);
-        else
-          trace_bundle_cull_lds<512, false><<<2 * p.num_cus, 512, lds, stream>>>(q);
-      } else {
-        if (p.diag || p.probe)
-          trace_bundle_cull_lds<1024, true><<<p.num_cus, 1024, lds, stream>>>(q);
-        else
-          trace_bundle_cull_lds<1024, false><<<p.num_cus, 1024, lds, stream>>>(q);
-      }
-      break;
-    }
-    case HRT_KERNEL_BUNDLE:
-    case HRT_KERNEL_BUNDLE_CULL:
-    case HRT_KERNEL_BUNDLE_BVH:
-      if (p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
-      if (variant == HRT_KERNEL_BUNDLE)
-        p.diag ? trace_bundle<true><<<grid, 256, 0, stream>>>(p) : trace_bundle<false><<<grid, 256, 0, stream>>>(p);
-      else if (variant == HRT_KERNEL_BUNDLE_CULL)
-        p.diag ? trace_bundle_cull<true><<<grid, 256, 0, stream>>>(p)
-               : trace_bundle_cull<false><<<grid, 256, 0, stream>>>(p);
-      else
-        p.diag ? trace_bundle_bvh<true><<<grid, 256, 0, stream>>>(p)
-               : trace_bundle_bvh<false><<<grid, 256, 0, stream>>>(p);
-      break;
-    default:
-      trace_brute<<<grid, 256, 0, stream>>>(p);
-      break;
+  const int k = plan.kernel;
+  const KernelTraits& kt = kernel_traits(k);
+  if (p.sec_batch == 0) p.sec_batch = plan.sec_batch;
+  if (kt.camera_lists && p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
+  if (!kt.persistent) {
+    const int px = plan.block == 1024 ? 32 : 16;  // a workgroup's square of pixels
+    const dim3 grid((p.pc.width + px - 1) / px, (p.local_rows + px - 1) / px, 1);
+    void (*kernel)(TraceParams) =
+        k == HRT_KERNEL_LITERAL       ? trace_literal
+        : k == HRT_KERNEL_BRUTE_LDS   ? trace_brute_lds
+        : k == HRT_KERNEL_BUNDLE      ? (p.diag ? trace_bundle<true> : trace_bundle<false>)
+        : k == HRT_KERNEL_BUNDLE_CULL ? (p.diag ? trace_bundle_cull<true> : trace_bundle_cull<false>)
+        : k == HRT_KERNEL_BUNDLE_BVH  ? (p.diag ? trace_bundle_bvh<true> : trace_bundle_bvh<false>)
+                                      : trace_brute;
+    kernel<<<grid, plan.block, plan.lds_bytes, stream>>>(p);
+    return hipGetLastError();
+  }
+  // The persistent kernels: tile lists, this launch's scheduling parameters, the planner, then the kernel
+  if (HRT_TL_PREPASS && p.tl_cache && !p.tl_lists_ready) tile_lists<<<(tiles_of(p) + 3) / 4, 256, 0, stream>>>(p, 1u);
+  TraceParams q = p;
+  if (q.split_k == 0) q.split_k = plan.split_k;
+  // (BUNDLE_CULL_LDS's split_k 1: cooperative heavy tiles instead)
+  q.coop = k == HRT_KERNEL_BUNDLE_CULL_LDS && p.coop && q.split_k == 1 && p.pc.num_meshes <= 62;
+  if (kt.pair_traversal) {
+    const SplitFactor f = pair_split(tiles_of(p), p.n_frames, p.num_cus, q.split_factor);
+    q.split_factor = f.factor;
+    q.split_factor4 = f.factor4;
+    q.wq_ncap = plan.wq_ncap;
+    q.wq_tcap = plan.wq_tcap;
+    q.wq_lds_nodes = plan.wq_lds_nodes;
+  }
+  // The sky lane: product kernels only (diagnostics, probes and timeline builds keep every item on the
+  // main kernel), a scene without spheres (trace_fused_split's sky rule) and a planned launch
+  // (prepare_schedule).  The side stream waits for the planner kernels; the main stream waits for
+  // trace_sky before anything that follows this launch.
+  const bool d = p.diag || p.probe;
+  q.sky_lane = kt.sky_lane && sky && sky->run && !HRT_TIMELINE && HRT_TL_PREPASS && HRT_SKY_LOOP && !d && p.tl_cache &&
+               p.pc.num_spheres == 0;
+  if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
+  if (q.sky_lane) {
+    if (hipError_t e = hipEventRecord(sky->fork, stream); e != hipSuccess) return e;
+    if (hipError_t e = hipStreamWaitEvent(sky->stream, sky->fork, 0); e != hipSuccess) return e;
+  }
+  const bool nr = p.bvh_node_r != 0, lane = q.sky_lane != 0;  // (BUNDLE_WQ without the lane: the kernels outside the register cap)
+  void (*kernel)(TraceParams) =
+      k == HRT_KERNEL_BUNDLE_BVH_LDS ? (d ? trace_bundle_bvh_lds<true> : trace_bundle_bvh_lds<false>)
+      : k == HRT_KERNEL_BUNDLE_WQ && nr ? (d ? trace_bundle_wq_nr<true> : lane ? trace_bundle_wq_nr<false> : trace_bundle_wq_nr_solo)
+      : k == HRT_KERNEL_BUNDLE_WQ       ? (d ? trace_bundle_wq<true> : lane ? trace_bundle_wq<false> : trace_bundle_wq_solo)
+      : k == HRT_KERNEL_BUNDLE_WQ_L2 && nr ? (d ? trace_bundle_wq_l2_nr<true> : trace_bundle_wq_l2_nr<false>)
+      : k == HRT_KERNEL_BUNDLE_WQ_L2       ? (d ? trace_bundle_wq_l2<true> : trace_bundle_wq_l2<false>)
+      : plan.block == 512 ? (d ? trace_bundle_cull_lds<512, true> : trace_bundle_cull_lds<512, false>)  // BUNDLE_CULL_LDS
+                          : (d ? trace_bundle_cull_lds<1024, true> : trace_bundle_cull_lds<1024, false>);
+  kernel<<<plan.groups_per_cu * p.num_cus, plan.block, plan.lds_bytes, stream>>>(q);
+  if (q.sky_lane) {
+    // (after the main kernel's launch: its workgroups take their CUs first, one sky workgroup fits beside each)
+    trace_sky<<<p.num_cus * HRT_SKY_GRID, 256, 0, sky->stream>>>(q);
+    if (hipError_t e = hipEventRecord(sky->join, sky->stream); e != hipSuccess) return e;
+    if (hipError_t e = hipStreamWaitEvent(stream, sky->join, 0); e != hipSuccess) return e;
+  } else if (sky && !sky->run) {
+    trace_sky<<<1, 256, 0, sky->stream>>>(q);  // (returns at once: q.sky_lane == 0; nothing to order)
   }
   return hipGetLastError();
 }
@@ -4075,18 +3845,11 @@ __global__ __launch_bounds__(1024) void query_pairs(TraceParams P, QueryArgs Q) 
   }
 }
 
-int resolve_query_method(const TraceParams& p, int method) {
-  if (method == HRT_QUERY_AUTO) method = HRT_QUERY_BVH;
-  // (the traversals keep a ray's mesh filter in 64 bits, as the trace kernels' fallbacks say)
-  if (method == HRT_QUERY_PAIRS && (wq_lds_bytes(p, nullptr, nullptr) == 0 || p.pc.num_meshes > 64)) method = HRT_QUERY_BVH;
-  if (method == HRT_QUERY_BVH && (!p.bvh_nodes || p.pc.num_meshes > 64)) method = HRT_QUERY_SCAN;
-  return method;
-}
-
-hipError_t launch_query(const TraceParams& p0, const QueryArgs& q, int method, bool primary, hipStream_t stream) {
+hipError_t launch_query(const TraceParams& p0, const QueryArgs& q, const QueryPlan& plan, bool primary,
+                        hipStream_t stream) {
   if (q.n == 0) return hipSuccess;
   const uint32_t blocks = (q.n + 255u) / 256u;
-  switch (method) {
+  switch (plan.method) {
     case HRT_QUERY_SCAN:
       primary ? query_scan<true><<<blocks, 256, 0, stream>>>(p0, q) : query_scan<false><<<blocks, 256, 0, stream>>>(p0, q);
       break;
@@ -4094,17 +3857,16 @@ hipError_t launch_query(const TraceParams& p0, const QueryArgs& q, int method, b
       primary ? query_bvh<true><<<blocks, 256, 0, stream>>>(p0, q) : query_bvh<false><<<blocks, 256, 0, stream>>>(p0, q);
       break;
     case HRT_QUERY_PAIRS: {
+      if (plan.lds_bytes == 0) return hipErrorInvalidValue;
       TraceParams p = p0;
-      const size_t lds = wq_lds_bytes(p0, &p.wq_ncap, &p.wq_tcap);
-      if (lds == 0) return hipErrorInvalidValue;
-      if (p0.wq_ncap) p.wq_ncap = std::min(p.wq_ncap, std::max(128u, p0.wq_ncap & ~63u));  // HRT_OPT_WQ_NODE_CAP
-      if (p0.wq_tcap) p.wq_tcap = std::min(p.wq_tcap, std::max(128u, p0.wq_tcap & ~63u));  // HRT_DEBUG_OPT_WQ_TRI_CAP
+      p.wq_ncap = plan.wq_ncap;
+      p.wq_tcap = plan.wq_tcap;
       // (their dynamic-LDS limit: ensure_kernel_attributes)
       void (*kernel)(TraceParams, QueryArgs) =
           p.bvh_node_r ? (primary ? query_pairs<true, true> : query_pairs<false, true>)
                        : (primary ? query_pairs<true, false> : query_pairs<false, false>);
       const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
-      kernel<<<groups, 1024, lds, stream>>>(p, q);
+      kernel<<<groups, 1024, plan.lds_bytes, stream>>>(p, q);
       break;
     }
     default:
