@@ -189,7 +189,7 @@ DIAG_NAMES = ("primary_iters", "primary_considered", "primary_survivors", "bounc
               "shade_cycles", "bounce_stage2", "bounce_front", "bvh_trips",
               "bvh_leaf_trips", "band_scan_max", "band_scan_len", "sky_items", "sky_cycles",
               "primary_lanes", "loop_iters", "live_lanes", "wq_steps_16", "wq_steps_32", "wq_steps_48",
-              "wq_steps_64", "wq_members")
+              "wq_steps_64", "wq_members", "dir_lanes")
 SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh_built", "bvh_band_entries",
                     "bvh_sah_milli", "bvh_margin_milli")
 

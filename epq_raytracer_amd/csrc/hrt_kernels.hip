@@ -446,6 +446,116 @@ __device__ __forceinline__ bool shade_step(const Scene& sc, const hrt_push_const
   return true;
 }
 
+// shade_step in two phases (trace_fused_split).  Of a hit's shading only the new
+// direction is not needed at once: a lane that survives waits for its wave's next bounce batch, and a
+// lane that the roulette or the bounce limit ends never reads it.  shade_hit (phase A, at the hit) is
+// shade_step without adjust_dir: p.pos, emission, p.colour, the roulette on the RNG state after the
+// hit's 14 hashes (is_spec's, adjust_dir's 6 + 6 in either of its arms, the roulette's) -- none of
+// which depends on the direction.  A surviving hit keeps its old p.dir and leaves a Pending record;
+// shade_dir (phase B, once per bounce batch, all of the batch's lanes together) fetches the normal and
+// the material again and runs adjust_dir on the same inputs from the same RNG state.  normalize_fl
+// gives the same bits whichever lanes share the wave (hrt_math.h), so the direction is the one
+// shade_step computes.
+#ifndef HRT_SHADE_PREDRAW
+#define HRT_SHADE_PREDRAW 0  // 1: the RNG state before the draw in a VGPR of its own; 0: re-advanced in phase B
+#endif
+// The hit that owes a direction.  Packed (the pair-traversal kernels: a hierarchy exists, so at most 64
+// meshes and 2^26 - 1 triangles): a triangle as (mesh << 26 | triangle) + 1 in one register, as the
+// traversal's slots hold it; the capped kernels have no second VGPR to give without a scratch access in
+// the fused loop.  sphere is a lane mask, not a VGPR.
+template <bool Packed>
+struct Pending {
+  uint32_t id = 0;      // triangle (see above) or sphere index + 1; 0: nothing pending
+  uint32_t mesh = 0;    // the triangle's mesh (dead when Packed)
+  bool sphere = false;  // id is a sphere's
+#if HRT_SHADE_PREDRAW
+  uint32_t st = 0;  // state after is_spec's hash
+#endif
+  __device__ __forceinline__ uint32_t tri() const { return Packed ? (id - 1u) & 0x3FFFFFFu : id - 1u; }
+  __device__ __forceinline__ uint32_t mesh_of() const { return Packed ? (id - 1u) >> 26 : mesh; }
+};
+
+// Phase A.  last: this segment is the path's last allowed one (its new direction would be dead too).
+// Returns true when the path has ended, as shade_step does.  With HRT_SHADE_PREDRAW 0 a lane with a
+// pending direction keeps the state from before the hit, and phase B advances it by the 14 hashes.
+// A sphere's normal comes from the hit position BEFORE the invisible-light offset (which turns -0 into
+// +0 even when it adds nothing), so a sphere hit with a pending direction keeps that position in p.pos
+// and phase B applies the offset after the normal; nothing reads p.pos in between.
+template <bool Packed>
+__device__ __forceinline__ bool shade_hit(const Scene& sc, const hrt_push_constants& pc, Path& p, const Closest& c,
+                                          uint32_t& state, bool last, Pending<Packed>& pd) {
+  if (c.kind != 0) {
+    const bool sph = c.kind == 1;
+    const f3 hpos = ray_at(p.pos, p.dir, c.t);
+    const hrt_material& m = sph ? sc.spheres[c.idx].material : sc.meshes[c.mesh].material;
+    const bool invis = (m.settings[3] == 1.0f);
+    p.pos = adds(hpos, (float)(int)invis * 0.001f);
+    if (invis && p.not_visible) {
+      p.pos = hpos + p.dir * 0.001f;
+      return false;  // continue: a waiting lane with nothing pending
+    }
+    p.not_visible = false;
+    uint32_t st = state;
+    const uint32_t s1 = hash(st);  // is_spec's
+#pragma unroll
+    for (int k = 0; k < 12; ++k) hash(st);  // adjust_dir's two draws
+    const f3 emitted = ld3(m.emission) * m.emission[3];
+    p.light = p.light + emitted * p.colour;
+    p.colour = p.colour * ld3(m.colour);
+    const float prob = gmax(p.colour.x, gmax(p.colour.y, p.colour.z));
+    if (u01(hash(st)) >= prob) {
+      state = st;
+      return true;
+    }
+    p.colour = div3(p.colour, prob);
+    if (last) {
+      state = st;
+      return false;
+    }
+    if (sph) p.pos = hpos;
+    pd.id = (Packed && !sph ? (c.mesh << 26) | c.idx : c.idx) + 1u;
+    pd.mesh = c.mesh;
+    pd.sphere = sph;
+#if HRT_SHADE_PREDRAW
+    pd.st = s1;
+    state = st;
+#else
+    (void)s1;
+#endif
+    return false;
+  }
+  p.light = p.light + environment_light(pc, p.dir);
+  return true;
+}
+
+// Phase B, for the lanes of a bounce batch with a pending direction.
+template <bool Packed>
+__device__ __forceinline__ void shade_dir(const Scene& sc, Path& p, uint32_t& state, Pending<Packed>& pd) {
+  f3 n;
+  const hrt_material* mat;
+  if (pd.sphere) {
+    const hrt_sphere& s = sc.spheres[pd.id - 1u];
+    n = normalize(p.pos - ld3(s.centre));  // resolve_hit's
+    mat = &s.material;
+    p.pos = adds(p.pos, (float)(int)(s.material.settings[3] == 1.0f) * 0.001f);
+  } else {
+    const float4 nh = sc.nhat[pd.tri()];
+    n = mk(nh.x, nh.y, nh.z);
+    mat = &sc.meshes[pd.mesh_of()].material;
+  }
+  const hrt_material& m = *mat;
+#if HRT_SHADE_PREDRAW
+  uint32_t st = pd.st;
+  const bool is_spec = u01(st) < m.settings[0];
+  p.dir = adjust_dir(p.dir, n, m, is_spec, st);
+#else
+  const bool is_spec = u01(hash(state)) < m.settings[0];
+  p.dir = adjust_dir(p.dir, n, m, is_spec, state);
+  hash(state);  // the roulette's
+#endif
+  pd.id = 0u;
+}
+
 __device__ __forceinline__ void store_pixel(const TraceParams& /*P*/, uint32_t x, uint32_t lr, f3 col,
                                             uint32_t frame = 0) {
   const KArgs K = kargs();  // (once per work item)
@@ -746,6 +856,7 @@ struct Diag {
   uint32_t prim_lanes = 0, loop_iters = 0, live_lanes = 0;  // fused-loop lane use
   uint32_t wq_fill[4] = {0, 0, 0, 0};  // BUNDLE_WQ: node steps with 1-16 / 17-32 / 33-48 / 49-64 node pairs
   uint32_t wq_members = 0;             // ... the members of the groups this lane popped (valid slots), summed
+  uint32_t dir_lanes = 0;              // lanes whose direction a bounce batch computed (shade_dir)
 };
 
 __device__ __forceinline__ float wave_min_all(float v) {  // all 64 lanes active
@@ -2432,6 +2543,10 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
   int sample = 0;
   Path p;
   p.bounce = pc.max_bounces + 1;
+  // the direction a surviving hit still owes (shade_hit / shade_dir).  Set only in a lane that then waits
+  // (0 < p.bounce <= max_bounces) and cleared by the batch every waiting lane joins, so it ends before
+  // the lane's next sample, pixel-frame or frame; an item's idle lanes never shade.
+  Pending<is_wq(Bounce)> pd;
   bool done = !active;
   Diag dg;
   // Frame runs (tile_loop): the item's frames frame .. frame + nrun - 1 of a multi-frame launch, one
@@ -2527,7 +2642,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     const bool run_sec = nwait > 0 && (nwait >= sec_thresh || !any_prim);
     const bool sec = waiting && run_sec;
     Closest c{kFltMax, 0, 0u, 0u};
-    uint64_t t0 = 0, t1 = 0, t2 = 0;
+    uint64_t t0 = 0, t1 = 0, t2 = 0, tb = 0;
     if (D && P.diag) {
       dg.prim_iters += any_prim ? 1u : 0u;
       dg.sec_iters += run_sec ? 1u : 0u;
@@ -2551,6 +2666,10 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     }
     if (D && P.diag) t1 = __builtin_readcyclecounter();
     if (run_sec) {
+      const bool owed = sec && pd.id != 0u;
+      if (D && P.diag) dg.dir_lanes += (uint32_t)__popcll(__ballot(owed));
+      if (owed) shade_dir(kscene(), p, state, pd);
+      if (D && P.diag) tb = __builtin_readcyclecounter() - t1;  // (shading's clocks)
       if (HRT_BOUNCE_PRIO && !co.hot) __builtin_amdgcn_s_setprio(HRT_BOUNCE_PRIO);
       if constexpr (is_wq(Bounce)) {
         world_hit_bounce_wq<D, is_wq_node_r(Bounce)>(kscene(), P, bsrc, sec, p.pos, p.dir, tests,
@@ -2567,7 +2686,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (D && P.diag) t2 = __builtin_readcyclecounter();
     if (prim || sec) {
       ++segs;
-      const bool ended = shade_step(kscene(), pc, p, c, state);
+      const bool ended = shade_hit(kscene(), pc, p, c, state, p.bounce >= pc.max_bounces, pd);
       ++p.bounce;
       if (ended || p.bounce > pc.max_bounces) {
         colour = colour + p.light * p.colour;
@@ -2577,8 +2696,8 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     if (D && P.diag) {
       const uint64_t t3 = __builtin_readcyclecounter();
       dg.cyc_prim += t1 - t0;
-      dg.cyc_sec += t2 - t1;
-      dg.cyc_shade += t3 - t2;
+      dg.cyc_sec += t2 - t1 - tb;
+      dg.cyc_shade += t3 - t2 + tb;
     }
   }
   if (co.w != 0) return;  // cooperative tile: wave 0 of the group writes the results
@@ -2641,6 +2760,7 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     }
   }
   if (D && P.diag && is_wq(Bounce) && dg.wq_members) atomicAdd(&P.diag[28], (unsigned long long)dg.wq_members);
+  if (D && P.diag && dg.dir_lanes && (threadIdx.x & 63) == 0) atomicAdd(&P.diag[29], (unsigned long long)dg.dir_lanes);
   if (D && P.diag && (Bounce == kBounceBvh || is_wq(Bounce))) {
     atomicAdd(&P.diag[7], (unsigned long long)dg.bvh_visits);
     atomicAdd(&P.diag[8], (unsigned long long)dg.bvh_prims);

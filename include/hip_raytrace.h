@@ -51,6 +51,7 @@ extern "C" {
  * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
  * 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
  * hrt_present_info, hrt_present, hrt_accumulate_present, hrt_present_done, hrt_present_wait.
+ * 6, additive (no bump: hrt_get_diagnostics takes the caller's count): HRT_DIAG_DIR_LANES (HRT_NUM_DIAG 30).
  * 6 (r06): hrt_release_caches; HRT_DEBUG_OPT_STACK_LIMIT.
  * 5 (r05): HRT_DIAG_WQ_STEPS_* / WQ_MEMBERS (HRT_NUM_DIAG 29), HRT_DEBUG_OPT_TIMELINE + hrt_debug_timeline.
  * 4 (r04): hrt_debug_wq_protocol; hrt_stats.last_frames; HRT_DIAG_SKY_* / PRIMARY_LANES / LOOP_ITERS /
@@ -491,7 +492,8 @@ typedef enum hrt_diag {
   HRT_DIAG_WQ_STEPS_48 = 26,       /* ... 33-48 */
   HRT_DIAG_WQ_STEPS_64 = 27,       /* ... 49-64 */
   HRT_DIAG_WQ_MEMBERS = 28,        /* ... valid members of the popped node groups, summed (vs 4 slots each) */
-  HRT_NUM_DIAG = 29
+  HRT_DIAG_DIR_LANES = 29,         /* bounce-batch lanes whose direction the batch computed (two-phase shading) */
+  HRT_NUM_DIAG = 30
 } hrt_diag;
 
 /* What hrt_set_scene built for BUNDLE_BVH (hrt_get_scene_info). */
