@@ -482,6 +482,8 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->query_rays);
   free_dev(ctx, ctx->query_hits);
   free_dev(ctx, ctx->query_stats);
+  free_dev(ctx, ctx->occl_bits);
+  free_dev(ctx, ctx->occl_stats);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -1184,6 +1186,83 @@ extern "C" hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_con
   }
   const uint32_t rect[3] = {x0, y0, w};
   return run_query(ctx, p, nullptr, (uint32_t)n, rect, method, hits, stats, "hrt_intersect_primary");
+}
+
+// Any hit, one bit per ray.  A chunk of staged rays or bits is kQueryChunk rays -- a multiple
+// of 64, so every launch but the last fills whole words (2,048 per chunk) and a wave's two words never
+// straddle two launches.
+extern "C" hrt_status hrt_occluded(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n, uint32_t method,
+                                   uint32_t* bits, hrt_occlusion_stats* stats) {
+  static_assert(kQueryChunk % 64u == 0 && kQueryLaunch % 64u == 0, "a launch's first ray is a multiple of 64");
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (!known_query_method(method)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: unknown method");
+  if (!ctx->scene_set) return fail(ctx, HRT_ERR_NO_SCENE, "hrt_occluded: hrt_set_scene has not been called");
+  if (n > 0 && (!rays || !bits)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: null rays or bits");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  hrt_push_constants pc{};
+  pc.width = ctx->width;
+  pc.height = ctx->height;
+  pc.num_spheres = (int32_t)ctx->scene.n_spheres;
+  pc.num_meshes = (int32_t)ctx->scene.n_meshes;
+  hrt::TraceParams p = make_params(ctx, &pc, 0);
+  const hrt::QueryPlan plan = hrt::plan_query(hrt::plan_scene(p), (int)method);
+  if (n == 0) {
+    if (stats) *stats = hrt_occlusion_stats{(uint32_t)plan.method, 0u, 0u, 0u, 0u};
+    return HRT_OK;
+  }
+  // a query writes no image, counter or planner buffer of the context
+  p.img8 = nullptr;
+  p.img32 = nullptr;
+  p.counters = nullptr;
+  p.diag = nullptr;
+  p.tile_cycles = nullptr;
+  p.sky_units = nullptr;
+  p.timeline = nullptr;
+  p.timeline_count = nullptr;
+  const bool rays_direct = query_direct(ctx, rays), bits_direct = query_direct(ctx, bits);
+  if (rays_direct && (uintptr_t)rays % 16 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: device rays must be 16-byte aligned");
+  if (bits_direct && (uintptr_t)bits % 4 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: device bits must be 4-byte aligned");
+  auto ensure = [&](void** buf, size_t bytes) -> hrt_status {
+    if (*buf) return HRT_OK;
+    if (hrt::dev_alloc(ctx, buf, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ctx, HRT_ERR_OUT_OF_MEMORY, "hrt_occluded: staging allocation failed");
+    }
+    return HRT_OK;
+  };
+  if (!rays_direct && (st = ensure(&ctx->query_rays, (size_t)kQueryChunk * sizeof(hrt_ray_query))) != HRT_OK) return st;
+  if (!bits_direct && (st = ensure(&ctx->occl_bits, (size_t)(kQueryChunk / 32u) * sizeof(uint32_t))) != HRT_OK) return st;
+  if (stats) {
+    if ((st = ensure(reinterpret_cast<void**>(&ctx->occl_stats), 3 * sizeof(unsigned long long))) != HRT_OK) return st;
+    HRT_HIP(ctx, hipMemsetAsync(ctx->occl_stats, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  }
+  const uint32_t chunk = (rays_direct && bits_direct) ? kQueryLaunch : kQueryChunk;
+  for (uint32_t at = 0; at < n; at += std::min(chunk, n - at)) {
+    const uint32_t m = std::min(chunk, n - at), words = (m + 31u) / 32u;
+    hrt::QueryArgs q{};
+    if (rays_direct) {
+      q.rays = reinterpret_cast<const float4*>(rays + at);
+    } else {
+      HRT_HIP(ctx, hipMemcpyAsync(ctx->query_rays, rays + at, (size_t)m * sizeof(hrt_ray_query), hipMemcpyDefault,
+                                  ctx->stream));
+      q.rays = static_cast<const float4*>(ctx->query_rays);
+    }
+    q.stats = stats ? ctx->occl_stats : nullptr;
+    q.n = m;
+    uint32_t* out = bits_direct ? bits + at / 32u : static_cast<uint32_t*>(ctx->occl_bits);
+    HRT_HIP(ctx, hrt::launch_occluded(p, q, out, plan, ctx->stream));
+    if (!bits_direct)
+      HRT_HIP(ctx, hipMemcpyAsync(bits + at / 32u, ctx->occl_bits, (size_t)words * sizeof(uint32_t), hipMemcpyDefault,
+                                  ctx->stream));
+  }
+  unsigned long long counts[3] = {0, 0, 0};
+  if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->occl_stats, sizeof(counts), hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) *stats = hrt_occlusion_stats{(uint32_t)plan.method, 0u, counts[0], counts[1], counts[2]};
+  return HRT_OK;
 }
 
 // The frame stack's allocation (the debug build can make it fail above HRT_DEBUG_OPT_STACK_LIMIT bytes).

@@ -217,6 +217,10 @@ struct hrt_context {
   void* query_rays = nullptr;
   void* query_hits = nullptr;
   unsigned long long* query_stats = nullptr;
+  // Occlusion queries (hrt_occluded): staging for a chunk's bits (kQueryChunk / 32 words) when the caller's
+  // are host memory, and the three statistics words
+  void* occl_bits = nullptr;
+  unsigned long long* occl_stats = nullptr;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

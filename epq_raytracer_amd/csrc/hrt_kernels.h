@@ -159,5 +159,10 @@ struct QueryArgs {
 };
 // Launches q.n rays as p's plan_query says; p.pc holds the sphere / mesh counts (and, primary, the camera).
 hipError_t launch_query(const TraceParams& p, const QueryArgs& q, const QueryPlan& plan, bool primary, hipStream_t stream);
+// Occlusion queries (hrt_occluded): any hit of q.n caller rays (q.rays; q.hits unused), ray i
+// as bit i & 31 of bits[i >> 5]: ceil(q.n / 32) words, each written in full.  q.stats: [0], [1] as above,
+// [2] the rays whose bit is 1; or nullptr.
+hipError_t launch_occluded(const TraceParams& p, const QueryArgs& q, uint32_t* bits, const QueryPlan& plan,
+                           hipStream_t stream);
 
 }  // namespace hrt

@@ -904,6 +904,16 @@ __device__ __forceinline__ void spheres_first(const Scene& sc, const hrt_push_co
     if (t > 0.001f && t < c.t) c = Closest{t, 1, (uint32_t)i, 0u};
   }
 }
+// ... with the running closest started at `best` (the any-hit traversals of the occlusion queries).
+__device__ __forceinline__ void spheres_first(const Scene& sc, const hrt_push_constants& pc, bool sel, f3 o, f3 d,
+                                              Closest& c, float best) {
+  if (!sel) return;
+  c = Closest{best, 0, 0u, 0u};
+  for (int i = 0; i < pc.num_spheres; ++i) {
+    const float t = sphere_dist(sc.spheres[i], o, d);
+    if (t > 0.001f && t < c.t) c = Closest{t, 1, (uint32_t)i, 0u};
+  }
+}
 
 // Read-only scene data seen through the constant address space: a load with a wave-uniform address
 // from it is a scalar (s_load) load.
@@ -1516,6 +1526,10 @@ struct BvhGlobal {
     bvh_prim_test(prims, k, mask, o, d, c, bkey, best_k);
   }
 };
+// The same source for an ANY-HIT traversal (occluded_bvh): world_hit_bounce_bvh then starts the
+// running closest at the c.t it is called with (the ray's min(t_max, FLT_MAX)) instead of FLT_MAX, and a lane
+// that has accepted anything leaves its loops.  c.kind != 0 is the answer; c is otherwise not a closest hit.
+struct BvhGlobalAny : BvhGlobal {};
 struct BvhLds {  // nodes and the triangle image in LDS; entry k = triangle | mesh << 26, key = kbase[m] + triangle
   const float4* nodes;
   const float4* tris;
@@ -1596,7 +1610,11 @@ template <bool D, class Bvh>
 __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const TraceParams& P, const Bvh& bvh, bool sec,
                                                      f3 o, f3 d, uint32_t& tests, Closest& c, Diag& dg) {
   const hrt_push_constants& pc = P.pc;
-  spheres_first(sc, pc, sec, o, d, c);
+  constexpr bool kAny = std::is_same<Bvh, BvhGlobalAny>::value;
+  if constexpr (kAny)
+    spheres_first(sc, pc, sec, o, d, c, c.t);
+  else
+    spheres_first(sc, pc, sec, o, d, c);
   unsigned long long mask = 0ull;
   if (sec) {
     for (int m = 0; m < pc.num_meshes; ++m) {
@@ -1611,6 +1629,10 @@ __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const Trac
   float best_k = c.t * kOnePlus;
   for (uint32_t k = 0; k < P.bvh_n_irregular; ++k)
     if (sec) bvh_prim_test(P.bvh_irregular, k, mask, o, d, c, bkey, best_k);
+  // (any hit: a lane already answered by a sphere or the irregular list skips the band and the nodes; its
+  // meshes' lengths are counted above whatever it skips)
+  if constexpr (kAny)
+    if (c.kind != 0) mask = 0ull;
   const f3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
   float R = 0.0f;
   if (P.bvh_n_nodes) {  // farthest root-box corner from the origin, rounded up
@@ -1646,14 +1668,20 @@ __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const Trac
           ++band_tests;
         }
       }
+      if constexpr (kAny)
+        if (c.kind != 0) break;
     }
     for (; k < b1; ++k) {
+      if constexpr (kAny)
+        if (c.kind != 0) break;
       const uint32_t q = band_entry(P.bvh_band, P.bvh_band_wide, k);
       if (bc.in(P.bvh_band_nhat[q])) {
         bvh.prim(q, mask, o, d, c, bkey, best_k);
         ++band_tests;
       }
     }
+    if constexpr (kAny)
+      if (c.kind != 0) node = end;
   }
   uint32_t trips = 0, leaf_trips = 0;  // wave-level loop iterations (diagnostics)
   while (node < end) {
@@ -1673,6 +1701,8 @@ __device__ __forceinline__ void world_hit_bounce_bvh(const Scene& sc, const Trac
       prim_tests += count;
     }
     node = (visit && !count) ? node + 1 : esc;
+    if constexpr (kAny)
+      if (c.kind != 0) node = end;
   }
   if (D && P.diag) {
     dg.bvh_visits += visits;
@@ -1965,6 +1995,23 @@ __device__ __forceinline__ void wq_leaf_prim(const float4* __restrict__ pr, cons
                                              unsigned long long mask, f3 o, f3 d) {
   wq_tri_test(wq_tri_rec(pr, k), wq, r, mask, o, d);
 }
+// The LDS source for an ANY-HIT pair traversal (occluded_pairs).  world_hit_bounce_wq then seeds
+// a ray's slot with the c.t it is called with (the ray's min(t_max, FLT_MAX)) and id 0, and a triangle pair
+// that accepts a hit lowers the slot to t = +0 with its (nonzero) id: no genuine t is that low (dist > 0.001),
+// so the ray's later node pairs keep no member and its later triangle pairs are dropped -- its remaining
+// pairs drain without pushing anything.  id != 0 is the answer; the slot's t is no hit distance.
+struct WqLdsAny : WqLds {};
+__device__ __forceinline__ void wq_leaf_prim(const float4* __restrict__ pr, const WqLdsAny& wq, uint32_t k, uint32_t r,
+                                             unsigned long long mask, f3 o, f3 d) {
+  const WqTriRec t = wq_tri_rec(pr, k);
+  const uint32_t m = __builtin_bit_cast(uint32_t, t.B.w);
+  const float st = wq_slot_t(wq, r);
+  float dist;
+  if (st > 0.0f && wq_tri_accept(t.A, t.B, t.C, t.N, o, d, st * kOnePlus, dist) && dist < st && ((mask >> m) & 1ull)) {
+    const uint32_t id = ((m << 26) | __builtin_bit_cast(uint32_t, t.C.w)) + 1u;
+    wq_slot_lower(wq.slot, r, (unsigned long long)id);
+  }
+}
 
 
 // The grazing-band lists of a wave's lanes laid end to end (world_hit_bounce_wq): lane l's list of n
@@ -2034,7 +2081,11 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   const float4* prims = K->bvh_prims;
   const float rel_t = K->bvh_rel_t, abs_coef = K->bvh_abs_coef;
   const uint32_t tcap = K->wq_tcap;
-  spheres_first(sc, pc, sec, o, d, c);
+  constexpr bool kAny = std::is_same<Src, WqLdsAny>::value;  // any hit (wq_leaf_prim's overload)
+  if constexpr (kAny)
+    spheres_first(sc, pc, sec, o, d, c, c.t);
+  else
+    spheres_first(sc, pc, sec, o, d, c);
   const f3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);  // the meshes' AABB tests and the traversal
   unsigned long long mask = 0ull;
   if (sec) {
@@ -2053,6 +2104,10 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
   const float4* irr = K->bvh_irregular;
   for (uint32_t k = 0; k < n_irr; ++k)
     if (sec) bvh_prim_test(irr, k, mask, o, d, c, bkey, best_k);
+  // (any hit: a ray already answered by a sphere or the irregular list enters the traversal as an inactive
+  // ray -- no band list, no root pair; its meshes' lengths are counted above)
+  if constexpr (kAny)
+    if (c.kind != 0) mask = 0ull;
   float R;
   {  // farthest root-box corner from the origin, rounded up
     float4 R0, R1;
@@ -2246,13 +2301,15 @@ __device__ __forceinline__ void world_hit_bounce_wq(const Scene& sc, const Trace
           A00 = na0[0], A01 = na0[1], A02 = na0[2], B00 = nb0[0], B01 = nb0[1], B02 = nb0[2];
         }
         // (both pairs up front: 24 more live VGPRs, scratch 92 -> 160 B with spills in the fused loop)
-        const float t_hi = wq_slot_t(wq, r) * (1.0f + rel_t) + rabs;
+        float t_any = 1.0f;  // any hit: the slot's t, +0 once the ray is answered (then no member is kept)
+        if constexpr (kAny) t_any = wq_slot_t(wq, r);
+        const float t_hi = (kAny ? t_any : wq_slot_t(wq, r)) * (1.0f + rel_t) + rabs;
         auto member = [&](const float4& N0, const float4& N1, const float4& N2, int k, bool valid = true) {
           float tnear;
           const uint32_t inf = __builtin_bit_cast(uint32_t, N2.w);
           // the outcome as selects: no branch, and the info word arrives with the record (a branch let
           // hipcc sink its LDS read into the kept path: one more dependent round trip per member)
-          const bool vis = wq_member_visit<NodeR>(N0, N1, N2, rq, t_hi, tnear) & valid;
+          const bool vis = wq_member_visit<NodeR>(N0, N1, N2, rq, t_hi, tnear) & valid & (!kAny || t_any > 0.0f);
           const bool leaf = (inf >> 27) != 0u;
           li[k] = (vis & leaf) ? inf : 0u;
           pe[k] = (vis & !leaf) ? ((inf << 6) | r) : ~0u;
@@ -3652,6 +3709,9 @@ static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
 // pre-existing kernel's code is what it is without the query kernels.
 template <bool Primary, bool NodeR>
 __global__ void query_pairs(TraceParams P, QueryArgs Q);
+// The occlusion queries' PAIRS kernel, declared here for the same two reasons (profiles/occlusion_resources.txt).
+template <bool NodeR>
+__global__ void occluded_pairs(TraceParams P, QueryArgs Q, uint32_t* bits);
 hipError_t ensure_kernel_attributes(int device) {
   static std::mutex mu;
   static std::vector<char> done;
@@ -3671,7 +3731,8 @@ hipError_t ensure_kernel_attributes(int device) {
                 {fn(&trace_bundle_wq_l2<false>), kWhole}, {fn(&trace_bundle_wq_l2<true>), kWhole},
                 {fn(&trace_bundle_wq_l2_nr<false>), kWhole}, {fn(&trace_bundle_wq_l2_nr<true>), kWhole},
                 {fn(&query_pairs<false, false>), kWhole}, {fn(&query_pairs<false, true>), kWhole},
-                {fn(&query_pairs<true, false>), kWhole}, {fn(&query_pairs<true, true>), kWhole}};
+                {fn(&query_pairs<true, false>), kWhole}, {fn(&query_pairs<true, true>), kWhole},
+                {fn(&occluded_pairs<false>), kWhole}, {fn(&occluded_pairs<true>), kWhole}};
   for (const auto& [f, bytes] : limits)
     if (hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); e != hipSuccess)
       return e;
@@ -3987,6 +4048,126 @@ hipError_t launch_query(const TraceParams& p0, const QueryArgs& q, const QueryPl
                        : (primary ? query_pairs<true, false> : query_pairs<false, false>);
       const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
       kernel<<<groups, 1024, plan.lds_bytes, stream>>>(p, q);
+      break;
+    }
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// ---- occlusion queries: any hit of caller rays, one bit per ray -------------------
+// occluded(i) = (the query above, same ray and method, returns kind != 0).  One ray per lane; a wave owns 64
+// consecutive rays whose first index is a multiple of 64, and so two words of the output: it forms them with
+// a ballot, and lanes 0 and 1 store one each (a word is written iff its first ray is below n; rays past n
+// contribute 0 bits).  The three methods:
+//   SCAN   world_hit_scan_from(...).kind != 0 -- the yardstick, no early exit;
+//   BVH    world_hit_bounce_bvh over BvhGlobalAny: closest seeded with the ray's best, lanes leave at a hit;
+//   PAIRS  world_hit_bounce_wq over WqLdsAny: slot seeded with best, lowered to +0 at a hit.
+// Exactness: every cull proves "the scan rejects this triangle given a running closest of c";
+// the seeded scan's running closest never exceeds best, so until a hit is found nothing with 0.001 < dist <
+// best behind its mesh's gate is culled, and after one the answer is 1 whatever else is skipped.
+// ALL 64 lanes.
+__device__ __forceinline__ void occluded_store(const QueryArgs& Q, uint32_t* bits, uint32_t i, const QueryRay& r,
+                                               bool occ, uint32_t tests) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long b = __ballot(occ && i < Q.n);
+  const uint32_t first = (i - lane) + 32u * lane;  // lanes 0, 1: the first ray of the wave's two words
+  if (lane < 2u && first < Q.n) bits[first >> 5] = (uint32_t)(b >> (32u * lane));
+  if (Q.stats) {
+    unsigned long long s = (r.live && !r.finite) ? 1u : 0u, t = tests;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      s += __shfl_xor(s, off, 64);
+      t += __shfl_xor(t, off, 64);
+    }
+    if (lane == 0 && (s | t | b)) {
+      if (s) atomicAdd(&Q.stats[0], s);
+      if (t) atomicAdd(&Q.stats[1], t);
+      if (b) atomicAdd(&Q.stats[2], (unsigned long long)__popcll(b));
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void occluded_scan(TraceParams P, QueryArgs Q, uint32_t* bits) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const QueryRay r = query_ray<false>(P, Q, i);
+  uint32_t tests = 0;
+  bool occ = false;
+  if (r.live) occ = world_hit_scan_from(sc, P.pc.num_spheres, P.pc.num_meshes, r.o, r.d, r.best, tests).kind != 0;
+  occluded_store(Q, bits, i, r, occ, tests);
+}
+
+// a traversal's answer, or the literal scan's for a ray outside the traversals' domain
+__device__ __forceinline__ bool occluded_finish(const Scene& sc, const TraceParams& P, const QueryRay& r, bool trav,
+                                                const Closest& c, uint32_t& tests) {
+  if (r.live && !r.finite)
+    return world_hit_scan_from(sc, P.pc.num_spheres, P.pc.num_meshes, r.o, r.d, r.best, tests).kind != 0;
+  return trav && c.kind != 0;
+}
+
+__global__ __launch_bounds__(256) void occluded_bvh(TraceParams P, QueryArgs Q, uint32_t* bits) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const QueryRay r = query_ray<false>(P, Q, i);
+  const bool trav = r.live && r.finite;
+  const f3 o = trav ? r.o : mk(0.0f, 0.0f, 0.0f), d = trav ? r.d : mk(0.0f, 0.0f, 1.0f);
+  uint32_t tests = 0;
+  Closest c{r.best, 0, 0u, 0u};  // (the seed: BvhGlobalAny)
+  Diag dg;
+  world_hit_bounce_bvh<false>(sc, P, BvhGlobalAny{{P.bvh_nodes, P.bvh_prims}}, trav, o, d, tests, c, dg);
+  const bool occ = occluded_finish(sc, P, r, trav, c, tests);
+  occluded_store(Q, bits, i, r, occ, tests);
+}
+
+// PAIRS: carved exactly as query_pairs.
+template <bool NodeR>
+__global__ __launch_bounds__(1024) void occluded_pairs(TraceParams P, QueryArgs Q, uint32_t* bits) {
+  const uint32_t nn = P.bvh_wq_n_nodes;
+  float4* nodes = lds_tris;
+  for (uint32_t k = threadIdx.x; k < 3 * nn; k += 1024) nodes[k] = P.bvh_wq_nodes[k];
+  const uint32_t wave = threadIdx.x >> 6;
+  char* base = reinterpret_cast<char*>(nodes + 3 * nn) + (size_t)wave * (512 + 4 * (P.wq_ncap + P.wq_tcap));
+  const WqLdsAny wq{{nodes, reinterpret_cast<unsigned long long*>(base), reinterpret_cast<uint32_t*>(base + 512),
+                     reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap, false}};
+  __syncthreads();
+  // (wave-uniform trip count: i - lane is the wave's first ray, a multiple of 64)
+  for (uint32_t w0 = blockIdx.x * 1024u + wave * 64u; w0 < Q.n; w0 += gridDim.x * 1024u) {
+    const uint32_t i = w0 + (threadIdx.x & 63u);
+    const QueryRay r = query_ray<false>(P, Q, i);
+    const bool trav = r.live && r.finite;
+    const f3 o = trav ? r.o : mk(0.0f, 0.0f, 0.0f), d = trav ? r.d : mk(0.0f, 0.0f, 1.0f);
+    uint32_t tests = 0;
+    Closest c{r.best, 0, 0u, 0u};  // (the seed: WqLdsAny)
+    Diag dg;
+    world_hit_bounce_wq<false, NodeR>(kscene(), P, wq, trav, o, d, tests, c, dg);
+    const Scene sc = kscene();
+    const bool occ = occluded_finish(sc, P, r, trav, c, tests);
+    occluded_store(Q, bits, i, r, occ, tests);
+  }
+}
+
+hipError_t launch_occluded(const TraceParams& p0, const QueryArgs& q, uint32_t* bits, const QueryPlan& plan,
+                           hipStream_t stream) {
+  if (q.n == 0) return hipSuccess;
+  const uint32_t blocks = (q.n + 255u) / 256u;
+  switch (plan.method) {
+    case HRT_QUERY_SCAN:
+      occluded_scan<<<blocks, 256, 0, stream>>>(p0, q, bits);
+      break;
+    case HRT_QUERY_BVH:
+      occluded_bvh<<<blocks, 256, 0, stream>>>(p0, q, bits);
+      break;
+    case HRT_QUERY_PAIRS: {
+      if (plan.lds_bytes == 0) return hipErrorInvalidValue;
+      TraceParams p = p0;
+      p.wq_ncap = plan.wq_ncap;
+      p.wq_tcap = plan.wq_tcap;
+      // (their dynamic-LDS limit: ensure_kernel_attributes)
+      void (*kernel)(TraceParams, QueryArgs, uint32_t*) = p.bvh_node_r ? occluded_pairs<true> : occluded_pairs<false>;
+      const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
+      kernel<<<groups, 1024, plan.lds_bytes, stream>>>(p, q, bits);
       break;
     }
     default:

@@ -341,6 +341,37 @@ class HrtContext:
         hits = hits.reshape(h, w)
         return (hits, st) if with_stats else hits
 
+    # ---- occlusion queries (hrt_occluded) ----
+
+    def occluded_into(self, rays_ptr: int, n: int, bits_ptr: int, method: int = _lib.QUERY_AUTO,
+                      with_stats: bool = False):
+        """hrt_occluded on caller memory: n hrt_ray_query records at rays_ptr -> ceil(n / 32) uint32 words at
+        bits_ptr, ray i as bit i & 31 of word i >> 5 (host pointers, or pointers into the context's device:
+        rays 16-byte, bits 4-byte aligned, e.g. a torch tensor's data_ptr()).  Blocking.  Returns the call's
+        _lib.OcclusionStats when with_stats, else None."""
+        st = _lib.OcclusionStats()
+        self._check(self.lib.hrt_occluded(self.handle, ctypes.c_void_p(rays_ptr), int(n), int(method),
+                                          ctypes.c_void_p(bits_ptr), ctypes.byref(st) if with_stats else None),
+                    "hrt_occluded")
+        return st if with_stats else None
+
+    def occluded(self, rays, method: int = _lib.QUERY_AUTO, with_stats: bool = False, packed: bool = False):
+        """hrt_occluded: whether anything lies on each ray before its t_max -- True iff
+        ``intersect`` of the same ray returns kind != 0 -- as a bool array of len(rays).  ``rays``: a
+        _lib.RAY_QUERY_DTYPE array (``ray_queries``), or a torch tensor of n x 8 float32 on the host or on the
+        context's device (anything with data_ptr() and shape).  packed=True returns the ceil(n / 32) uint32
+        words instead (ray i: bit i & 31 of word i >> 5).  with_stats=True returns (result,
+        _lib.OcclusionStats)."""
+        if hasattr(rays, "data_ptr"):
+            n, rays_ptr = int(rays.shape[0]), int(rays.data_ptr())
+        else:
+            rays = np.ascontiguousarray(rays, dtype=_lib.RAY_QUERY_DTYPE)
+            n, rays_ptr = len(rays), rays.ctypes.data
+        words = np.zeros((n + 31) // 32, np.uint32)
+        st = self.occluded_into(rays_ptr if n else 0, n, words.ctypes.data if n else 0, method, with_stats)
+        out = words if packed else np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+        return (out, st) if with_stats else out
+
     def check_guards(self):
         """libhip_raytrace_debug.so: (guarded device buffers, buffers whose guard bands were overwritten)."""
         n, bad = ctypes.c_uint32(), ctypes.c_uint32()
@@ -515,6 +546,22 @@ class RayTracePipeline:
         trace-image coordinates; the present pass flips rows, so a pixel of a presented height-H target is
         row H - 1 - y here."""
         return self.first_hits(camera, (int(x), int(y), 1, 1))[0, 0]
+
+    @staticmethod
+    def segment_rays(a, b) -> np.ndarray:
+        """The rays of the segments a[i] -> b[i] (_lib.RAY_QUERY_DTYPE): origin a, direction b - a, t_max =
+        |b - a|, every step in binary32 (the squares summed x, y, z in order, then the square root)."""
+        a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+        d = b - a
+        sq = d * d
+        length = np.sqrt((sq[:, 0] + sq[:, 1]) + sq[:, 2], dtype=np.float32)
+        return HrtContext.ray_queries(a, d, length)
+
+    def visible(self, a, b, method: int = _lib.QUERY_AUTO) -> np.ndarray:
+        """Whether b[i] is visible from a[i]: nothing of the scene on the open segment between them that the
+        reference's world_hit accepts (0.001 < dist < |b - a|).  ~occluded(segment_rays(a, b))."""
+        return ~self.ctx.occluded(self.segment_rays(a, b), method)
 
     def init(self) -> None:
         self.ctx.trace(self.push_constants(Camera(), 0, True))

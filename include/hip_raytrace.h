@@ -41,7 +41,8 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): HRT_KERNEL_BUNDLE_WQ_L2, HRT_OPT_WQ_LDS_NODES,
+/* 6, additive (no bump: nothing existing changed): occlusion queries -- hrt_occlusion_stats, hrt_occluded.
+ * 6, additive (no bump: nothing existing changed): HRT_KERNEL_BUNDLE_WQ_L2, HRT_OPT_WQ_LDS_NODES,
  * hrt_debug_bvh_wq_nodes_bfs, hrt_debug_wq_l2_plan.
  * 6, additive (no bump: nothing existing changed): ray queries -- hrt_ray_query, hrt_hit, hrt_query_stats,
  * hrt_query_method, hrt_intersect, hrt_intersect_primary.
@@ -255,6 +256,16 @@ typedef enum hrt_query_method {
   HRT_QUERY_PAIRS = 3  /* the pair traversal, 64 rays per wave (BVH when its node image does not fit) */
 } hrt_query_method;
 
+/* ---- occlusion queries (hrt_occluded) ---- */
+typedef struct hrt_occlusion_stats {
+  uint32_t method_ran; /* as hrt_query_stats */
+  uint32_t reserved;   /* 0 */
+  uint64_t scan_rays;  /* as hrt_query_stats */
+  uint64_t tri_tests;  /* as hrt_query_stats: the sum over live rays of len of every mesh whose AABB test passes --
+                          by definition, whatever the traversal skipped after a hit */
+  uint64_t occluded;   /* rays whose bit is 1 */
+} hrt_occlusion_stats;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -296,6 +307,10 @@ HRT_STATIC_ASSERT(sizeof(hrt_hit) == 32 && offsetof(hrt_hit, kind) == 4 && offse
 HRT_STATIC_ASSERT(sizeof(hrt_query_stats) == 24 && offsetof(hrt_query_stats, scan_rays) == 8 &&
                       offsetof(hrt_query_stats, tri_tests) == 16,
                   "hrt_query_stats");
+HRT_STATIC_ASSERT(sizeof(hrt_occlusion_stats) == 32 && offsetof(hrt_occlusion_stats, reserved) == 4 &&
+                      offsetof(hrt_occlusion_stats, scan_rays) == 8 && offsetof(hrt_occlusion_stats, tri_tests) == 16 &&
+                      offsetof(hrt_occlusion_stats, occluded) == 24,
+                  "hrt_occlusion_stats");
 
 typedef struct hrt_context hrt_context;
 
@@ -575,6 +590,21 @@ hrt_status hrt_intersect(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n
  * HRT_ERR_INVALID_ARGUMENT. */
 hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_constants* pc, uint32_t x0, uint32_t y0,
                                  uint32_t w, uint32_t h, uint32_t method, hrt_hit* hits, hrt_query_stats* stats);
+
+/* Any hit of caller rays, one bit per ray: ray i is occluded iff hrt_intersect on the same
+ * context, ray and method returns kind != 0 -- a sphere or triangle exists that world_hit accepts with
+ * 0.001 < dist < min(t_max, FLT_MAX), behind the meshes' AABB test.  Ray i is bit i & 31 of word i >> 5; the call
+ * writes exactly ceil(n / 32) words, each in full, the unused high bits of the last one 0, and nothing beyond
+ * them.  Methods, fallbacks and AUTO as hrt_intersect; every method gives the same bits.  The traversals stop
+ * a ray at its first accepted hit and start its running closest at min(t_max, FLT_MAX), so a short segment
+ * walks only the hierarchy near it.  BLOCKING; ordered on the context's stream after the work issued so far;
+ * touches no trace lane, image, hrt_stats, fold record or ticket.  rays: host memory (staged in chunks) or
+ * memory of the context's device (then 16-byte aligned); bits: host memory or memory of the context's device
+ * (then 4-byte aligned).  stats may be NULL.  n == 0: OK, nothing written.  HRT_ERR_INVALID_ARGUMENT (unknown
+ * method, NULL rays / bits with n > 0, a misaligned device pointer) and HRT_ERR_NO_SCENE are decided before
+ * anything is enqueued. */
+hrt_status hrt_occluded(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n, uint32_t method, uint32_t* bits,
+                        hrt_occlusion_stats* stats);
 
 /* The records of the newest min(cap, available) folds (HRT_OPT_FOLD_RECORDS = 1), oldest first; the ring
  * keeps the last HRT_FOLD_RECORD_RING.  Folds deferred combines and synchronizes the context, as

@@ -27,6 +27,7 @@
 #define HRT_APP_HPP
 
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <functional>
@@ -392,6 +393,42 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
   std::vector<hrt_hit> first_hits(const Camera& camera) const { return first_hits(camera, 0, 0, size_[0], size_[1]); }
   // What lies under pixel (x, y) of the view (trace-image coordinates: row height - 1 - y of a presented target).
   hrt_hit pick(const Camera& camera, uint32_t x, uint32_t y) const { return first_hits(camera, x, y, 1, 1)[0]; }
+  // Occlusion queries (hrt_occluded; not a reference feature).  occluded(rays)[i]: something of the scene lies
+  // on ray i before its t_max -- true iff hrt_intersect of the same ray returns kind != 0.
+  std::vector<bool> occluded(const std::vector<hrt_ray_query>& rays, uint32_t method = HRT_QUERY_AUTO) const {
+    std::vector<uint32_t> words((rays.size() + 31) / 32);
+    check(hrt_occluded(ctx_->get(), rays.data(), (uint32_t)rays.size(), method, words.data(), nullptr), "hrt_occluded",
+          ctx_->get());
+    std::vector<bool> out(rays.size());
+    for (size_t i = 0; i < rays.size(); ++i) out[i] = ((words[i >> 5] >> (i & 31)) & 1u) != 0;
+    return out;
+  }
+  // The ray of the segment a -> b: origin a, direction b - a, t_max = |b - a|, every step in binary32 (the
+  // squares summed x, y, z in order, then the square root).
+  static hrt_ray_query segment_ray(const Vec3& a, const Vec3& b) {
+    hrt_ray_query r{};
+    float sq[3];
+    for (int k = 0; k < 3; ++k) {
+      r.origin[k] = a[k];
+      r.direction[k] = b[k] - a[k];
+      sq[k] = r.direction[k] * r.direction[k];
+    }
+    const float s01 = sq[0] + sq[1];
+    const float s = s01 + sq[2];
+    r.t_max = std::sqrt(s);
+    return r;
+  }
+  // visible(from, to)[i]: nothing of the scene on the open segment from[i] -> to[i] that the reference's
+  // world_hit accepts (0.001 < dist < |to - from|): the complement of occluded() on the segments' rays.
+  std::vector<bool> visible(const std::vector<Vec3>& from, const std::vector<Vec3>& to,
+                            uint32_t method = HRT_QUERY_AUTO) const {
+    if (from.size() != to.size()) throw std::invalid_argument("visible: from and to differ in length");
+    std::vector<hrt_ray_query> rays(from.size());
+    for (size_t i = 0; i < from.size(); ++i) rays[i] = segment_ray(from[i], to[i]);
+    std::vector<bool> out = occluded(rays, method);
+    out.flip();
+    return out;
+  }
   Context& context() const { return *ctx_; }
   std::array<uint32_t, 2> image_size() const { return size_; }
 
