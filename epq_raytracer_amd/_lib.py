@@ -127,6 +127,18 @@ class OcclusionStats(ctypes.Structure):
 
 
 assert ctypes.sizeof(OcclusionStats) == 32
+
+
+class RadianceStats(ctypes.Structure):
+    """hrt_radiance_stats: what one hrt_radiance call ran (32 bytes)."""
+
+    _fields_ = [("method_ran", c_uint32), ("reserved", c_uint32), ("scan_segments", c_uint64), ("segments", c_uint64),
+                ("tri_tests", c_uint64)]
+
+
+assert ctypes.sizeof(RadianceStats) == 32
+RADIANCE_QUERY_DTYPE = np.dtype([("origin", "<f4", 3), ("seed", "<u4"), ("centre", "<f4", 3), ("reserved", "<u4")])
+assert RADIANCE_QUERY_DTYPE.itemsize == 32
 assert ctypes.sizeof(RayQuery) == 32 and ctypes.sizeof(Hit) == 32 and ctypes.sizeof(QueryStats) == 24
 RAY_QUERY_DTYPE = np.dtype([("origin", "<f4", 3), ("t_max", "<f4"), ("direction", "<f4", 3), ("reserved", "<u4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("mesh", "<u4"), ("normal", "<f4", 3),
@@ -204,7 +216,7 @@ SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh
 # Every symbol include/*.h declares (tests/test_abi.py checks the export table against this).
 EXPORTED_SYMBOLS = (
     "hrt_abi_version", "hrt_build_id", "hrt_debug_build", "hrt_debug_check_guards", "hrt_create", "hrt_destroy", "hrt_set_scene", "hrt_trace", "hrt_accumulate", "hrt_compute_n",
-    "hrt_compute_until", "hrt_get_fold_records", "hrt_intersect", "hrt_intersect_primary", "hrt_occluded",
+    "hrt_compute_until", "hrt_get_fold_records", "hrt_intersect", "hrt_intersect_primary", "hrt_occluded", "hrt_radiance",
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
@@ -268,6 +280,7 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_intersect_primary": (c_int32, [P, POINTER(PushConstants), c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                             P, POINTER(QueryStats)]),
         "hrt_occluded": (c_int32, [P, P, c_uint32, c_uint32, P, POINTER(OcclusionStats)]),
+        "hrt_radiance": (c_int32, [P, POINTER(PushConstants), P, c_uint32, c_uint32, P, POINTER(RadianceStats)]),
         "hrt_read_image": (c_int32, [P, c_uint32, c_uint32, P, c_size_t]),
         "hrt_load_accumulator": (c_int32, [P, c_uint32, P, c_size_t]),
         "hrt_get_layout": (c_int32, [P, POINTER(Layout)]),

@@ -484,6 +484,8 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->query_stats);
   free_dev(ctx, ctx->occl_bits);
   free_dev(ctx, ctx->occl_stats);
+  free_dev(ctx, ctx->rad_out);
+  free_dev(ctx, ctx->rad_words);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -751,15 +753,21 @@ extern "C" hrt_status hrt_set_scene(hrt_context* ctx, const hrt_ray* rays, uint3
 
 namespace {
 
+// The scene and the counts of a push block: everything of check_dispatch but the image size (hrt_radiance).
+hrt_status check_counts(hrt_context* ctx, const hrt_push_constants* pc, const char* who) {
+  if (!ctx->scene_set) return fail(ctx, HRT_ERR_NO_SCENE, std::string(who) + ": hrt_set_scene has not been called");
+  if (pc->num_spheres < 0 || (uint32_t)pc->num_spheres > ctx->scene.n_spheres || pc->num_meshes < 0 ||
+      (uint32_t)pc->num_meshes > ctx->scene.n_meshes)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": num_spheres/num_meshes exceed the uploaded scene");
+  return HRT_OK;
+}
+
 // Validates a dispatch's push block against the context (hrt_trace / hrt_compute_n).
 hrt_status check_dispatch(hrt_context* ctx, const hrt_push_constants* pc, const char* who) {
   if (!ctx->scene_set) return fail(ctx, HRT_ERR_NO_SCENE, std::string(who) + ": hrt_set_scene has not been called");
   if (pc->width != ctx->width || pc->height != ctx->height)
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": push constant width/height differ from the context");
-  if (pc->num_spheres < 0 || (uint32_t)pc->num_spheres > ctx->scene.n_spheres || pc->num_meshes < 0 ||
-      (uint32_t)pc->num_meshes > ctx->scene.n_meshes)
-    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": num_spheres/num_meshes exceed the uploaded scene");
-  return HRT_OK;
+  return check_counts(ctx, pc, who);
 }
 
 // The image a trace writes: the one place that fills TraceParams' (RGBA8 pointer, RGBA32F pointer) pair.
@@ -1073,12 +1081,8 @@ bool query_direct(hrt_context* ctx, const void* p) {
   return (at.type == hipMemoryTypeDevice && at.device == ctx->device) || at.type == hipMemoryTypeManaged;
 }
 
-// n rays (rays, or, when rays is null, the primary rays k = 0 .. n - 1 of rect) -> hits, blocking.  Every
-// argument has been checked; p.pc holds the counts (and the camera).
-hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* rays, uint32_t n, const uint32_t rect[3],
-                     uint32_t method, hrt_hit* hits, hrt_query_stats* stats, const char* who) {
-  const bool primary = rays == nullptr;
-  // a query writes no image, counter or planner buffer of the context
+// A query writes no image, counter or planner buffer of the context.
+void query_only(hrt::TraceParams& p) {
   p.img8 = nullptr;
   p.img32 = nullptr;
   p.counters = nullptr;
@@ -1087,18 +1091,29 @@ hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* 
   p.sky_units = nullptr;
   p.timeline = nullptr;
   p.timeline_count = nullptr;
+}
+
+// A staging or statistics buffer of the queries, allocated at its first use (the context's allocator).
+hrt_status ensure_staging(hrt_context* ctx, void** buf, size_t bytes, const char* who) {
+  if (*buf) return HRT_OK;
+  if (hrt::dev_alloc(ctx, buf, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(ctx, HRT_ERR_OUT_OF_MEMORY, std::string(who) + ": staging allocation failed");
+  }
+  return HRT_OK;
+}
+
+// n rays (rays, or, when rays is null, the primary rays k = 0 .. n - 1 of rect) -> hits, blocking.  Every
+// argument has been checked; p.pc holds the counts (and the camera).
+hrt_status run_query(hrt_context* ctx, hrt::TraceParams p, const hrt_ray_query* rays, uint32_t n, const uint32_t rect[3],
+                     uint32_t method, hrt_hit* hits, hrt_query_stats* stats, const char* who) {
+  const bool primary = rays == nullptr;
+  query_only(p);
   const hrt::QueryPlan plan = hrt::plan_query(hrt::plan_scene(p), (int)method);
   const bool rays_direct = primary || query_direct(ctx, rays), hits_direct = query_direct(ctx, hits);
   if ((!primary && rays_direct && (uintptr_t)rays % 16 != 0) || (hits_direct && (uintptr_t)hits % 16 != 0))
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": device rays / hits must be 16-byte aligned");
-  auto ensure = [&](void** buf, size_t bytes) -> hrt_status {
-    if (*buf) return HRT_OK;
-    if (hrt::dev_alloc(ctx, buf, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, HRT_ERR_OUT_OF_MEMORY, std::string(who) + ": staging allocation failed");
-    }
-    return HRT_OK;
-  };
+  auto ensure = [&](void** buf, size_t bytes) { return ensure_staging(ctx, buf, bytes, who); };
   hrt_status st;
   if (!rays_direct && (st = ensure(&ctx->query_rays, (size_t)kQueryChunk * sizeof(hrt_ray_query))) != HRT_OK) return st;
   if (!hits_direct && (st = ensure(&ctx->query_hits, (size_t)kQueryChunk * sizeof(hrt_hit))) != HRT_OK) return st;
@@ -1211,28 +1226,13 @@ extern "C" hrt_status hrt_occluded(hrt_context* ctx, const hrt_ray_query* rays, 
     if (stats) *stats = hrt_occlusion_stats{(uint32_t)plan.method, 0u, 0u, 0u, 0u};
     return HRT_OK;
   }
-  // a query writes no image, counter or planner buffer of the context
-  p.img8 = nullptr;
-  p.img32 = nullptr;
-  p.counters = nullptr;
-  p.diag = nullptr;
-  p.tile_cycles = nullptr;
-  p.sky_units = nullptr;
-  p.timeline = nullptr;
-  p.timeline_count = nullptr;
+  query_only(p);
   const bool rays_direct = query_direct(ctx, rays), bits_direct = query_direct(ctx, bits);
   if (rays_direct && (uintptr_t)rays % 16 != 0)
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: device rays must be 16-byte aligned");
   if (bits_direct && (uintptr_t)bits % 4 != 0)
     return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_occluded: device bits must be 4-byte aligned");
-  auto ensure = [&](void** buf, size_t bytes) -> hrt_status {
-    if (*buf) return HRT_OK;
-    if (hrt::dev_alloc(ctx, buf, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, HRT_ERR_OUT_OF_MEMORY, "hrt_occluded: staging allocation failed");
-    }
-    return HRT_OK;
-  };
+  auto ensure = [&](void** buf, size_t bytes) { return ensure_staging(ctx, buf, bytes, "hrt_occluded"); };
   if (!rays_direct && (st = ensure(&ctx->query_rays, (size_t)kQueryChunk * sizeof(hrt_ray_query))) != HRT_OK) return st;
   if (!bits_direct && (st = ensure(&ctx->occl_bits, (size_t)(kQueryChunk / 32u) * sizeof(uint32_t))) != HRT_OK) return st;
   if (stats) {
@@ -1262,6 +1262,63 @@ extern "C" hrt_status hrt_occluded(hrt_context* ctx, const hrt_ray_query* rays, 
   if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->occl_stats, sizeof(counts), hipMemcpyDefault, ctx->stream));
   HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (stats) *stats = hrt_occlusion_stats{(uint32_t)plan.method, 0u, counts[0], counts[1], counts[2]};
+  return HRT_OK;
+}
+
+// The path tracer for caller-chosen samples.  Staged records use the ray queries'
+// buffer (both records are 32 bytes); ctx->rad_words holds the call's three counts and, after them, the PAIRS
+// kernel's query counter, which launch_radiance zeroes before every launch.
+extern "C" hrt_status hrt_radiance(hrt_context* ctx, const hrt_push_constants* pc, const hrt_radiance_query* queries,
+                                   uint32_t n, uint32_t method, float* rgba, hrt_radiance_stats* stats) {
+  static_assert(sizeof(hrt_radiance_query) == sizeof(hrt_ray_query), "one staging buffer for both");
+  if (!ctx || !pc) return HRT_ERR_INVALID_ARGUMENT;
+  if (!known_query_method(method)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_radiance: unknown method");
+  if (pc->init) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_radiance: pc->init must be 0");
+  hrt_status st = check_counts(ctx, pc, "hrt_radiance");
+  if (st != HRT_OK) return st;
+  if (n > 0 && (!queries || !rgba)) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_radiance: null queries or rgba");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  hrt::TraceParams p = make_params(ctx, pc, 0);
+  // AUTO: the pair traversal when it fits -- every segment after a query's first is a bounce ray (§26)
+  const hrt::QueryPlan plan =
+      hrt::plan_query(hrt::plan_scene(p), method == HRT_QUERY_AUTO ? (int)HRT_QUERY_PAIRS : (int)method);
+  if (n == 0) {
+    if (stats) *stats = hrt_radiance_stats{(uint32_t)plan.method, 0u, 0u, 0u, 0u};
+    return HRT_OK;
+  }
+  query_only(p);
+  const bool q_direct = query_direct(ctx, queries), out_direct = query_direct(ctx, rgba);
+  if ((q_direct && (uintptr_t)queries % 16 != 0) || (out_direct && (uintptr_t)rgba % 16 != 0))
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_radiance: device queries / rgba must be 16-byte aligned");
+  auto ensure = [&](void** buf, size_t bytes) { return ensure_staging(ctx, buf, bytes, "hrt_radiance"); };
+  if (!q_direct && (st = ensure(&ctx->query_rays, (size_t)kQueryChunk * sizeof(hrt_radiance_query))) != HRT_OK) return st;
+  if (!out_direct && (st = ensure(&ctx->rad_out, (size_t)kQueryChunk * 4 * sizeof(float))) != HRT_OK) return st;
+  if ((st = ensure(reinterpret_cast<void**>(&ctx->rad_words), 4 * sizeof(unsigned long long))) != HRT_OK) return st;
+  if (stats) HRT_HIP(ctx, hipMemsetAsync(ctx->rad_words, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  const uint32_t chunk = (q_direct && out_direct) ? kQueryLaunch : kQueryChunk;
+  for (uint32_t at = 0; at < n; at += std::min(chunk, n - at)) {
+    const uint32_t m = std::min(chunk, n - at);
+    hrt::RadianceArgs q{};
+    if (q_direct) {
+      q.queries = reinterpret_cast<const float4*>(queries + at);
+    } else {
+      HRT_HIP(ctx, hipMemcpyAsync(ctx->query_rays, queries + at, (size_t)m * sizeof(hrt_radiance_query),
+                                  hipMemcpyDefault, ctx->stream));
+      q.queries = static_cast<const float4*>(ctx->query_rays);
+    }
+    q.out = out_direct ? reinterpret_cast<float4*>(rgba + 4 * (size_t)at) : static_cast<float4*>(ctx->rad_out);
+    q.stats = stats ? ctx->rad_words : nullptr;
+    q.next = reinterpret_cast<uint32_t*>(ctx->rad_words + 3);
+    q.n = m;
+    HRT_HIP(ctx, hrt::launch_radiance(p, q, plan, ctx->stream));
+    if (!out_direct)
+      HRT_HIP(ctx, hipMemcpyAsync(rgba + 4 * (size_t)at, ctx->rad_out, (size_t)m * 4 * sizeof(float), hipMemcpyDefault,
+                                  ctx->stream));
+  }
+  unsigned long long counts[3] = {0, 0, 0};
+  if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->rad_words, sizeof(counts), hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) *stats = hrt_radiance_stats{(uint32_t)plan.method, 0u, counts[0], counts[1], counts[2]};
   return HRT_OK;
 }
 

@@ -221,6 +221,10 @@ struct hrt_context {
   // are host memory, and the three statistics words
   void* occl_bits = nullptr;
   unsigned long long* occl_stats = nullptr;
+  // Radiance queries (hrt_radiance): staging for a chunk's results (kQueryChunk x 16 bytes) when the caller's
+  // are host memory, and four words: the three statistics counts, then the PAIRS kernel's query counter
+  void* rad_out = nullptr;
+  unsigned long long* rad_words = nullptr;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

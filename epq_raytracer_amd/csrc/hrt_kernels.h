@@ -164,5 +164,17 @@ hipError_t launch_query(const TraceParams& p, const QueryArgs& q, const QueryPla
 // [2] the rays whose bit is 1; or nullptr.
 hipError_t launch_occluded(const TraceParams& p, const QueryArgs& q, uint32_t* bits, const QueryPlan& plan,
                            hipStream_t stream);
+// Radiance queries (hrt_radiance): the reference's main() for n caller records.  Query i
+// is queries[2 i] = (origin, seed bits), queries[2 i + 1] = (centre, -) (hrt_radiance_query); its result
+// (colour / num_samples, 1.0) goes to out[i] as one 16-byte store.  p.pc is the caller's push block.
+struct RadianceArgs {
+  const float4* queries;
+  float4* out;
+  unsigned long long* stats;  // [0] segments the literal scan answered (irregular), [1] segments, [2] triangle
+                              // tests; or nullptr
+  uint32_t* next;             // PAIRS: the launch's query counter (zero when the launch starts)
+  uint32_t n;                 // queries of this launch
+};
+hipError_t launch_radiance(const TraceParams& p, const RadianceArgs& q, const QueryPlan& plan, hipStream_t stream);
 
 }  // namespace hrt

@@ -3702,6 +3702,12 @@ static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
 
 // The persistent kernels' dynamic-LDS limits, set once per device (hrt_create calls this for its device;
 // the attribute is per device, so every device a context lives on gets its own call).
+// The radiance queries' PAIRS kernel (defined at the end of the file), declared here for the two reasons given
+// for query_pairs below -- and AHEAD of it, in this order and in the list's: declared and listed after
+// occluded_pairs, its instantiations brought the extra address computation back into the six trace_bundle_wq*,
+// the four trace_bundle_wq_l2* and the four query_pairs kernels (profiles/radiance_resources.txt, 5).
+template <bool NodeR, bool Stats>
+__global__ void radiance_pairs(TraceParams P, RadianceArgs Q);
 // The ray queries' PAIRS kernel (defined at the end of the file).  Declared here so that the list below can
 // take its instantiations' addresses -- and keep it here: it also fixes where the compiler emits them.  With
 // the kernel first used at the end of the file, hipcc compiled the six trace_bundle_wq* kernels' triangle step
@@ -3730,6 +3736,8 @@ hipError_t ensure_kernel_attributes(int device) {
                 {fn(&trace_bundle_wq_solo), kWhole}, {fn(&trace_bundle_wq_nr_solo), kWhole},
                 {fn(&trace_bundle_wq_l2<false>), kWhole}, {fn(&trace_bundle_wq_l2<true>), kWhole},
                 {fn(&trace_bundle_wq_l2_nr<false>), kWhole}, {fn(&trace_bundle_wq_l2_nr<true>), kWhole},
+                {fn(&radiance_pairs<false, false>), kWhole}, {fn(&radiance_pairs<false, true>), kWhole},
+                {fn(&radiance_pairs<true, false>), kWhole}, {fn(&radiance_pairs<true, true>), kWhole},
                 {fn(&query_pairs<false, false>), kWhole}, {fn(&query_pairs<false, true>), kWhole},
                 {fn(&query_pairs<true, false>), kWhole}, {fn(&query_pairs<true, true>), kWhole},
                 {fn(&occluded_pairs<false>), kWhole}, {fn(&occluded_pairs<true>), kWhole}};
@@ -4168,6 +4176,249 @@ hipError_t launch_occluded(const TraceParams& p0, const QueryArgs& q, uint32_t* 
       void (*kernel)(TraceParams, QueryArgs, uint32_t*) = p.bvh_node_r ? occluded_pairs<true> : occluded_pairs<false>;
       const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
       kernel<<<groups, 1024, plan.lds_bytes, stream>>>(p, q, bits);
+      break;
+    }
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// ---- radiance queries: the reference's main() for caller records ------------------
+// out[i] = (sum over num_samples of trace_ray(origin, normalize(get_ray_dir(pc, centre, state)), state) /
+// num_samples, 1.0) with state started at the record's seed: a pixel of a frame is the record (cam_pos,
+// rng_offset * 719393 + id, ray centre id).  One query per lane.  Every SEGMENT takes S11's test -- origin
+// finite, direction finite with dot(d, d) normal and finite -- and one that fails it is answered by the literal
+// scan whatever the method (stats[0]); the three methods feed the others to world_hit's three implementations:
+//   SCAN   trace_literal's loops over world_hit_scan_from and shade_step -- the yardstick;
+//   BVH    the same loop wave-converged, one world_hit_bounce_bvh per trip;
+//   PAIRS  trace_fused_split's loop without tile lists: every segment through world_hit_bounce_wq, shading in
+//          two phases, lanes refilled from one grid-wide query counter.
+// A query's result is a function of its record alone (its own RNG chain, its samples in order), so which lane
+// or wave runs it, and in whose company, cannot show in the bytes.
+struct RadianceRecord {
+  f3 origin, centre;
+  uint32_t seed;
+};
+__device__ __forceinline__ RadianceRecord radiance_record(const RadianceArgs& Q, uint32_t i) {
+  const float4 a = Q.queries[2 * (size_t)i], b = Q.queries[2 * (size_t)i + 1];
+  return RadianceRecord{mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), fbits(a.w)};
+}
+// S11's test of one segment (d: the direction the segment is traced with)
+__device__ __forceinline__ bool segment_regular(f3 o, f3 d) {
+  const float d2 = dot(d, d);
+  return finite3(o) && finite3(d) && d2 >= 0x1p-126f && d2 <= kFltMax;
+}
+// The wave's share of the call's three counts: one atomic each.  ALL 64 lanes.
+__device__ __forceinline__ void radiance_counts(unsigned long long* stats, uint32_t scan, uint32_t segs, uint32_t tests) {
+  if (!stats) return;
+  unsigned long long s, t, a = scan;
+  uint32_t mx;
+  wave_counters(segs, tests, s, t, mx);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+  if ((threadIdx.x & 63u) == 0) {
+    if (a) atomicAdd(&stats[0], a);
+    if (s) atomicAdd(&stats[1], s);
+    if (t) atomicAdd(&stats[2], t);
+  }
+}
+
+__global__ __launch_bounds__(256) void radiance_scan(TraceParams P, RadianceArgs Q) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const hrt_push_constants& pc = P.pc;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  uint32_t scan = 0, segs = 0, tests = 0;
+  if (i < Q.n) {
+    const RadianceRecord q = radiance_record(Q, i);
+    f3 colour = mk(0.0f, 0.0f, 0.0f);
+    uint32_t state = q.seed;
+    for (int s = 0; s < pc.num_samples; ++s) {
+      const f3 dir = get_ray_dir(pc, q.centre, state);
+      Path p{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), q.origin, normalize(dir), 0, true};
+      for (int b = 0; b <= pc.max_bounces; ++b) {
+        if (!segment_regular(p.pos, p.dir)) ++scan;
+        const Closest c = world_hit_scan_from(sc, pc.num_spheres, pc.num_meshes, p.pos, p.dir, kFltMax, tests);
+        ++segs;
+        if (shade_step(sc, pc, p, c, state)) break;
+      }
+      colour = colour + p.light * p.colour;
+    }
+    colour = div3(colour, (float)pc.num_samples);
+    Q.out[i] = make_float4(colour.x, colour.y, colour.z, 1.0f);
+  }
+  radiance_counts(Q.stats, scan, segs, tests);
+}
+
+__global__ __launch_bounds__(256) void radiance_bvh(TraceParams P, RadianceArgs Q) {
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  const hrt_push_constants& pc = P.pc;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool live = i < Q.n;
+  RadianceRecord q{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), 0u};
+  if (live) q = radiance_record(Q, i);
+  uint32_t scan = 0, segs = 0, tests = 0;
+  f3 colour = mk(0.0f, 0.0f, 0.0f);
+  uint32_t state = q.seed;
+  int sample = 0;
+  Path p{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 1.0f), 0, true};
+  p.bounce = pc.max_bounces + 1;  // no path under way
+  bool done = !live;
+  while (__any(!done)) {
+    if (!done && p.bounce > pc.max_bounces) {
+      if (sample >= pc.num_samples) {
+        done = true;
+      } else {
+        ++sample;
+        const f3 dir = get_ray_dir(pc, q.centre, state);
+        p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), q.origin, normalize(dir), 0, true};
+        if (pc.max_bounces < 0) colour = colour + p.light * p.colour;  // trace_ray's loop does not run
+      }
+    }
+    // (lanes without a regular segment due enter as inactive rays, as query_bvh's tail lanes do)
+    const bool seg = !done && p.bounce <= pc.max_bounces;
+    const bool reg = seg && segment_regular(p.pos, p.dir);
+    const f3 o = reg ? p.pos : mk(0.0f, 0.0f, 0.0f), d = reg ? p.dir : mk(0.0f, 0.0f, 1.0f);
+    Closest c{kFltMax, 0, 0u, 0u};
+    Diag dg;
+    world_hit_bounce_bvh<false>(sc, P, BvhGlobal{P.bvh_nodes, P.bvh_prims}, reg, o, d, tests, c, dg);
+    if (seg && !reg) {
+      c = world_hit_scan_from(sc, pc.num_spheres, pc.num_meshes, p.pos, p.dir, kFltMax, tests);
+      ++scan;
+    }
+    if (seg) {
+      ++segs;
+      const bool ended = shade_step(sc, pc, p, c, state);
+      ++p.bounce;
+      if (ended || p.bounce > pc.max_bounces) {
+        colour = colour + p.light * p.colour;
+        p.bounce = pc.max_bounces + 1;
+      }
+    }
+  }
+  if (live) {
+    colour = div3(colour, (float)pc.num_samples);
+    Q.out[i] = make_float4(colour.x, colour.y, colour.z, 1.0f);
+  }
+  radiance_counts(Q.stats, scan, segs, tests);
+}
+
+// PAIRS: LDS carved exactly as query_pairs carves it; persistent workgroups.  A lane holds one query at a time
+// (its index, the colour so far, the sample count, the path) and reads its record again at each sample's
+// start.  Each trip of a wave: lanes whose query is complete store it; the idle lanes draw the next indices
+// from Q.next -- one atomicAdd by the first idle lane for all of them, handed out in lane order -- until the
+// counter has passed n (then `dry`, wave-uniform: no further atomics); lanes between paths start their next
+// sample; lanes that owe a direction compute it (shade_dir); ALL 64 lanes enter the traversal, those without a
+// regular segment due as inactive rays; irregular segments take the scan; every lane with a segment shades
+// its hit (shade_hit).  Q.next never exceeds n + 64 x the grid's waves (a wave overshoots once), and a launch
+// has n <= 2^31 (launch_radiance), so it does not wrap.
+template <bool NodeR, bool Stats>
+__global__ __launch_bounds__(1024) void radiance_pairs(TraceParams P, RadianceArgs Q) {
+  const uint32_t nn = P.bvh_wq_n_nodes;
+  float4* nodes = lds_tris;
+  for (uint32_t k = threadIdx.x; k < 3 * nn; k += 1024) nodes[k] = P.bvh_wq_nodes[k];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  char* base = reinterpret_cast<char*>(nodes + 3 * nn) + (size_t)wave * (512 + 4 * (P.wq_ncap + P.wq_tcap));
+  const WqLds wq{nodes, reinterpret_cast<unsigned long long*>(base), reinterpret_cast<uint32_t*>(base + 512),
+                 reinterpret_cast<uint32_t*>(base + 512) + P.wq_ncap, P.wq_ncap, false};
+  __syncthreads();
+  const hrt_push_constants& pc = P.pc;
+  uint32_t scan = 0, segs = 0, tests = 0;
+  uint32_t qi = 0, state = 0;
+  bool have = false, dry = false;
+  f3 colour = mk(0.0f, 0.0f, 0.0f);
+  int sample = 0;
+  Path p{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 1.0f), 0, true};
+  p.bounce = pc.max_bounces + 1;  // no path under way
+  Pending<true> pd;  // set only in a lane that then has a segment due, cleared by the next trip's shade_dir
+  for (;;) {
+    // (a loop: with num_samples <= 0 a query just drawn is complete at once and must still be stored)
+    for (;;) {
+      if (have && p.bounce > pc.max_bounces && sample >= pc.num_samples) {
+        const f3 r = div3(colour, (float)pc.num_samples);
+        Q.out[qi] = make_float4(r.x, r.y, r.z, 1.0f);
+        have = false;
+      }
+      const unsigned long long nb = __ballot(!have);
+      if (dry || !nb) break;
+      const uint32_t cnt = (uint32_t)__popcll(nb), first = (uint32_t)__ffsll((long long)nb) - 1u;
+      uint32_t got = 0;
+      if (lane == first) got = atomicAdd(Q.next, cnt);
+      const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)got, (int)first);
+      dry = at >= Q.n || Q.n - at <= cnt;
+      const uint32_t idx = at + lanes_below(nb);
+      if (!have && idx < Q.n) {
+        have = true;
+        qi = idx;
+        state = fbits(Q.queries[2 * (size_t)idx].w);
+        colour = mk(0.0f, 0.0f, 0.0f);
+        sample = 0;
+      }
+    }
+    if (!__any(have)) break;
+    if (have && p.bounce > pc.max_bounces) {  // (sample < num_samples: the query is not complete)
+      ++sample;
+      const RadianceRecord q = radiance_record(Q, qi);
+      // the matrix and jitter read at the sample's start (kargs): not held in SGPRs across the loop
+      const f3 dir = get_ray_dir(kargs()->pc, q.centre, state);
+      p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), q.origin, normalize_fl(dir), 0, true};
+      if (pc.max_bounces < 0) colour = colour + p.light * p.colour;  // trace_ray's loop does not run
+    }
+    const bool seg = have && p.bounce <= pc.max_bounces;
+    if (__any(seg)) {
+      if (seg && pd.id != 0u) shade_dir(kscene(), p, state, pd);
+      const bool reg = seg && segment_regular(p.pos, p.dir);
+      const f3 o = reg ? p.pos : mk(0.0f, 0.0f, 0.0f), d = reg ? p.dir : mk(0.0f, 0.0f, 1.0f);
+      Closest c{kFltMax, 0, 0u, 0u};
+      Diag dg;
+      world_hit_bounce_wq<false, NodeR>(kscene(), P, wq, reg, o, d, tests, c, dg);
+      if (seg && !reg) {
+        const Scene sc = kscene();
+        c = world_hit_scan_from(sc, pc.num_spheres, pc.num_meshes, p.pos, p.dir, kFltMax, tests);
+        ++scan;
+      }
+      if (seg) {
+        ++segs;
+        const bool ended = shade_hit(kscene(), pc, p, c, state, p.bounce >= pc.max_bounces, pd);
+        ++p.bounce;
+        if (ended || p.bounce > pc.max_bounces) {
+          colour = colour + p.light * p.colour;
+          p.bounce = pc.max_bounces + 1;
+        }
+      }
+      // a segment adds fewer than 2^26 tests (a hierarchy exists): flushed long before a lane's count wraps
+      if (Stats && __any(tests >= 0x80000000u)) {
+        radiance_counts(Q.stats, scan, segs, tests);
+        scan = segs = tests = 0;
+      }
+    }
+  }
+  if (Stats) radiance_counts(Q.stats, scan, segs, tests);
+}
+
+hipError_t launch_radiance(const TraceParams& p0, const RadianceArgs& q, const QueryPlan& plan, hipStream_t stream) {
+  if (q.n == 0) return hipSuccess;
+  if (q.n > 0x80000000u) return hipErrorInvalidValue;
+  const uint32_t blocks = (q.n + 255u) / 256u;
+  switch (plan.method) {
+    case HRT_QUERY_SCAN:
+      radiance_scan<<<blocks, 256, 0, stream>>>(p0, q);
+      break;
+    case HRT_QUERY_BVH:
+      radiance_bvh<<<blocks, 256, 0, stream>>>(p0, q);
+      break;
+    case HRT_QUERY_PAIRS: {
+      if (plan.lds_bytes == 0 || !q.next) return hipErrorInvalidValue;
+      TraceParams p = p0;
+      p.wq_ncap = plan.wq_ncap;
+      p.wq_tcap = plan.wq_tcap;
+      // (their dynamic-LDS limit: ensure_kernel_attributes)
+      void (*kernel)(TraceParams, RadianceArgs) =
+          p.bvh_node_r ? (q.stats ? radiance_pairs<true, true> : radiance_pairs<true, false>)
+                       : (q.stats ? radiance_pairs<false, true> : radiance_pairs<false, false>);
+      if (hipError_t e = hipMemsetAsync(q.next, 0, sizeof(uint32_t), stream); e != hipSuccess) return e;
+      const uint32_t groups = std::min((q.n + 1023u) / 1024u, std::max(1u, p.num_cus));
+      kernel<<<groups, 1024, plan.lds_bytes, stream>>>(p, q);
       break;
     }
     default:

@@ -372,6 +372,48 @@ class HrtContext:
         out = words if packed else np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
         return (out, st) if with_stats else out
 
+    # ---- radiance queries (hrt_radiance) ----
+
+    @staticmethod
+    def radiance_queries(origins, seeds, centres) -> np.ndarray:
+        """n hrt_radiance_query records (_lib.RADIANCE_QUERY_DTYPE) of origins[n, 3], seeds[n] (uint32) and
+        centres[n, 3]."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+        if len(o) != len(c):
+            raise ValueError("origins and centres differ in length")
+        q = np.zeros(len(o), dtype=_lib.RADIANCE_QUERY_DTYPE)
+        q["origin"], q["centre"] = o, c
+        q["seed"] = np.asarray(seeds, np.uint32)
+        return q
+
+    def radiance_into(self, pc: _lib.PushConstants, queries_ptr: int, n: int, rgba_ptr: int,
+                      method: int = _lib.QUERY_AUTO, with_stats: bool = False):
+        """hrt_radiance on caller memory: n hrt_radiance_query records at queries_ptr -> n x 4 float32 at
+        rgba_ptr (host pointers, or 16-byte aligned pointers into the context's device, e.g. a torch tensor's
+        data_ptr()).  Blocking.  Returns the call's _lib.RadianceStats when with_stats, else None."""
+        st = _lib.RadianceStats()
+        self._check(self.lib.hrt_radiance(self.handle, ctypes.byref(pc), ctypes.c_void_p(queries_ptr), int(n),
+                                          int(method), ctypes.c_void_p(rgba_ptr),
+                                          ctypes.byref(st) if with_stats else None), "hrt_radiance")
+        return st if with_stats else None
+
+    def radiance(self, queries, pc: _lib.PushConstants, method: int = _lib.QUERY_AUTO, with_stats: bool = False):
+        """hrt_radiance: what the path tracer returns for each query -- the reference's main()
+        for a virtual pixel with trace_ray's root ``origin``, RNG state ``seed`` and sample centre ``centre``,
+        under pc's matrix, jitter, sample and bounce counts -- as an (n, 4) float32 array, alpha 1.
+        ``queries``: a _lib.RADIANCE_QUERY_DTYPE array (``radiance_queries``), or a torch tensor of n x 8
+        32-bit words on the host or on the context's device (anything with data_ptr() and shape).
+        with_stats=True returns (rgba, _lib.RadianceStats)."""
+        if hasattr(queries, "data_ptr"):
+            n, q_ptr = int(queries.shape[0]), int(queries.data_ptr())
+        else:
+            queries = np.ascontiguousarray(queries, dtype=_lib.RADIANCE_QUERY_DTYPE)
+            n, q_ptr = len(queries), queries.ctypes.data
+        rgba = np.zeros((n, 4), np.float32)
+        st = self.radiance_into(pc, q_ptr if n else 0, n, rgba.ctypes.data if n else 0, method, with_stats)
+        return (rgba, st) if with_stats else rgba
+
     def check_guards(self):
         """libhip_raytrace_debug.so: (guarded device buffers, buffers whose guard bands were overwritten)."""
         n, bad = ctypes.c_uint32(), ctypes.c_uint32()
@@ -562,6 +604,26 @@ class RayTracePipeline:
         """Whether b[i] is visible from a[i]: nothing of the scene on the open segment between them that the
         reference's world_hit accepts (0.001 < dist < |b - a|).  ~occluded(segment_rays(a, b))."""
         return ~self.ctx.occluded(self.segment_rays(a, b), method)
+
+    def pixel_queries(self, camera: Camera, xs, ys, frame: int) -> np.ndarray:
+        """The radiance queries (_lib.RADIANCE_QUERY_DTYPE) of pixels (xs[i], ys[i]) of the frame that
+        ``compute(camera, frame)`` traces: origin the camera position, seed frame * 719393 + id, centre the
+        ray centre of id = x + y * width."""
+        w, h = self.image_size
+        xs = np.asarray(xs, np.int64).reshape(-1)
+        ys = np.asarray(ys, np.int64).reshape(-1)
+        if len(xs) != len(ys) or (len(xs) and (xs.min() < 0 or xs.max() >= w or ys.min() < 0 or ys.max() >= h)):
+            raise ValueError("pixel coordinates outside the image")
+        ids = xs + ys * w
+        seeds = ((int(frame) & 0xFFFFFFFF) * 719393 + ids) & 0xFFFFFFFF
+        origins = np.broadcast_to(np.asarray(camera.position, np.float32)[:3], (len(ids), 3))
+        return HrtContext.radiance_queries(origins, seeds, self.rays["sample_centre"][ids, :3])
+
+    def radiance_pixels(self, camera: Camera, xs, ys, frame: int, method: int = _lib.QUERY_AUTO) -> np.ndarray:
+        """What ``compute(camera, frame)`` stores at pixels (xs[i], ys[i]) of an RGBA32F trace image, bit for
+        bit, as an (n, 4) float32 array -- without tracing the frame (hrt_radiance on ``pixel_queries``)."""
+        return self.ctx.radiance(self.pixel_queries(camera, xs, ys, frame), self.push_constants(camera, frame, False),
+                                 method)
 
     def init(self) -> None:
         self.ctx.trace(self.push_constants(Camera(), 0, True))

@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): occlusion queries -- hrt_occlusion_stats, hrt_occluded.
+/* 6, additive (no bump: nothing existing changed): radiance queries -- hrt_radiance_query, hrt_radiance_stats,
+ * hrt_radiance.
+ * 6, additive (no bump: nothing existing changed): occlusion queries -- hrt_occlusion_stats, hrt_occluded.
  * 6, additive (no bump: nothing existing changed): HRT_KERNEL_BUNDLE_WQ_L2, HRT_OPT_WQ_LDS_NODES,
  * hrt_debug_bvh_wq_nodes_bfs, hrt_debug_wq_l2_plan.
  * 6, additive (no bump: nothing existing changed): ray queries -- hrt_ray_query, hrt_hit, hrt_query_stats,
@@ -266,6 +268,24 @@ typedef struct hrt_occlusion_stats {
   uint64_t occluded;   /* rays whose bit is 1 */
 } hrt_occlusion_stats;
 
+/* ---- radiance queries (hrt_radiance) ---- */
+typedef struct hrt_radiance_query { /* 32 bytes, two 16-byte loads */
+  float origin[3];   /* trace_ray's root */
+  uint32_t seed;     /* the RNG state main() would start the pixel with */
+  float centre[3];   /* the sample centre get_ray_dir jitters and rotates */
+  uint32_t reserved; /* ignored */
+} hrt_radiance_query;
+
+typedef struct hrt_radiance_stats {
+  uint32_t method_ran;    /* as hrt_query_stats */
+  uint32_t reserved;      /* 0 */
+  uint64_t scan_segments; /* segments answered by the literal scan because they are irregular (S11's rule, per
+                             segment: origin not finite, or direction not finite, or its dot(d, d) zero, denormal
+                             or overflowed) */
+  uint64_t segments;      /* world_hit calls, as hrt_stats.segments counts them */
+  uint64_t tri_tests;     /* as hrt_stats.tri_tests */
+} hrt_radiance_stats;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -311,6 +331,13 @@ HRT_STATIC_ASSERT(sizeof(hrt_occlusion_stats) == 32 && offsetof(hrt_occlusion_st
                       offsetof(hrt_occlusion_stats, scan_rays) == 8 && offsetof(hrt_occlusion_stats, tri_tests) == 16 &&
                       offsetof(hrt_occlusion_stats, occluded) == 24,
                   "hrt_occlusion_stats");
+HRT_STATIC_ASSERT(sizeof(hrt_radiance_query) == 32 && offsetof(hrt_radiance_query, seed) == 12 &&
+                      offsetof(hrt_radiance_query, centre) == 16 && offsetof(hrt_radiance_query, reserved) == 28,
+                  "hrt_radiance_query");
+HRT_STATIC_ASSERT(sizeof(hrt_radiance_stats) == 32 && offsetof(hrt_radiance_stats, reserved) == 4 &&
+                      offsetof(hrt_radiance_stats, scan_segments) == 8 && offsetof(hrt_radiance_stats, segments) == 16 &&
+                      offsetof(hrt_radiance_stats, tri_tests) == 24,
+                  "hrt_radiance_stats");
 
 typedef struct hrt_context hrt_context;
 
@@ -605,6 +632,36 @@ hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_constants* pc,
  * anything is enqueued. */
 hrt_status hrt_occluded(hrt_context* ctx, const hrt_ray_query* rays, uint32_t n, uint32_t method, uint32_t* bits,
                         hrt_occlusion_stats* stats);
+
+/* The path tracer for caller-chosen samples: query i is the reference's main() for a virtual
+ * pixel, and rgba[4 i .. 4 i + 3] is exactly what main() stores into an RGBA32F image:
+ *     state = seed; colour = 0
+ *     for s in 0 .. num_samples - 1:
+ *         dir = get_ray_dir(pc, centre, state)               -- three draws always; pc's matrix and jitter_size
+ *         colour += trace_ray(origin, normalize(dir), state)  -- the second normalize, as main() applies it
+ *     out = (colour / float(num_samples), 1.0)
+ * Of pc the call uses cam_alignment_mat, jitter_size, num_samples, max_bounces, use_environment_light, and
+ * num_spheres / num_meshes (validated against the uploaded counts as hrt_trace validates them); it ignores
+ * cam_pos, rng_offset, num_rays, width and height; pc->init must be 0.  Consequences:
+ *   - the query (cam_pos, rng_offset * 719393 + id, ray centre id) under a frame's own push block is that
+ *     frame's pixel id, bit for bit (the seed map is a bijection on uint32: 719393 is odd);
+ *   - a fixed direction d is an identity matrix with jitter 0 and centre = d; it still burns the three draws
+ *     and is normalised twice;
+ *   - num_samples <= 0 gives colour / float(num_samples) of a zero colour as the frame kernels store it: 0/0 =
+ *     NaN in rgb at 0 (-0 below it);
+ *   - max_bounces < 0 gives 0.
+ * Every segment takes S11's regularity test (hrt_radiance_stats.scan_segments); an irregular one is answered
+ * by the literal scan whatever the method.  Methods and fallbacks as hrt_intersect, and every method gives the
+ * same bytes and the same three counts; HRT_QUERY_AUTO here is PAIRS when it fits, else BVH, else SCAN --
+ * unlike hrt_intersect's, on purpose: every segment after a query's first is a bounce ray.
+ * BLOCKING; ordered on the context's stream after the work issued so far; touches no trace lane, image,
+ * hrt_stats, counter, fold record or ticket; works on any context (a row-tile part too) and is no collective.
+ * queries, rgba: host memory (staged in chunks of 65,536) or memory of the context's device (then 16-byte
+ * aligned).  stats may be NULL.  n == 0: OK, nothing written.  HRT_ERR_INVALID_ARGUMENT (unknown method,
+ * pc->init, counts beyond the scene, NULL queries / rgba with n > 0, a misaligned device pointer) and
+ * HRT_ERR_NO_SCENE are decided before anything is enqueued. */
+hrt_status hrt_radiance(hrt_context* ctx, const hrt_push_constants* pc, const hrt_radiance_query* queries, uint32_t n,
+                        uint32_t method, float* rgba /* n x 4 */, hrt_radiance_stats* stats);
 
 /* The records of the newest min(cap, available) folds (HRT_OPT_FOLD_RECORDS = 1), oldest first; the ring
  * keeps the last HRT_FOLD_RECORD_RING.  Folds deferred combines and synchronizes the context, as

@@ -339,13 +339,15 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
                                     tris.data(), (uint32_t)ntri, meshes.data()),
           "hrt_host_transform_meshes");
     ray_count_ = n_rays;
+    rays.resize(n_rays);
+    rays_ = std::move(rays);  // (the centres radiance_pixels builds its queries from)
     sphere_count_ = (int32_t)settings.sphere_data.size();
     mesh_count_ = (int32_t)settings.mesh_data.size();
     num_samples_ = settings.num_samples > 1 ? (int32_t)settings.num_samples : 1;  // :88
     max_bounces_ = (int32_t)settings.max_bounces;                                // :89
     use_env_ = settings.use_environment_lighting;
     jitter_ = settings.sample_jitter ? *settings.sample_jitter : jitter;
-    check(hrt_set_scene(ctx.get(), rays.data(), n_rays, spheres.data(), (uint32_t)spheres.size(), tris.data(),
+    check(hrt_set_scene(ctx.get(), rays_.data(), n_rays, spheres.data(), (uint32_t)spheres.size(), tris.data(),
                         (uint32_t)ntri, meshes.data(), (uint32_t)mesh_count_),
           "hrt_set_scene", ctx.get());
   }
@@ -429,12 +431,49 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
     out.flip();
     return out;
   }
+  // Radiance queries (hrt_radiance; not a reference feature).  radiance(queries, camera)[i]: what the path
+  // tracer returns for query i -- the reference's main() for a virtual pixel whose trace_ray root is origin,
+  // whose RNG state starts at seed and whose sample centre is centre -- under the push block of `camera` (its
+  // matrix; the pipeline's jitter, sample and bounce counts), as main() stores it: (r, g, b, 1).
+  std::vector<std::array<float, 4>> radiance(const std::vector<hrt_radiance_query>& queries, const Camera& camera,
+                                             uint32_t method = HRT_QUERY_AUTO) const {
+    const hrt_push_constants pc = push_constants(camera, 0u, false);
+    std::vector<std::array<float, 4>> out(queries.size());
+    check(hrt_radiance(ctx_->get(), &pc, queries.data(), (uint32_t)queries.size(), method,
+                       out.empty() ? nullptr : out[0].data(), nullptr),
+          "hrt_radiance", ctx_->get());
+    return out;
+  }
+  // The query of pixel (x, y) of the frame compute(camera, frame) traces: origin the camera position, seed
+  // frame * 719393 + id, centre the ray centre of id = x + y * width.
+  hrt_radiance_query pixel_query(const Camera& camera, uint32_t x, uint32_t y, uint32_t frame) const {
+    if (x >= size_[0] || y >= size_[1]) throw std::invalid_argument("pixel_query: pixel outside the image");
+    const uint32_t id = x + y * size_[0];
+    hrt_radiance_query q{};
+    for (int k = 0; k < 3; ++k) {
+      q.origin[k] = camera.position[k];
+      q.centre[k] = rays_[id].sample_centre[k];
+    }
+    q.seed = frame * 719393u + id;
+    return q;
+  }
+  // What compute(camera, frame) stores at pixels (xs[i], ys[i]) of an RGBA32F trace image, bit for bit, without
+  // tracing the frame.
+  std::vector<std::array<float, 4>> radiance_pixels(const Camera& camera, const std::vector<uint32_t>& xs,
+                                                    const std::vector<uint32_t>& ys, uint32_t frame,
+                                                    uint32_t method = HRT_QUERY_AUTO) const {
+    if (xs.size() != ys.size()) throw std::invalid_argument("radiance_pixels: xs and ys differ in length");
+    std::vector<hrt_radiance_query> queries(xs.size());
+    for (size_t i = 0; i < xs.size(); ++i) queries[i] = pixel_query(camera, xs[i], ys[i], frame);
+    return radiance(queries, camera, method);
+  }
   Context& context() const { return *ctx_; }
   std::array<uint32_t, 2> image_size() const { return size_; }
 
  private:
   Context* ctx_;
   std::array<uint32_t, 2> size_;
+  std::vector<hrt_ray> rays_;
   uint32_t ray_count_ = 0;
   int32_t sphere_count_ = 0, mesh_count_ = 0, num_samples_ = 1, max_bounces_ = 0;
   bool use_env_ = true;
