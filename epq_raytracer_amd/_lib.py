@@ -149,6 +149,21 @@ QUERY_NAMES = {0: "auto", 1: "scan", 2: "bvh", 3: "pairs"}
 HIT_MISS, HIT_SPHERE, HIT_TRIANGLE = 0, 1, 2  # hrt_hit.kind
 HIT_NONE = 0xFFFFFFFF  # hrt_hit.index / mesh of a miss
 
+
+class DenoiseInfo(ctypes.Structure):
+    """hrt_denoise_info: one denoise pass (32 bytes)."""
+
+    _fields_ = [("image_id", c_uint32), ("iterations", c_uint32), ("method", c_uint32), ("flags", c_uint32),
+                ("sigma_colour", c_float), ("sigma_normal", c_float), ("sigma_depth", c_float), ("reserved", c_uint32)]
+
+
+assert ctypes.sizeof(DenoiseInfo) == 32
+DENOISE_AUTO, DENOISE_DIRECT, DENOISE_TILED = 0, 1, 2  # hrt_denoise_method
+DENOISE_NAMES = {0: "auto", 1: "direct", 2: "tiled"}
+DEBUG_DENOISE_DENSE, DEBUG_DENOISE_LATTICE = 3, 4  # libhip_raytrace_debug.so only
+DENOISE_MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16
+DENOISE_SIGMAS = (8.0, 0.25, 0.5)  # HRT_DENOISE_SIGMA_COLOUR / _NORMAL / _DEPTH (hrt_denoise_defaults)
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -220,6 +235,7 @@ EXPORTED_SYMBOLS = (
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
+    "hrt_denoise_defaults", "hrt_denoise", "hrt_denoise_present",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -296,6 +312,10 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_release_external_memory": (c_int32, [P, P]),
         "hrt_present": (c_int32, [P, POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
         "hrt_accumulate_present": (c_int32, [P, c_uint32, POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
+        "hrt_denoise_defaults": (None, [POINTER(DenoiseInfo)]),
+        "hrt_denoise": (c_int32, [P, POINTER(DenoiseInfo), P, c_uint32, P, c_size_t]),
+        "hrt_denoise_present": (c_int32, [P, POINTER(DenoiseInfo), P, POINTER(PresentInfo), P, c_uint64,
+                                          POINTER(c_uint64)]),
         "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
         "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),

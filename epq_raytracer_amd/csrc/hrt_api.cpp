@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -22,6 +23,7 @@
 #include "hip_raytrace.h"
 #include "hrt_bvh.h"
 #include "hrt_context.h"
+#include "hrt_denoise.h"
 #include "hrt_host.h"
 #include "hrt_image.h"
 #include "hrt_kernels.h"
@@ -486,6 +488,10 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->occl_stats);
   free_dev(ctx, ctx->rad_out);
   free_dev(ctx, ctx->rad_words);
+  free_dev(ctx, ctx->dn_img[0]);
+  free_dev(ctx, ctx->dn_img[1]);
+  free_dev(ctx, ctx->dn_guide);
+  free_dev(ctx, ctx->dn_keys);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -1771,6 +1777,123 @@ extern "C" hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, c
                                               frame, present_target(info, dst), ctx->stream));
   ctx->accumulates++;
   if ((st = hrt::release_lane(ctx, l)) != HRT_OK) return st;
+  return ticket_end(ctx, ev, ticket);
+}
+
+// ---- the denoise pass (kernels in hrt_denoise.hip) ---------------------------
+namespace {
+
+// Every check of hrt_denoise / hrt_denoise_present that concerns the filter itself, on the host.
+hrt_status check_denoise(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!info) return bad("null info");
+  if (ctx->comm || ctx->part_count > 1)
+    return bad("a context of a row-tile partition or joined to a communicator cannot denoise (a tap's neighbour rows "
+               "live on another part; the gathered form is out of scope)");
+  if (info->image_id != HRT_IMG_ACCUM && info->image_id != HRT_IMG_TRACE) return bad("unknown image id");
+  if (info->iterations == 0 || info->iterations > hrt::kDenoiseMaxIterations) return bad("iterations must be 1..5");
+#ifdef HRT_DEBUG_OPTIONS
+  if (info->method > HRT_DEBUG_DENOISE_LATTICE) return bad("unknown method");
+#else
+  if (info->method > HRT_DENOISE_TILED) return bad("unknown method");
+#endif
+  if (info->flags != 0) return bad("flags must be 0");
+  for (const float s : {info->sigma_colour, info->sigma_normal, info->sigma_depth})
+    if (!(std::isfinite(s) && s > 0.0f)) return bad("every sigma must be finite and greater than 0");
+  if (guide) {
+    hrt_status st = bind(ctx);
+    if (st != HRT_OK) return st;
+    if ((uintptr_t)guide % 16 != 0) return bad("the guide must be 16-byte aligned");
+    if (!query_direct(ctx, guide) || !query_direct(ctx, guide + (ctx->npix() - 1)))
+      return bad("the guide must be width x height records in memory of the context's device");
+  }
+  return HRT_OK;
+}
+
+// The filter on ctx->stream, after everything that wrote the source image (arguments already checked): prep,
+// then one pass per iteration between the two scratch images.  The last pass writes out (float4 texels, or
+// RGBA8 words when out_rgba8) when out is not null, else the scratch image the pass before it did not write;
+// *result = where the result is.
+hrt_status enqueue_denoise(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide, void* out, bool out_rgba8,
+                           void** result, const char* who) {
+  const size_t np = ctx->npix();
+  hrt_status st;
+  for (void*& img : ctx->dn_img)
+    if ((st = ensure_staging(ctx, &img, np * 16, who)) != HRT_OK) return st;
+  if (guide) {
+    if ((st = ensure_staging(ctx, &ctx->dn_guide, np * 16, who)) != HRT_OK) return st;
+    if ((st = ensure_staging(ctx, &ctx->dn_keys, np * 4, who)) != HRT_OK) return st;
+  }
+  void* gd = guide ? ctx->dn_guide : nullptr;
+  void* keys = guide ? ctx->dn_keys : nullptr;
+  const void* src = hrt::local_image(ctx, info->image_id);
+  if (!src) return fail(ctx, HRT_ERR_HIP, std::string(who) + ": lane wait failed");
+  HRT_HIP(ctx, hrt::launch_denoise_prep(src, ctx->f32(), guide, ctx->dn_img[0], gd, keys, np, ctx->stream));
+  if (info->image_id == HRT_IMG_TRACE) {
+    // prep was the source's only reader: the trace image's next writer follows it (enqueue_present's rule)
+    if (ctx->cur_slot >= 0) {
+      HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+      ctx->fold_set = true;
+    }
+    if ((st = hrt::release_lane(ctx, ctx->cur_lane)) != HRT_OK) return st;
+  }
+  // S14's host constants, each one rounded float operation
+  const float kc0 = 1.0f / (info->sigma_colour * info->sigma_colour), kn = 1.0f / info->sigma_normal;
+  for (uint32_t i = 0; i < info->iterations; ++i) {
+    const bool last = i + 1 == info->iterations;
+    void* to = last && out ? out : ctx->dn_img[(i + 1) & 1];
+    const hrt::AtrousPass p{ctx->dn_img[i & 1], gd, keys, to, last && out_rgba8, ctx->width, ctx->local_rows, 1u << i,
+                            ldexpf(kc0, 2 * (int)i), kn, info->sigma_depth};
+    HRT_HIP(ctx, hrt::launch_atrous(p, hrt::atrous_form(info->method, i), ctx->stream));
+    *result = to;
+  }
+  return HRT_OK;
+}
+
+}  // namespace
+
+extern "C" void hrt_denoise_defaults(hrt_denoise_info* info) {
+  if (!info) return;
+  *info = hrt_denoise_info{HRT_IMG_ACCUM, hrt::kDenoiseMaxIterations, HRT_DENOISE_AUTO, 0u,
+                           HRT_DENOISE_SIGMA_COLOUR, HRT_DENOISE_SIGMA_NORMAL, HRT_DENOISE_SIGMA_DEPTH, 0u};
+}
+
+extern "C" hrt_status hrt_denoise(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide, uint32_t fmt,
+                                  void* dst, size_t bytes) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = check_denoise(ctx, info, guide, "hrt_denoise");
+  if (st != HRT_OK) return st;
+  if (fmt != HRT_FMT_RGBA8 && fmt != HRT_FMT_RGBA32F) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_denoise: unknown format");
+  if (!dst) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_denoise: null destination");
+  const bool rgba8 = fmt == HRT_FMT_RGBA8;
+  const size_t need = ctx->npix() * (rgba8 ? 4 : 16);
+  if (bytes < need) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_denoise: destination too small");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  // device memory a texel store may address: the last pass writes it; anything else is copied from the scratch
+  const bool direct = (uintptr_t)dst % (rgba8 ? 4 : 16) == 0 && query_direct(ctx, dst) &&
+                      query_direct(ctx, static_cast<const char*>(dst) + (need - 1));
+  void* res = nullptr;
+  if ((st = enqueue_denoise(ctx, info, guide, direct ? dst : nullptr, rgba8, &res, "hrt_denoise")) != HRT_OK) return st;
+  if (!direct) HRT_HIP(ctx, hipMemcpyAsync(dst, res, need, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_denoise_present(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide,
+                                          const hrt_present_info* target, void* dst, uint64_t dst_bytes,
+                                          uint64_t* ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = check_denoise(ctx, info, guide, "hrt_denoise_present");
+  if (st != HRT_OK) return st;
+  if ((st = check_present(ctx, target, dst, dst_bytes, ticket, false, "hrt_denoise_present")) != HRT_OK) return st;
+  if (target->image_id != info->image_id)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_denoise_present: the target's image_id differs from the filter's");
+  hipEvent_t ev = nullptr;
+  if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  void* res = nullptr;
+  if ((st = enqueue_denoise(ctx, info, guide, nullptr, false, &res, "hrt_denoise_present")) != HRT_OK) return st;
+  // the filtered float image through the present pass unchanged
+  HRT_HIP(ctx, hrt::launch_present(res, true, ctx->width, ctx->local_rows, present_target(target, dst), ctx->stream));
   return ticket_end(ctx, ev, ticket);
 }
 

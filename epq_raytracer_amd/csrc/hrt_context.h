@@ -225,6 +225,12 @@ struct hrt_context {
   // are host memory, and four words: the three statistics counts, then the PAIRS kernel's query counter
   void* rad_out = nullptr;
   unsigned long long* rad_words = nullptr;
+  // The denoise pass (hrt_denoise, hrt_denoise_present): the two float4 images its passes ping-pong between,
+  // allocated by the first call, and the compact guide ({n, t} and the surface key per pixel), by the first
+  // guided one
+  void* dn_img[2] = {};
+  void* dn_guide = nullptr;
+  void* dn_keys = nullptr;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

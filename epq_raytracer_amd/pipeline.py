@@ -287,6 +287,51 @@ class HrtContext:
         """Block until the present pass of `ticket` has finished."""
         self._check(self.lib.hrt_present_wait(self.handle, int(ticket)), "hrt_present_wait")
 
+    # ---- the denoise pass (hrt_denoise, hrt_denoise_present) ----
+
+    def denoise_info(self, image_id: int = _lib.IMG_ACCUM, iterations: Optional[int] = None,
+                     method: int = _lib.DENOISE_AUTO, sigma_colour: Optional[float] = None,
+                     sigma_normal: Optional[float] = None, sigma_depth: Optional[float] = None) -> _lib.DenoiseInfo:
+        """hrt_denoise_defaults with the given fields replaced (None: the default)."""
+        info = _lib.DenoiseInfo()
+        self.lib.hrt_denoise_defaults(ctypes.byref(info))
+        info.image_id, info.method = int(image_id), int(method)
+        if iterations is not None:
+            info.iterations = int(iterations)
+        for name, v in (("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+            if v is not None:
+                setattr(info, name, float(v))
+        return info
+
+    def denoise_into(self, dst_ptr: int, nbytes: int, fmt: int = _lib.FMT_RGBA8, guide_ptr: Optional[int] = None,
+                     info: Optional[_lib.DenoiseInfo] = None, **fields):
+        """hrt_denoise into caller memory (host or device pointer): the guided a-trous filter
+        of image ``image_id`` as local_rows x W texels of fmt.  guide_ptr: None for the colour-only filter, else
+        a 16-byte aligned device pointer to W x H hrt_hit records (``intersect_primary_into`` of the whole
+        image).  ``info`` or the fields of ``denoise_info``.  Blocking."""
+        info = info if info is not None else self.denoise_info(**fields)
+        self._check(self.lib.hrt_denoise(self.handle, ctypes.byref(info), ctypes.c_void_p(guide_ptr or 0), int(fmt),
+                                         ctypes.c_void_p(dst_ptr), int(nbytes)), "hrt_denoise")
+
+    def denoise(self, fmt: int = _lib.FMT_RGBA8, guide_ptr: Optional[int] = None,
+                info: Optional[_lib.DenoiseInfo] = None, **fields) -> np.ndarray:
+        """hrt_denoise: the filtered image as uint8 or float32 (local_rows, W, 4)."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.uint8 if fmt == _lib.FMT_RGBA8 else np.float32)
+        self.denoise_into(out.ctypes.data, out.nbytes, fmt, guide_ptr, info, **fields)
+        return out
+
+    def denoise_present(self, dst_ptr: int, nbytes: int, width: int, height: int, pitch: Optional[int] = None,
+                        fmt: int = _lib.PRESENT_B8G8R8A8, guide_ptr: Optional[int] = None,
+                        info: Optional[_lib.DenoiseInfo] = None, **fields) -> int:
+        """hrt_denoise_present: the filter, then ``present`` of the filtered image (same target rules, same
+        ticket sequence); returns the ticket without waiting."""
+        info = info if info is not None else self.denoise_info(**fields)
+        target, t = self._present_info(info.image_id, width, height, pitch, fmt), ctypes.c_uint64()
+        self._check(self.lib.hrt_denoise_present(self.handle, ctypes.byref(info), ctypes.c_void_p(guide_ptr or 0),
+                                                 ctypes.byref(target), ctypes.c_void_p(dst_ptr), int(nbytes),
+                                                 ctypes.byref(t)), "hrt_denoise_present")
+        return t.value
+
     # ---- ray queries (hrt_intersect, hrt_intersect_primary) ----
 
     @staticmethod
@@ -340,6 +385,19 @@ class HrtContext:
                     "hrt_intersect_primary")
         hits = hits.reshape(h, w)
         return (hits, st) if with_stats else hits
+
+    def intersect_primary_into(self, pc: _lib.PushConstants, hits_ptr: int, rect=None, method: int = _lib.QUERY_AUTO,
+                               with_stats: bool = False):
+        """hrt_intersect_primary into caller memory: w x h hrt_hit records, row-major, at hits_ptr (a host
+        pointer, or a 16-byte aligned pointer into the context's device -- the guide of ``denoise`` when rect
+        is None, without a round trip through the host).  Blocking.  Returns the call's _lib.QueryStats when
+        with_stats, else None."""
+        x0, y0, w, h = (0, 0, self.width, self.height) if rect is None else (int(v) for v in rect)
+        st = _lib.QueryStats()
+        self._check(self.lib.hrt_intersect_primary(self.handle, ctypes.byref(pc), x0, y0, w, h, int(method),
+                                                   ctypes.c_void_p(hits_ptr), ctypes.byref(st) if with_stats else None),
+                    "hrt_intersect_primary")
+        return st if with_stats else None
 
     # ---- occlusion queries (hrt_occluded) ----
 
@@ -529,6 +587,17 @@ class RenderPassOverFrame:
         return self.ctx.present(view.image_id, target.ptr, target.nbytes, target.width, target.height, target.pitch,
                                 target.format)
 
+    def render_denoised(self, view: Image, target: PresentTarget, guide_ptr: Optional[int] = None, **fields) -> int:
+        """``render`` with the denoise pass between the image and the quad (hrt_denoise_present): guide_ptr as
+        ``HrtContext.denoise_into`` takes it (``RayTracePipeline.first_hits_into``), ``fields`` those of
+        ``HrtContext.denoise_info`` (iterations, method, sigmas).  Returns the ticket."""
+        if view.ctx is not self.ctx:
+            raise ValueError("view must be an image of the render pass's context")
+        if target.format != self.output_format:
+            raise ValueError("the target's format differs from the render pass's output format")
+        return self.ctx.denoise_present(target.ptr, target.nbytes, target.width, target.height, target.pitch,
+                                        target.format, guide_ptr, image_id=view.image_id, **fields)
+
 
 # ---- pipelines ---------------------------------------------------------------------------------
 
@@ -582,6 +651,12 @@ class RayTracePipeline:
         the un-jittered primary ray of every pixel of rect = (x0, y0, w, h) (None: the whole image), as an
         (h, w) array in trace-image rows (hrt_intersect_primary)."""
         return self.ctx.intersect_primary(self.push_constants(camera, 0, False), rect)
+
+    def first_hits_into(self, camera: Camera, ptr: int) -> None:
+        """``first_hits`` of the whole image written to W x H hrt_hit records at ptr (host, or 16-byte aligned
+        device memory of the context): the guide of ``DiffusePipeline.denoised`` /
+        ``RenderPassOverFrame.render_denoised``, kept on the device."""
+        self.ctx.intersect_primary_into(self.push_constants(camera, 0, False), ptr)
 
     def pick(self, camera: Camera, x: int, y: int):
         """What lies under pixel (x, y) of the view: one hit record (numpy.void of _lib.HIT_DTYPE).  x, y are
@@ -643,3 +718,9 @@ class DiffusePipeline:
         if next_image.ctx is not self.ctx or next_image.image_id != _lib.IMG_TRACE:
             raise ValueError("next_image must be the trace image of the same context")
         self.ctx.accumulate(frame_num)
+
+    def denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **sigmas) -> np.ndarray:
+        """The accumulated image through the denoise pass (hrt_denoise), as uint8 or float32 (H, W, 4):
+        guide_ptr = the view's first hits on the device (``RayTracePipeline.first_hits_into``) or None for the
+        colour-only filter; ``sigmas`` (and iterations / method) as ``HrtContext.denoise_info`` takes them."""
+        return self.ctx.denoise(fmt, guide_ptr, image_id=_lib.IMG_ACCUM, **sigmas)

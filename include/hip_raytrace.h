@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): radiance queries -- hrt_radiance_query, hrt_radiance_stats,
+/* 6, additive (no bump: nothing existing changed): the denoise pass -- hrt_denoise_method, hrt_denoise_info,
+ * hrt_denoise_defaults, hrt_denoise, hrt_denoise_present.
+ * 6, additive (no bump: nothing existing changed): radiance queries -- hrt_radiance_query, hrt_radiance_stats,
  * hrt_radiance.
  * 6, additive (no bump: nothing existing changed): occlusion queries -- hrt_occlusion_stats, hrt_occluded.
  * 6, additive (no bump: nothing existing changed): HRT_KERNEL_BUNDLE_WQ_L2, HRT_OPT_WQ_LDS_NODES,
@@ -286,6 +288,32 @@ typedef struct hrt_radiance_stats {
   uint64_t tri_tests;     /* as hrt_stats.tri_tests */
 } hrt_radiance_stats;
 
+/* ---- the denoise pass (hrt_denoise, hrt_denoise_present) ---- */
+typedef enum hrt_denoise_method {
+  HRT_DENOISE_AUTO = 0,   /* per step, the kernel that measured faster */
+  HRT_DENOISE_DIRECT = 1, /* atrous_direct: every tap a global load */
+  HRT_DENOISE_TILED = 2   /* atrous_tiled: taps from a tile staged in LDS */
+} hrt_denoise_method;
+/* libhip_raytrace_debug.so only (measurements of the tiled kernel's two forms): the dense tile
+ * at every step whose halo fits (1, 2, 4; the sub-lattice above), and the sub-lattice at every step */
+#define HRT_DEBUG_DENOISE_DENSE 3u
+#define HRT_DEBUG_DENOISE_LATTICE 4u
+/* hrt_denoise_defaults' sigmas: design parameters chosen on the CPU oracle's frames */
+#define HRT_DENOISE_SIGMA_COLOUR 8.0f
+#define HRT_DENOISE_SIGMA_NORMAL 0.25f
+#define HRT_DENOISE_SIGMA_DEPTH 0.5f
+
+typedef struct hrt_denoise_info { /* 32 bytes */
+  uint32_t image_id;   /* HRT_IMG_ACCUM or HRT_IMG_TRACE */
+  uint32_t iterations; /* 1..5: passes with steps 1, 2, 4, 8, 16 */
+  uint32_t method;     /* hrt_denoise_method; every method gives the same bytes */
+  uint32_t flags;      /* must be 0 */
+  float sigma_colour;  /* each sigma finite and > 0 */
+  float sigma_normal;
+  float sigma_depth;
+  uint32_t reserved;   /* ignored */
+} hrt_denoise_info;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -338,6 +366,11 @@ HRT_STATIC_ASSERT(sizeof(hrt_radiance_stats) == 32 && offsetof(hrt_radiance_stat
                       offsetof(hrt_radiance_stats, scan_segments) == 8 && offsetof(hrt_radiance_stats, segments) == 16 &&
                       offsetof(hrt_radiance_stats, tri_tests) == 24,
                   "hrt_radiance_stats");
+
+HRT_STATIC_ASSERT(sizeof(hrt_denoise_info) == 32 && offsetof(hrt_denoise_info, method) == 8 &&
+                      offsetof(hrt_denoise_info, sigma_colour) == 16 && offsetof(hrt_denoise_info, sigma_depth) == 24 &&
+                      offsetof(hrt_denoise_info, reserved) == 28,
+                  "hrt_denoise_info");
 
 typedef struct hrt_context hrt_context;
 
@@ -818,6 +851,43 @@ hrt_status hrt_accumulate_present(hrt_context* ctx, uint32_t frame, const hrt_pr
 hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done);
 /* Blocks until the pass of `ticket` has finished. */
 hrt_status hrt_present_wait(hrt_context* ctx, uint64_t ticket);
+/* ---- the denoise pass (DESIGN.md §2 S14 pins the arithmetic, §27 the kernels) ----------------------------
+ * An edge-avoiding a-trous filter between an image of the context and its consumer: info->iterations passes
+ * of a 5 x 5 B3-spline window with taps 1, 2, 4, 8, 16 pixels apart, each tap weighted by its colour
+ * distance (sigma_colour) and, with a guide, by the angle between the normals (sigma_normal) and the depth
+ * difference relative to the centre's depth (sigma_depth); taps on another surface than the centre's are
+ * skipped.  Every byte of the result is defined by S14: the three methods, both libraries and the numpy
+ * restatement in tests/denoise_ref.py agree bit for bit.  The data stays float between the passes in either
+ * context mode; the source image is never written.
+ *
+ * guide: NULL (the colour-only filter), or width x height hrt_hit records in memory of the context's device,
+ * 16-byte aligned, row-major in trace-image row order -- what hrt_intersect_primary writes for the whole
+ * image (x0 = y0 = 0, w = width, h = height) into device memory.
+ *
+ * Both calls are ordered on the context's stream after the work issued so far (deferred combines are folded
+ * first; HRT_IMG_TRACE joins and releases the current trace lane like hrt_read_image) and touch no trace
+ * lane's image, hrt_stats, counter or fold record.  Their scratch images (two float4 images and the compact
+ * guide, 52 bytes per pixel in all) are allocated by the first call and freed by hrt_destroy.
+ *
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued (the message names the reason): a NULL
+ * info; iterations 0 or above 5; a sigma that is not finite or not > 0; flags != 0; an unknown method, image
+ * id or fmt; a guide that is not memory of the context's device or not 16-byte aligned; a NULL or too small
+ * dst; and a context of a row-tile partition (part_count > 1) or one joined to any communicator: a tap's
+ * neighbour rows live on another part, and the gathered form of the filter is deliberately out of scope. */
+
+/* ACCUM, 5 iterations, AUTO and the default sigmas (DESIGN.md §27 has the grid they were chosen from). */
+void hrt_denoise_defaults(hrt_denoise_info* info);
+/* BLOCKING, like hrt_read_image: height x width texels of the filtered image in fmt (hrt_format; RGBA8 is S7's
+ * store of each channel with alpha 255, RGBA32F has alpha 1.0f) to host or device memory at dst
+ * (bytes >= height * width * 4 or 16). */
+hrt_status hrt_denoise(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide, uint32_t fmt, void* dst,
+                       size_t bytes);
+/* NON-blocking: the filter, then hrt_present's pass over the filtered float image -- target, dst, dst_bytes and
+ * ticket exactly as hrt_present takes them (flip, nearest sampling, byte order, the writable-memory rule, the
+ * ticket sequence and its cap of 8 in flight; hrt_present_done, hrt_present_wait and hrt_synchronize apply).
+ * target->image_id must equal info->image_id. */
+hrt_status hrt_denoise_present(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide,
+                               const hrt_present_info* target, void* dst, uint64_t dst_bytes, uint64_t* ticket);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

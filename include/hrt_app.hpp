@@ -234,6 +234,27 @@ class Context {
     check(hrt_accumulate_present(get(), frame, &info, dst, dst_bytes, &ticket), "hrt_accumulate_present", get());
     return ticket;
   }
+  // the denoise pass (hrt_denoise; not a reference feature): the guided a-trous filter of image info.image_id as
+  // local_rows x width texels of fmt.  guide: null, or width x height hrt_hit records in memory of the context's
+  // device, 16-byte aligned (RayTracePipeline::first_hits_into).  Blocking.
+  static hrt_denoise_info denoise_defaults(hrt_image_id image = HRT_IMG_ACCUM) {
+    hrt_denoise_info info;
+    hrt_denoise_defaults(&info);
+    info.image_id = (uint32_t)image;
+    return info;
+  }
+  std::vector<uint8_t> denoise(const hrt_denoise_info& info, const hrt_hit* guide, hrt_format fmt) {
+    std::vector<uint8_t> out((size_t)layout_.local_rows * layout_.width * (fmt == HRT_FMT_RGBA8 ? 4 : 16));
+    check(hrt_denoise(get(), &info, guide, fmt, out.data(), out.size()), "hrt_denoise", get());
+    return out;
+  }
+  // ... and straight into the present pass (hrt_denoise_present): enqueued, not waited for; returns the ticket
+  uint64_t denoise_present(const hrt_denoise_info& info, const hrt_hit* guide, const hrt_present_info& target, void* dst,
+                           uint64_t dst_bytes) {
+    uint64_t ticket = 0;
+    check(hrt_denoise_present(get(), &info, guide, &target, dst, dst_bytes, &ticket), "hrt_denoise_present", get());
+    return ticket;
+  }
   bool present_done(uint64_t ticket) const {
     uint32_t done = 0;
     check(hrt_present_done(get(), ticket, &done), "hrt_present_done", get());
@@ -298,6 +319,19 @@ class RenderPassOverFrame {
     const hrt_present_info info{(uint32_t)view.id, (uint32_t)target.format, target.width, target.height,
                                 target.pitch ? target.pitch : target.width * 4u, 0u};
     return ctx_->present(info, target.ptr, target.nbytes);
+  }
+  // render() with the denoise pass between the image and the quad (hrt_denoise_present): guide as
+  // Context::denoise takes it; info null: hrt_denoise_defaults (its image_id is set to the view's either way).
+  uint64_t render_denoised(const Image& view, const PresentTarget& target, const hrt_hit* guide = nullptr,
+                           const hrt_denoise_info* info = nullptr) {
+    if (view.ctx != ctx_) throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: view must be an image of the pass's context");
+    if (target.format != format_)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: the target's format differs from the pass's output format");
+    hrt_denoise_info dn = info ? *info : Context::denoise_defaults();
+    dn.image_id = (uint32_t)view.id;
+    const hrt_present_info pi{(uint32_t)view.id, (uint32_t)target.format, target.width, target.height,
+                              target.pitch ? target.pitch : target.width * 4u, 0u};
+    return ctx_->denoise_present(dn, guide, pi, target.ptr, target.nbytes);
   }
 
  private:
@@ -393,6 +427,13 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
     return hits;
   }
   std::vector<hrt_hit> first_hits(const Camera& camera) const { return first_hits(camera, 0, 0, size_[0], size_[1]); }
+  // ... of the whole image into caller memory: width x height records at hits (host, or 16-byte aligned memory of
+  // the context's device -- the guide of DiffusePipeline::denoised / RenderPassOverFrame::render_denoised)
+  void first_hits_into(const Camera& camera, hrt_hit* hits, uint32_t method = HRT_QUERY_AUTO) const {
+    const hrt_push_constants pc = push_constants(camera, 0u, false);
+    check(hrt_intersect_primary(ctx_->get(), &pc, 0, 0, size_[0], size_[1], method, hits, nullptr), "hrt_intersect_primary",
+          ctx_->get());
+  }
   // What lies under pixel (x, y) of the view (trace-image coordinates: row height - 1 - y of a presented target).
   hrt_hit pick(const Camera& camera, uint32_t x, uint32_t y) const { return first_hits(camera, x, y, 1, 1)[0]; }
   // Occlusion queries (hrt_occluded; not a reference feature).  occluded(rays)[i]: something of the scene lies
@@ -489,6 +530,15 @@ class DiffusePipeline {  // src/diffuse.rs:22-136 (image_combiner.glsl)
     if (next_image.ctx != ctx_ || next_image.id != HRT_IMG_TRACE)
       throw HrtError(HRT_ERR_INVALID_ARGUMENT, "next_frame: next_image must be the trace image of the same context");
     check(hrt_accumulate(ctx_->get(), frame_num), "hrt_accumulate", ctx_->get());
+  }
+  // The accumulated image through the denoise pass (hrt_denoise; not a reference feature): guide = the view's
+  // first hits on the device (RayTracePipeline::first_hits_into) or null for the colour-only filter; info null:
+  // hrt_denoise_defaults.
+  std::vector<uint8_t> denoised(const hrt_hit* guide = nullptr, hrt_format fmt = HRT_FMT_RGBA8,
+                                const hrt_denoise_info* info = nullptr) {
+    hrt_denoise_info dn = info ? *info : Context::denoise_defaults();
+    dn.image_id = HRT_IMG_ACCUM;
+    return ctx_->denoise(dn, guide, fmt);
   }
 
  private:

@@ -1,0 +1,14 @@
+# denoise_demo: the denoise pass through the C++ host mirror (include/hrt_app.hpp) against the in-tree
+# libhip_raytrace.so; built by __graft_entry__.build() so that the GPU box runs the same binary
+# (tests/test_gpu_denoise.py).  Its guide and target are device buffers: it links the HIP runtime for
+# hipMalloc / hipMemcpy / hipFree.  Run from this directory: make -f denoise_demo.mk [clean]
+ROOT := $(abspath ../..)
+LIB := $(ROOT)/epq_raytracer_amd/lib
+ROCM ?= /opt/rocm
+CXX ?= g++
+denoise_demo: denoise_demo.cpp $(ROOT)/include/hrt_app.hpp $(ROOT)/include/hip_raytrace.h $(ROOT)/include/hrt_host.h $(LIB)/libhip_raytrace.so
+	$(CXX) -O2 -std=c++17 -Wall -Wextra -I$(ROOT)/include $< -o $@ -L$(LIB) -lhip_raytrace -L$(ROCM)/lib -lamdhip64 \
+		-Wl,-rpath,'$$ORIGIN/../../epq_raytracer_amd/lib' -Wl,-rpath,$(ROCM)/lib
+clean:
+	rm -f denoise_demo
+.PHONY: clean

@@ -16,6 +16,10 @@ not scaling).  Every frame traces and accumulates on every part; b reads the gat
 read_frame into device memory, c presents on the group's root, d is hrt_accumulate_present on the root.
 --baseline-lib PATH adds, to every repeat, variant b on another build of the library (what that build
 offers a group), alternating with this build's variants.
+--denoise runs two variants only, taking turns in one sitting: c, and
+  e  c with hrt_denoise_present in place of hrt_present (five guided a-trous passes, default sigmas; the
+     guide is the view's first hits, written once into device memory before the loop: the camera stands still)
+and writes profiles/present_loop_denoise.jsonl with the ratio e / c (single context only).
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -31,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = ("a", "b", "c", "d")
+DENOISE_VARIANTS = ("c", "e")
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
 
@@ -62,6 +67,10 @@ def child(variant: str, parts: int = 1) -> dict:
         raytrace.init()
         diffuse.next_frame(0, raytrace.image())
     frame, tickets = 1, []
+    guide = None
+    if variant == "e":
+        guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
+        raytraces[0].first_hits_into(camera, guide.data_ptr())
 
     def step():
         nonlocal frame
@@ -77,6 +86,8 @@ def child(variant: str, parts: int = 1) -> dict:
                 ctx.read_into(_lib.IMG_ACCUM, _lib.FMT_RGBA8, dst, nbytes)
             elif variant == "c":
                 tickets.append(ctx.present(_lib.IMG_ACCUM, dst, nbytes, W, H))
+            elif variant == "e":
+                tickets.append(ctx.denoise_present(dst, nbytes, W, H, guide_ptr=guide.data_ptr()))
         if len(tickets) > LAG:  # the frame of three back is on screen before its target is reused
             ctx.present_wait(tickets[-1 - LAG])
         frame += 1
@@ -103,10 +114,12 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS, help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e",), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
+    ap.add_argument("--denoise", action="store_true",
+                    help="variants c and e (hrt_denoise_present in place of hrt_present) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -118,9 +131,13 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
+    if a.denoise and a.parts > 1:
+        ap.error("--denoise runs on a single context (a partitioned context cannot denoise)")
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl")
-    order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in VARIANTS]
+        name = "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        a.out = os.path.join(ROOT, "profiles", name)
+    variants = DENOISE_VARIANTS if a.denoise else VARIANTS
+    order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
     for rep in range(a.repeats):
@@ -143,9 +160,12 @@ def main() -> int:
     med = {v: statistics.median(runs[v]) for v in runs}
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
-                               "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs},
-               "c_over_b": round(med["c"] / med["b"], 4), "d_over_c": round(med["d"] / med["c"], 4),
-               "d_minus_c_ms": round(med["d"] - med["c"], 4)}
+                               "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
+    if a.denoise:
+        summary.update(e_over_c=round(med["e"] / med["c"], 4), e_minus_c_ms=round(med["e"] - med["c"], 4))
+    else:
+        summary.update(c_over_b=round(med["c"] / med["b"], 4), d_over_c=round(med["d"] / med["c"], 4),
+                       d_minus_c_ms=round(med["d"] - med["c"], 4))
     if a.baseline_lib:
         summary["b_over_b_baseline"] = round(med["b"] / med["b_baseline"], 4)
     lines.append(json.dumps(summary))
