@@ -164,6 +164,27 @@ DEBUG_DENOISE_DENSE, DEBUG_DENOISE_LATTICE = 3, 4  # libhip_raytrace_debug.so on
 DENOISE_MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16
 DENOISE_SIGMAS = (8.0, 0.25, 0.5)  # HRT_DENOISE_SIGMA_COLOUR / _NORMAL / _DEPTH (hrt_denoise_defaults)
 
+
+class View(ctypes.Structure):
+    """hrt_view: a camera and the affine grid of its ray centres (128 bytes)."""
+
+    _fields_ = [("cam_pos", c_float * 4), ("cam_alignment_mat", c_float * 16), ("grid_first", c_float * 4),
+                ("grid_dx", c_float * 4), ("grid_dy", c_float * 4)]
+
+
+class ReprojectInfo(ctypes.Structure):
+    """hrt_reproject_info: one reprojection (32 bytes)."""
+
+    _fields_ = [("filter", c_uint32), ("flags", c_uint32), ("depth_tolerance", c_float), ("min_normal_dot", c_float),
+                ("reserved", c_uint32 * 4)]
+
+
+assert ctypes.sizeof(View) == 128 and ctypes.sizeof(ReprojectInfo) == 32
+REPROJECT_NEAREST, REPROJECT_BILINEAR = 0, 1  # hrt_reproject_filter
+REPROJECT_NAMES = {0: "nearest", 1: "bilinear"}
+REPROJECT_DEFAULTS = (0.02, 0.9)  # HRT_REPROJECT_DEPTH_TOLERANCE / _MIN_NORMAL_DOT (hrt_reproject_defaults)
+HISTORY_MAX = 1 << 24  # HRT_HISTORY_MAX: the largest max_history of hrt_accumulate_history
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -236,6 +257,7 @@ EXPORTED_SYMBOLS = (
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
     "hrt_denoise_defaults", "hrt_denoise", "hrt_denoise_present",
+    "hrt_reproject_defaults", "hrt_reproject", "hrt_accumulate_history", "hrt_fill_history", "hrt_read_history",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -316,6 +338,11 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_denoise": (c_int32, [P, POINTER(DenoiseInfo), P, c_uint32, P, c_size_t]),
         "hrt_denoise_present": (c_int32, [P, POINTER(DenoiseInfo), P, POINTER(PresentInfo), P, c_uint64,
                                           POINTER(c_uint64)]),
+        "hrt_reproject_defaults": (None, [POINTER(ReprojectInfo)]),
+        "hrt_reproject": (c_int32, [P, POINTER(ReprojectInfo), POINTER(View), P, POINTER(View), P]),
+        "hrt_accumulate_history": (c_int32, [P, c_uint32]),
+        "hrt_fill_history": (c_int32, [P, c_uint32]),
+        "hrt_read_history": (c_int32, [P, P, c_size_t]),
         "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
         "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),

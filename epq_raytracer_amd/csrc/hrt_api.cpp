@@ -24,6 +24,7 @@
 #include "hrt_bvh.h"
 #include "hrt_context.h"
 #include "hrt_denoise.h"
+#include "hrt_history.h"
 #include "hrt_host.h"
 #include "hrt_image.h"
 #include "hrt_kernels.h"
@@ -492,6 +493,9 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->dn_img[1]);
   free_dev(ctx, ctx->dn_guide);
   free_dev(ctx, ctx->dn_keys);
+  free_dev(ctx, ctx->hist_cnt);
+  free_dev(ctx, ctx->hist_cnt_next);
+  free_dev(ctx, ctx->hist_accum_next);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -1895,6 +1899,112 @@ extern "C" hrt_status hrt_denoise_present(hrt_context* ctx, const hrt_denoise_in
   // the filtered float image through the present pass unchanged
   HRT_HIP(ctx, hrt::launch_present(res, true, ctx->width, ctx->local_rows, present_target(target, dst), ctx->stream));
   return ticket_end(ctx, ev, ticket);
+}
+
+// ---- temporal history (kernels in hrt_history.hip) -----------------------------
+namespace {
+
+// What all four history calls refuse, and the count image: allocated and zeroed (on ctx->stream) by the first.
+hrt_status begin_history(hrt_context* ctx, const char* who) {
+  if (ctx->comm || ctx->part_count > 1)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT,
+                std::string(who) + ": a context of a row-tile partition or joined to a communicator keeps no history (a "
+                                   "reprojected pixel's source rows live on another part; the gathered form is out of scope)");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if (ctx->hist_cnt) return HRT_OK;
+  void* p = nullptr;
+  if ((st = ensure_staging(ctx, &p, ctx->npix() * 4, who)) != HRT_OK) return st;
+  ctx->hist_cnt = static_cast<uint32_t*>(p);
+  HRT_HIP(ctx, hipMemsetAsync(ctx->hist_cnt, 0, ctx->npix() * 4, ctx->stream));
+  return HRT_OK;
+}
+
+bool hits_on_device(hrt_context* ctx, const hrt_hit* hits) {
+  return query_direct(ctx, hits) && query_direct(ctx, hits + (ctx->npix() - 1));
+}
+
+}  // namespace
+
+extern "C" void hrt_reproject_defaults(hrt_reproject_info* info) {
+  if (!info) return;
+  *info = hrt_reproject_info{HRT_REPROJECT_BILINEAR, 0u, HRT_REPROJECT_DEPTH_TOLERANCE, HRT_REPROJECT_MIN_NORMAL_DOT,
+                             {0u, 0u, 0u, 0u}};
+}
+
+extern "C" hrt_status hrt_reproject(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
+                                    const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string("hrt_reproject: ") + what); };
+  if (!info) return bad("null info");
+  if (!prev || !cur) return bad("null view");
+  if (!prev_hits || !cur_hits) return bad("null hit array");
+  if (info->filter != HRT_REPROJECT_NEAREST && info->filter != HRT_REPROJECT_BILINEAR) return bad("unknown filter");
+  if (info->flags != 0) return bad("flags must be 0");
+  if (!(std::isfinite(info->depth_tolerance) && info->depth_tolerance >= 0.0f))
+    return bad("depth_tolerance must be finite and not negative");
+  if (!std::isfinite(info->min_normal_dot)) return bad("min_normal_dot must be finite");
+  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, "hrt_reproject");  // (the rejection)
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if ((uintptr_t)prev_hits % 16 != 0 || (uintptr_t)cur_hits % 16 != 0) return bad("the hit arrays must be 16-byte aligned");
+  if (!hits_on_device(ctx, prev_hits) || !hits_on_device(ctx, cur_hits))
+    return bad("the hit arrays must be width x height records in memory of the context's device");
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  if ((st = begin_history(ctx, "hrt_reproject")) != HRT_OK) return st;
+  const size_t np = ctx->npix();
+  void* p = ctx->hist_cnt_next;
+  if ((st = ensure_staging(ctx, &p, np * 4, "hrt_reproject")) != HRT_OK) return st;
+  ctx->hist_cnt_next = static_cast<uint32_t*>(p);
+  if ((st = ensure_staging(ctx, &ctx->hist_accum_next, np * ctx->px_bytes(), "hrt_reproject")) != HRT_OK) return st;
+  const hrt::ReprojectPass pass{ctx->accum, ctx->hist_cnt, ctx->hist_accum_next, ctx->hist_cnt_next, prev_hits, cur_hits,
+                                *prev, *cur, ctx->f32(), info->filter, ctx->width, ctx->local_rows,
+                                info->depth_tolerance, info->min_normal_dot};
+  HRT_HIP(ctx, hrt::launch_reproject(pass, ctx->stream));
+  // A' and N' become the context's accumulator and count image; the old ones are the next pass's targets
+  std::swap(ctx->accum, ctx->hist_accum_next);
+  std::swap(ctx->hist_cnt, ctx->hist_cnt_next);
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_accumulate_history(hrt_context* ctx, uint32_t max_history) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (max_history == 0 || max_history > hrt::kHistoryMax)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_accumulate_history: max_history must be 1..2^24");
+  hrt_status st = begin_history(ctx, "hrt_accumulate_history");
+  if (st != HRT_OK) return st;
+  const int l = ctx->cur_lane;  // next_image = the most recent trace
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // frames fold in call order
+  if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
+  HRT_HIP(ctx, hrt::launch_fold_history(ctx->accum, hrt::trace_image(ctx), ctx->hist_cnt, ctx->f32(), ctx->npix(),
+                                        max_history, ctx->stream));
+  if (ctx->cur_slot >= 0) {  // a slot of the deferred combiner's ring: its next trace waits for this fold
+    HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+    ctx->fold_set = true;
+  }
+  ctx->accumulates++;
+  return hrt::release_lane(ctx, l);
+}
+
+extern "C" hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = begin_history(ctx, "hrt_fill_history");
+  if (st != HRT_OK) return st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  HRT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->hist_cnt, (int)count, ctx->npix(), ctx->stream));
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t bytes) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (!dst) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_read_history: null destination");
+  const size_t need = ctx->npix() * 4;
+  if (bytes < need) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_read_history: destination too small");
+  hrt_status st = begin_history(ctx, "hrt_read_history");
+  if (st != HRT_OK) return st;
+  HRT_HIP(ctx, hipMemcpyAsync(dst, ctx->hist_cnt, need, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HRT_OK;
 }
 
 extern "C" hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done) {

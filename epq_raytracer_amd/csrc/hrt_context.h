@@ -231,6 +231,13 @@ struct hrt_context {
   void* dn_img[2] = {};
   void* dn_guide = nullptr;
   void* dn_keys = nullptr;
+  // Temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history): the count
+  // image N, one uint32 per pixel, allocated and zeroed by the first call of any of the four; and what
+  // hrt_reproject writes A' and N' into, allocated by its first call -- after the pass they are swapped with
+  // `accum` and `hist_cnt`, so the pass never reads a texel it has replaced
+  uint32_t* hist_cnt = nullptr;
+  uint32_t* hist_cnt_next = nullptr;
+  void* hist_accum_next = nullptr;
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

@@ -85,6 +85,26 @@ def sphere_records(spheres: List[Sphere]) -> np.ndarray:
     return np.array([s.record() for s in spheres], dtype=_lib.SPHERE_DTYPE)
 
 
+class View:
+    """hrt_view of a camera: its position and view matrix as ``RayTracePipeline.push_constants`` writes them,
+    and the affine grid of the ray centres (hrt_host_ray_grid) of an image of ``image_size`` under
+    ``settings`` (anything with camera_focal_length, viewport_height and up).  ``record`` is the
+    _lib.View that hrt_reproject takes."""
+
+    def __init__(self, camera: Camera, image_size, settings):
+        lib = _lib.load()
+        first, dx, dy = ((ctypes.c_float * 3)() for _ in range(3))
+        lib.hrt_host_ray_grid(int(image_size[0]), int(image_size[1]), float(np.float32(settings.camera_focal_length)),
+                              float(np.float32(settings.viewport_height)), _lib.f3(settings.up), first, dx, dy, None)
+        rec = _lib.View()
+        pos = np.asarray(camera.position, np.float32)
+        rec.cam_pos[:] = [float(pos[0]), float(pos[1]), float(pos[2]), 1.0]
+        rec.cam_alignment_mat[:] = [float(v) for v in view_matrix(camera.direction, camera.up)]
+        for dst, src in ((rec.grid_first, first), (rec.grid_dx, dx), (rec.grid_dy, dy)):
+            dst[:] = [float(src[0]), float(src[1]), float(src[2]), 0.0]
+        self.record = rec
+
+
 # ---- the device context (one hrt_context = the trace image + the accumulated image) ------------
 
 class HrtContext:
@@ -331,6 +351,51 @@ class HrtContext:
                                                  ctypes.byref(target), ctypes.c_void_p(dst_ptr), int(nbytes),
                                                  ctypes.byref(t)), "hrt_denoise_present")
         return t.value
+
+    # ---- temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history) ----
+
+    def reproject_info(self, filter: Optional[int] = None, depth_tolerance: Optional[float] = None,  # noqa: A002
+                       min_normal_dot: Optional[float] = None) -> _lib.ReprojectInfo:
+        """hrt_reproject_defaults with the given fields replaced (None: the default)."""
+        info = _lib.ReprojectInfo()
+        self.lib.hrt_reproject_defaults(ctypes.byref(info))
+        if filter is not None:
+            info.filter = int(filter)
+        if depth_tolerance is not None:
+            info.depth_tolerance = float(depth_tolerance)
+        if min_normal_dot is not None:
+            info.min_normal_dot = float(min_normal_dot)
+        return info
+
+    def reproject(self, prev: "View", prev_hits_ptr: int, cur: "View", cur_hits_ptr: int,
+                  info: Optional[_lib.ReprojectInfo] = None, **fields) -> None:
+        """hrt_reproject: the accumulator and the count image of view ``prev`` become those of view ``cur``
+        (DESIGN.md S15).  The hit pointers are 16-byte aligned device pointers to W x H hrt_hit records
+        (``intersect_primary_into`` of the whole image under each view).  ``info`` or the fields of
+        ``reproject_info``.  Only enqueues: keep the hit arrays unchanged until the pass has run."""
+        info = info if info is not None else self.reproject_info(**fields)
+        self._check(self.lib.hrt_reproject(self.handle, ctypes.byref(info), ctypes.byref(prev.record),
+                                           ctypes.c_void_p(prev_hits_ptr), ctypes.byref(cur.record),
+                                           ctypes.c_void_p(cur_hits_ptr)), "hrt_reproject")
+
+    def accumulate_history(self, max_history: int) -> None:
+        """hrt_accumulate_history: the trace image folded into the accumulator with every pixel's own frame
+        count, which then grows by one up to max_history (1 .. 2^24)."""
+        self._check(self.lib.hrt_accumulate_history(self.handle, int(max_history)), "hrt_accumulate_history")
+
+    def fill_history(self, count: int) -> None:
+        """hrt_fill_history: every pixel's count = count (0: no history)."""
+        self._check(self.lib.hrt_fill_history(self.handle, int(count)), "hrt_fill_history")
+
+    def read_history_into(self, dst_ptr: int, nbytes: int) -> None:
+        """hrt_read_history into caller memory (host or device pointer).  Blocking."""
+        self._check(self.lib.hrt_read_history(self.handle, ctypes.c_void_p(dst_ptr), int(nbytes)), "hrt_read_history")
+
+    def read_history(self) -> np.ndarray:
+        """hrt_read_history: the count image as uint32 (local_rows, W)."""
+        out = np.empty((self.local_rows, self.width), dtype=np.uint32)
+        self.read_history_into(out.ctypes.data, out.nbytes)
+        return out
 
     # ---- ray queries (hrt_intersect, hrt_intersect_primary) ----
 
@@ -718,6 +783,14 @@ class DiffusePipeline:
         if next_image.ctx is not self.ctx or next_image.image_id != _lib.IMG_TRACE:
             raise ValueError("next_image must be the trace image of the same context")
         self.ctx.accumulate(frame_num)
+
+    def next_frame_history(self, next_image: Image, max_history: int = 32) -> None:
+        """``next_frame`` with per-pixel frame counts (hrt_accumulate_history; not a reference feature): after a
+        camera move, ``HrtContext.reproject`` first, then this -- a pixel whose surface point the old view
+        held keeps its history, the others start again with this frame."""
+        if next_image.ctx is not self.ctx or next_image.image_id != _lib.IMG_TRACE:
+            raise ValueError("next_image must be the trace image of the same context")
+        self.ctx.accumulate_history(max_history)
 
     def denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **sigmas) -> np.ndarray:
         """The accumulated image through the denoise pass (hrt_denoise), as uint8 or float32 (H, W, 4):

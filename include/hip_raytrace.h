@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): the denoise pass -- hrt_denoise_method, hrt_denoise_info,
+/* 6, additive (no bump: nothing existing changed): temporal history -- hrt_view, hrt_reproject_filter,
+ * hrt_reproject_info, hrt_reproject_defaults, hrt_reproject, hrt_accumulate_history, hrt_fill_history,
+ * hrt_read_history.
+ * 6, additive (no bump: nothing existing changed): the denoise pass -- hrt_denoise_method, hrt_denoise_info,
  * hrt_denoise_defaults, hrt_denoise, hrt_denoise_present.
  * 6, additive (no bump: nothing existing changed): radiance queries -- hrt_radiance_query, hrt_radiance_stats,
  * hrt_radiance.
@@ -314,6 +317,29 @@ typedef struct hrt_denoise_info { /* 32 bytes */
   uint32_t reserved;   /* ignored */
 } hrt_denoise_info;
 
+/* ---- temporal history (hrt_reproject, hrt_accumulate_history) ---- */
+/* A view: the camera of a push block plus the affine grid of its ray centres in camera space --
+ * the centre of pixel (x, y) is first + dx x + dy y, as hrt_host_ray_grid returns first / px / py. */
+typedef struct hrt_view {            /* 128 bytes */
+  float cam_pos[4];                  /* as hrt_push_constants */
+  float cam_alignment_mat[16];       /* as hrt_push_constants; mat3 used, assumed a rotation */
+  float grid_first[4], grid_dx[4], grid_dy[4]; /* w unused */
+} hrt_view;
+
+typedef enum hrt_reproject_filter { HRT_REPROJECT_NEAREST = 0, HRT_REPROJECT_BILINEAR = 1 } hrt_reproject_filter;
+/* hrt_reproject_defaults' thresholds: design parameters chosen on the CPU oracle's frames */
+#define HRT_REPROJECT_DEPTH_TOLERANCE 0.02f
+#define HRT_REPROJECT_MIN_NORMAL_DOT 0.9f
+#define HRT_HISTORY_MAX 16777216u /* the largest max_history of hrt_accumulate_history: 2^24 */
+
+typedef struct hrt_reproject_info { /* 32 bytes */
+  uint32_t filter;       /* hrt_reproject_filter */
+  uint32_t flags;        /* must be 0 */
+  float depth_tolerance; /* finite, >= 0: a tap is kept when |expected - stored depth| <= tolerance * expected */
+  float min_normal_dot;  /* finite: a tap is kept when dot(normal now, normal then) >= this; -2 disables */
+  uint32_t reserved[4];  /* ignored */
+} hrt_reproject_info;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -371,6 +397,15 @@ HRT_STATIC_ASSERT(sizeof(hrt_denoise_info) == 32 && offsetof(hrt_denoise_info, m
                       offsetof(hrt_denoise_info, sigma_colour) == 16 && offsetof(hrt_denoise_info, sigma_depth) == 24 &&
                       offsetof(hrt_denoise_info, reserved) == 28,
                   "hrt_denoise_info");
+
+HRT_STATIC_ASSERT(sizeof(hrt_view) == 128 && offsetof(hrt_view, cam_alignment_mat) == 16 &&
+                      offsetof(hrt_view, grid_first) == 80 && offsetof(hrt_view, grid_dx) == 96 &&
+                      offsetof(hrt_view, grid_dy) == 112,
+                  "hrt_view");
+HRT_STATIC_ASSERT(sizeof(hrt_reproject_info) == 32 && offsetof(hrt_reproject_info, flags) == 4 &&
+                      offsetof(hrt_reproject_info, depth_tolerance) == 8 &&
+                      offsetof(hrt_reproject_info, min_normal_dot) == 12 && offsetof(hrt_reproject_info, reserved) == 16,
+                  "hrt_reproject_info");
 
 typedef struct hrt_context hrt_context;
 
@@ -888,6 +923,45 @@ hrt_status hrt_denoise(hrt_context* ctx, const hrt_denoise_info* info, const hrt
  * target->image_id must equal info->image_id. */
 hrt_status hrt_denoise_present(hrt_context* ctx, const hrt_denoise_info* info, const hrt_hit* guide,
                                const hrt_present_info* target, void* dst, uint64_t dst_bytes, uint64_t* ticket);
+/* ---- temporal history (DESIGN.md §2 S15 pins the arithmetic, §28 the kernels) -----------------------------
+ * The context owns a count image N: one uint32 per pixel, the number of frames that pixel's accumulator texel
+ * holds.  It is allocated and zeroed by the first call of any of the four functions below, freed by
+ * hrt_destroy, and neither read nor written by anything else (hrt_accumulate, hrt_compute_n, ... keep their
+ * single frame number).  hrt_accumulate_history folds the trace image into the accumulator with the pixel's own
+ * count as the combiner's frame number; hrt_reproject carries accumulator and counts from the previous view to
+ * the current one through the two views' first hits, rejecting (count 0, texel cleared) every pixel whose
+ * surface point the previous view did not hold.  Every byte is defined by S15: both libraries and the numpy
+ * restatement in tests/history_ref.py agree bit for bit.
+ *
+ * hrt_reproject, hrt_accumulate_history and hrt_fill_history are NON-blocking, ordered on the context's stream
+ * after the work issued so far (deferred combines are folded first).  hrt_accumulate_history joins and releases
+ * the current trace lane exactly as hrt_accumulate does and hrt_stats.accumulates counts it once; it appends no
+ * fold record.  Nothing else in hrt_stats, no counter, no ticket and no trace image is touched.
+ *
+ * prev_hits / cur_hits: width x height hrt_hit records in memory of the context's device, 16-byte aligned,
+ * row-major in trace-image row order -- what hrt_intersect_primary writes for the whole image.  They are read
+ * by the enqueued pass: keep them unchanged until it has run.
+ *
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued (the message names the reason): a NULL
+ * argument; an unknown filter; flags != 0; a tolerance that is not finite or negative; a min_normal_dot that is
+ * not finite; max_history 0 or above HRT_HISTORY_MAX; hit arrays that are not memory of the context's device or
+ * not 16-byte aligned; a too small dst; and a context of a row-tile partition (part_count > 1) or one joined to
+ * any communicator: a reprojected pixel's source rows live on another part, and the gathered form is
+ * deliberately out of scope. */
+
+/* BILINEAR and the default thresholds (DESIGN.md §28 has the grid they were chosen from). */
+void hrt_reproject_defaults(hrt_reproject_info* info);
+/* Accumulator and count image of the view `prev` become those of the view `cur` (S15). */
+hrt_status hrt_reproject(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev, const hrt_hit* prev_hits,
+                         const hrt_view* cur, const hrt_hit* cur_hits);
+/* Per pixel with count n: n == 0 copies the trace texel (alpha 255 / 1.0f), else the combiner's fold with
+ * frame = n; then the count becomes min(n + 1, max_history) (1 <= max_history <= HRT_HISTORY_MAX). */
+hrt_status hrt_accumulate_history(hrt_context* ctx, uint32_t max_history);
+/* Every pixel's count = count (0: no history). */
+hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count);
+/* BLOCKING: the count image, height x width uint32 in trace-image row order, to host or device memory at dst
+ * (bytes >= height * width * 4). */
+hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t bytes);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

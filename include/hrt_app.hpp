@@ -183,6 +183,20 @@ struct RayTracerSettings {  // src/raytracing_app.rs:17-29
   Vec3 up{0.0f, 1.0f, 0.0f};
 };
 
+// The hrt_view of a camera (hrt_reproject): its position and view matrix as RayTracePipeline::push_constants
+// writes them, and the affine grid of the ray centres (hrt_host_ray_grid) of an image of image_size.
+inline hrt_view view_of(const Camera& camera, std::array<uint32_t, 2> image_size, const RayTracerSettings& settings) {
+  hrt_view v{};
+  v.cam_pos[0] = camera.position[0];
+  v.cam_pos[1] = camera.position[1];
+  v.cam_pos[2] = camera.position[2];
+  v.cam_pos[3] = 1.0f;
+  hrt_host_view_matrix(camera.direction.data(), camera.up.data(), v.cam_alignment_mat);
+  (void)hrt_host_ray_grid(image_size[0], image_size[1], settings.camera_focal_length, settings.viewport_height,
+                          settings.up.data(), v.grid_first, v.grid_dx, v.grid_dy, nullptr);
+  return v;
+}
+
 // ---- the device context: the trace image and the accumulated image of one hrt_context -----------
 class Context {
  public:
@@ -254,6 +268,29 @@ class Context {
     uint64_t ticket = 0;
     check(hrt_denoise_present(get(), &info, guide, &target, dst, dst_bytes, &ticket), "hrt_denoise_present", get());
     return ticket;
+  }
+  // temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history; not a reference
+  // feature).  The hit arrays are width x height hrt_hit records in memory of the context's device, 16-byte
+  // aligned (RayTracePipeline::first_hits_into under each view); reproject, accumulate_history and fill_history
+  // only enqueue, read_history blocks.
+  static hrt_reproject_info reproject_defaults() {
+    hrt_reproject_info info;
+    hrt_reproject_defaults(&info);
+    return info;
+  }
+  void reproject(const hrt_view& prev, const hrt_hit* prev_hits, const hrt_view& cur, const hrt_hit* cur_hits,
+                 const hrt_reproject_info* info = nullptr) {
+    const hrt_reproject_info ri = info ? *info : reproject_defaults();
+    check(hrt_reproject(get(), &ri, &prev, prev_hits, &cur, cur_hits), "hrt_reproject", get());
+  }
+  void accumulate_history(uint32_t max_history) {
+    check(hrt_accumulate_history(get(), max_history), "hrt_accumulate_history", get());
+  }
+  void fill_history(uint32_t count) { check(hrt_fill_history(get(), count), "hrt_fill_history", get()); }
+  std::vector<uint32_t> read_history() {
+    std::vector<uint32_t> out((size_t)layout_.local_rows * layout_.width);
+    check(hrt_read_history(get(), out.data(), out.size() * sizeof(uint32_t)), "hrt_read_history", get());
+    return out;
   }
   bool present_done(uint64_t ticket) const {
     uint32_t done = 0;
@@ -530,6 +567,14 @@ class DiffusePipeline {  // src/diffuse.rs:22-136 (image_combiner.glsl)
     if (next_image.ctx != ctx_ || next_image.id != HRT_IMG_TRACE)
       throw HrtError(HRT_ERR_INVALID_ARGUMENT, "next_frame: next_image must be the trace image of the same context");
     check(hrt_accumulate(ctx_->get(), frame_num), "hrt_accumulate", ctx_->get());
+  }
+  // next_frame with per-pixel frame counts (hrt_accumulate_history; not a reference feature): after a camera
+  // move, Context::reproject first, then this -- a pixel whose surface point the old view held keeps its
+  // history, the others start again with this frame.
+  void next_frame_history(const Image& next_image, uint32_t max_history = 32) {
+    if (next_image.ctx != ctx_ || next_image.id != HRT_IMG_TRACE)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "next_frame_history: next_image must be the trace image of the same context");
+    ctx_->accumulate_history(max_history);
   }
   // The accumulated image through the denoise pass (hrt_denoise; not a reference feature): guide = the view's
   // first hits on the device (RayTracePipeline::first_hits_into) or null for the colour-only filter; info null:

@@ -20,6 +20,13 @@ offers a group), alternating with this build's variants.
   e  c with hrt_denoise_present in place of hrt_present (five guided a-trous passes, default sigmas; the
      guide is the view's first hits, written once into device memory before the loop: the camera stands still)
 and writes profiles/present_loop_denoise.jsonl with the ratio e / c (single context only).
+--moving runs e and two variants of the temporal pipeline, taking turns in one sitting (single context only):
+  f  the camera moves every frame (a sway of up to two pixels and a short step): hrt_intersect_primary of the
+     new view into device memory (blocking), trace, hrt_reproject from the previous view, hrt_accumulate_history
+     (max_history 32) and hrt_denoise_present guided by the new first hits
+  g  f with the first hits taken on a second context of the same scene, so that the blocking query does not
+     wait for the rendering context's stream
+and writes profiles/present_loop_history.jsonl with f / e, g / e and f - g.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -36,6 +43,8 @@ sys.path.insert(0, ROOT)
 
 VARIANTS = ("a", "b", "c", "d")
 DENOISE_VARIANTS = ("c", "e")
+MOVING_VARIANTS = ("e", "f", "g")
+MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
 
@@ -72,8 +81,50 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
+    moving = variant in ("f", "g")
+    if moving:
+        import numpy as np
+
+        # first hits of the previous and the current view: LAG + 2 buffers, so that one the enqueued passes of
+        # the last LAG frames still read is never overwritten
+        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(LAG + 2)]
+        guide_ctx, guide_rt = ctx, raytraces[0]
+        if variant == "g":
+            guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
+            guide_rt = E.RayTracePipeline(guide_ctx, SIZE, settings)
+        d0 = np.asarray(camera.direction, np.float64) / np.linalg.norm(camera.direction)
+        side = np.cross(d0, np.asarray(camera.up, np.float64))
+        side /= np.linalg.norm(side)
+        px = 2.0 / H
+
+        def camera_at(k):
+            sway = 2.0 * px * np.sin(0.7 * k)
+            pos = [float(c + 0.01 * k * s) for c, s in zip(camera.position, side)]
+            return E.Camera(pos, [float(v) for v in d0 + sway * side], camera.up)
+
+        prev_view = E.View(camera, SIZE, settings)
+        guide_rt.first_hits_into(camera, guides[0].data_ptr())
+
+    def step_moving():
+        nonlocal frame, prev_view
+        dst = targets[frame % len(targets)].data_ptr()
+        cam = camera_at(frame)
+        view = E.View(cam, SIZE, settings)
+        prev_hits, cur_hits = guides[(frame - 1) % len(guides)], guides[frame % len(guides)]
+        guide_rt.first_hits_into(cam, cur_hits.data_ptr())  # blocking
+        raytraces[0].compute(cam, frame)
+        ctx.reproject(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
+        diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY)
+        tickets.append(ctx.denoise_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+        if len(tickets) > LAG:
+            ctx.present_wait(tickets[-1 - LAG])
+        prev_view = view
+        frame += 1
+
     def step():
         nonlocal frame
+        if moving:
+            return step_moving()
         dst = targets[frame % len(targets)].data_ptr()
         for raytrace in raytraces:
             raytrace.compute(camera, frame)
@@ -107,6 +158,8 @@ def child(variant: str, parts: int = 1) -> dict:
     out = {"variant": variant, "parts": parts, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
            "width": W, "height": H, "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
            "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
+    if variant == "g":
+        guide_ctx.close()
     for c in ctxs:
         c.close()
     return out
@@ -114,12 +167,15 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e",), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
     ap.add_argument("--denoise", action="store_true",
                     help="variants c and e (hrt_denoise_present in place of hrt_present) only, taking turns")
+    ap.add_argument("--moving", action="store_true",
+                    help="variants e, f (the temporal pipeline with a moving camera) and g (f with the first hits "
+                         "taken on a second context) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -131,12 +187,12 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    if a.denoise and a.parts > 1:
-        ap.error("--denoise runs on a single context (a partitioned context cannot denoise)")
+    if (a.denoise or a.moving) and a.parts > 1:
+        ap.error("--denoise and --moving run on a single context (a partitioned context cannot denoise or keep history)")
     if a.out is None:
-        name = "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        name = "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
         a.out = os.path.join(ROOT, "profiles", name)
-    variants = DENOISE_VARIANTS if a.denoise else VARIANTS
+    variants = MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
     order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
@@ -161,7 +217,11 @@ def main() -> int:
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
                                "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
-    if a.denoise:
+    if a.moving:
+        summary.update(f_over_e=round(med["f"] / med["e"], 4), f_minus_e_ms=round(med["f"] - med["e"], 4),
+                       g_over_e=round(med["g"] / med["e"], 4), g_minus_e_ms=round(med["g"] - med["e"], 4),
+                       f_minus_g_ms=round(med["f"] - med["g"], 4))
+    elif a.denoise:
         summary.update(e_over_c=round(med["e"] / med["c"], 4), e_minus_c_ms=round(med["e"] - med["c"], 4))
     else:
         summary.update(c_over_b=round(med["c"] / med["b"], 4), d_over_c=round(med["d"] / med["c"], 4),
