@@ -203,6 +203,7 @@ OPT_FRAMES_PER_LAUNCH, OPT_OVERLAP, OPT_BUSY_SPLIT, OPT_BVH_WIDTH, OPT_WQ_NODE_R
 OPT_COMM_TIMEOUT_MS, OPT_DEFER_COMBINE, OPT_FOLD_RECORDS = 17, 18, 19
 OPT_SKY_LANE = 20  # BUNDLE_WQ: sky items on trace_sky beside the main kernel (-1 auto, 0 off, 1 on)
 OPT_WQ_LDS_NODES = 21  # BUNDLE_WQ_L2: nodes of the breadth-first image kept in LDS (-1 auto, 0 none, n)
+OPT_PRIMARY_BATCH = 22  # fused loop: primary segments join a bounce batch's trip from this many ready lanes (0 auto)
 DEBUG_OPT_FAIL_ALLOC = 1001  # libhip_raytrace_debug.so only
 DEBUG_OPT_WQ_TRI_CAP = 1002  # libhip_raytrace_debug.so only
 DEBUG_OPT_GRAB_RUNS = 1003  # libhip_raytrace_debug.so only
@@ -245,7 +246,7 @@ DIAG_NAMES = ("primary_iters", "primary_considered", "primary_survivors", "bounc
               "shade_cycles", "bounce_stage2", "bounce_front", "bvh_trips",
               "bvh_leaf_trips", "band_scan_max", "band_scan_len", "sky_items", "sky_cycles",
               "primary_lanes", "loop_iters", "live_lanes", "wq_steps_16", "wq_steps_32", "wq_steps_48",
-              "wq_steps_64", "wq_members", "dir_lanes")
+              "wq_steps_64", "wq_members", "dir_lanes", "primary_deferred", "batch_only_iters")
 SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh_built", "bvh_band_entries",
                     "bvh_sah_milli", "bvh_margin_milli")
 

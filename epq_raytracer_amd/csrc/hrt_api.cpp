@@ -813,6 +813,7 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
   p.cam_tris = s.cam_tris[l];
   p.cam_cull = s.cam_cull[l];
   p.sec_batch = ctx->sec_batch;
+  p.prim_batch = ctx->prim_batch;
   p.sched = lane.sched;
   p.tile_cost = lane.tile_cost;
   p.item_buf = lane.item_buf;
@@ -2338,6 +2339,11 @@ extern "C" hrt_status hrt_set_option(hrt_context* ctx, uint32_t key, int64_t val
       if (value < 0 || value > 64)
         return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "secondary batch must be 0 (auto) or in [1, 64]");
       ctx->sec_batch = (uint32_t)value;
+      return HRT_OK;
+    case HRT_OPT_PRIMARY_BATCH:
+      if (value < 0 || value > 64)
+        return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "primary batch must be 0 (auto) or in [1, 64]");
+      ctx->prim_batch = (uint32_t)value;
       return HRT_OK;
     case HRT_OPT_SPLIT:
       if (value < 0 || value > 64 || (value & (value - 1)) != 0)

@@ -35,6 +35,8 @@ struct TraceParams {
   float4* cam_tris;              // 4 float4 per record: (ao, num_t) (e1, index bits) (e2, -) (n, -)
   float4* cam_cull;              // 5 float4 per record: bundle-cull linear forms + margins
   uint32_t sec_batch;            // bounce segments run once this many lanes of a wave wait (1..64)
+  uint32_t prim_batch;           // a trip that runs a bounce batch runs primary segments too once this many
+                                 // lanes are ready for one (1..64; 1: whenever a lane is ready)
   // Persistent (LDS) variants' scheduler: sched[1] item count, [2] heavy tiles,
   // [3] first heavy cost bucket, [5] cooperative-item counter, [6..7] u64 sum of tile costs,
   // [8..) planner histogram / offsets / cursors, [1000] the plan's trailing sky items, [1002..1003] the u64

@@ -857,6 +857,7 @@ struct Diag {
   uint32_t wq_fill[4] = {0, 0, 0, 0};  // BUNDLE_WQ: node steps with 1-16 / 17-32 / 33-48 / 49-64 node pairs
   uint32_t wq_members = 0;             // ... the members of the groups this lane popped (valid slots), summed
   uint32_t dir_lanes = 0;              // lanes whose direction a bounce batch computed (shade_dir)
+  uint32_t prim_deferred = 0, batch_only_iters = 0;  // fused loop: trips that ran a batch alone, and their ready lanes
 };
 
 __device__ __forceinline__ float wave_min_all(float v) {  // all 64 lanes active
@@ -2596,7 +2597,10 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
 #endif
   // bounce batch threshold scaled to the item's active lanes (a split tile's row group has 8/k rows):
   // a batch of few lanes then runs alongside the other lanes' primary segments instead of after them
-  const uint32_t sec_thresh = max(1u, (kargs()->sec_batch * (uint32_t)__popcll(__ballot(active)) + 63u) / 64u);
+  const uint32_t nactive = (uint32_t)__popcll(__ballot(active));
+  const uint32_t sec_thresh = max(1u, (kargs()->sec_batch * nactive + 63u) / 64u);
+  // ... and the primary phase's threshold beside a batch, scaled the same way
+  const uint32_t prim_thresh = max(1u, (kargs()->prim_batch * nactive + 63u) / 64u);
   int sample = 0;
   Path p;
   p.bounce = pc.max_bounces + 1;
@@ -2668,6 +2672,10 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
         }
       }
     }
+    // ready: the lane's path has ended and its pixel-frame has a sample left, which starts in the trip
+    // that runs its primary segment (below).  A lane with no sample left (and, pooled, no pool entry: the
+    // refill above made it done) is done here, whatever the trip runs, and never counts as ready.
+    bool ready = false;
     if (!done && p.bounce > pc.max_bounces) {
       // (a while: with num_samples <= 0 every frame of the run ends at once and each must still be stored)
       while (!pool && sample >= pc.num_samples && fr + 1u < nrun) {  // the pixel's next frame of the run
@@ -2680,37 +2688,51 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
       if (sample >= pc.num_samples) {
         done = true;
       } else {
-        ++sample;
-        // the camera (matrix, jitter, position) read at the sample's start (kargs): 13 values not held
-        // in SGPRs across the loop
-        const KArgs K = kargs();
-        const f3 dir = get_ray_dir(K->pc, centre, state);
-        p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), mk(K->pc.cam_pos[0], K->pc.cam_pos[1], K->pc.cam_pos[2]),
-                 normalize_fl(dir), 0, true};
+        ready = true;
       }
     }
-    const bool ready = !done && p.bounce == 0;  // a primary segment to run
-    const bool waiting = !done && p.bounce != 0;
+    const bool waiting = !done && !ready;  // 0 < p.bounce <= max_bounces: a bounce segment to run
     const uint32_t nwait = (uint32_t)__popcll(__ballot(waiting));
+    const uint32_t nready = (uint32_t)__popcll(__ballot(ready));
+    // The phases run when their lanes are full: the batch once sec_thresh lanes wait, or
+    // when no lane is ready; the primary phase in a trip without a batch, and beside a batch once
+    // prim_thresh lanes are ready (1: in every trip with a ready lane).  A deferred lane keeps its state
+    // and draws nothing, exactly as a waiting lane does, so its pixel's samples and RNG draws keep their order.
     // (r04d, measured and dropped: primary segments waiting too while a bounce batch runs and fewer than
     // 8 lanes have one -- island 1.859 -> 1.878 ms)
-    const bool prim = ready;
-    const bool any_prim = __any(prim);
-    const bool run_sec = nwait > 0 && (nwait >= sec_thresh || !any_prim);
+    // Progress: a lane that is not done is ready or waiting.  nready > 0 without a batch runs the primary
+    // phase, nready == 0 leaves nwait > 0 and runs the batch: every trip with a live lane runs a phase,
+    // and a phase runs one of the finitely many segments of each lane in it.
+    const bool run_sec = nwait > 0 && (nwait >= sec_thresh || nready == 0);
+    const bool run_prim = nready > 0 && (!run_sec || nready >= prim_thresh);
+    const bool prim = ready && run_prim;
     const bool sec = waiting && run_sec;
+    if (prim) {
+      ++sample;
+      // the camera (matrix, jitter, position) read at the sample's start (kargs): 13 values not held
+      // in SGPRs across the loop
+      const KArgs K = kargs();
+      const f3 dir = get_ray_dir(K->pc, centre, state);
+      p = Path{mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), mk(K->pc.cam_pos[0], K->pc.cam_pos[1], K->pc.cam_pos[2]),
+               normalize_fl(dir), 0, true};
+    }
     Closest c{kFltMax, 0, 0u, 0u};
     uint64_t t0 = 0, t1 = 0, t2 = 0, tb = 0;
     if (D && P.diag) {
-      dg.prim_iters += any_prim ? 1u : 0u;
+      dg.prim_iters += run_prim ? 1u : 0u;
       dg.sec_iters += run_sec ? 1u : 0u;
       dg.sec_lanes += run_sec ? nwait : 0u;
-      dg.prim_lanes += (uint32_t)__popcll(__ballot(prim));
-      dg.loop_iters += 1u;
+      dg.prim_lanes += run_prim ? nready : 0u;
+      dg.prim_deferred += run_prim ? 0u : nready;  // (then a batch runs: nready > 0 without one runs the phase)
+      dg.batch_only_iters += run_sec && !run_prim ? 1u : 0u;
+      // (an item's last trip only finds every lane done and runs nothing: not counted, so that every
+      // counted trip ran a phase)
+      dg.loop_iters += nready + nwait > 0 ? 1u : 0u;
       dg.live_lanes += (uint32_t)__popcll(__ballot(!done));
       t0 = __builtin_readcyclecounter();
     }
-    if (co.w == 0) co.work += 2u + (any_prim ? 1u + (tl.ok ? tl.n : 64u) : 0u);  // shading, primary list
-    if (any_prim) {
+    if (co.w == 0) co.work += 2u + (run_prim ? 1u + (tl.ok ? tl.n : 64u) : 0u);  // shading, primary list
+    if (run_prim) {
       if (tl.ok) {
         const uint32_t tested = world_hit_tile(kscene(), P, tl, prim, p.pos, p.dir, tests, c);
         if (D && P.diag) {
@@ -2811,6 +2833,10 @@ __device__ __forceinline__ void trace_fused_split(const TraceParams& P, uint32_t
     atomicAdd(&P.diag[21], (unsigned long long)dg.prim_lanes);
     atomicAdd(&P.diag[22], (unsigned long long)dg.loop_iters);
     atomicAdd(&P.diag[23], (unsigned long long)dg.live_lanes);
+    if (dg.batch_only_iters) {
+      atomicAdd(&P.diag[30], (unsigned long long)dg.prim_deferred);
+      atomicAdd(&P.diag[31], (unsigned long long)dg.batch_only_iters);
+    }
     if (is_wq(Bounce)) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) atomicAdd(&P.diag[24 + b], (unsigned long long)dg.wq_fill[b]);
@@ -3756,7 +3782,8 @@ hipError_t launch_trace(const TraceParams& p0, const LaunchPlan& plan, hipStream
   TraceParams p = p0;
   const int k = plan.kernel;
   const KernelTraits& kt = kernel_traits(k);
-  if (p.sec_batch == 0) p.sec_batch = plan.sec_batch;
+  p.sec_batch = batch_threshold(p.sec_batch, plan.sec_batch);
+  p.prim_batch = batch_threshold(p.prim_batch, plan.prim_batch);
   if (kt.camera_lists && p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
   if (!kt.persistent) {
     const int px = plan.block == 1024 ? 32 : 16;  // a workgroup's square of pixels

@@ -115,21 +115,29 @@ struct KernelTraits {
   // kernel, whose scenes bounce far more (cave 20 / 28 / 36 / 44 / 56: 7.43 / 7.38 / 7.31 / 7.32 /
   // 7.45 ms; island stays best at 28: profiles/r02v_ab.txt)
   uint32_t sec_batch, sec_batch_node_r;
+  // primary threshold, auto (HRT_OPT_PRIMARY_BATCH): ready lanes from which a trip that runs a bounce batch
+  // runs the primary phase too.  1 is the schedule without it.  BUNDLE_WQ: 48 at its bounce thresholds
+  // (profiles/phase_batch_bench_ab.txt): against the parent, interleaved, island 2.4% and cave 1.2%
+  // faster at the bench's medians and faster in every pair of runs, where 1 -- the parent's schedule in the
+  // restructured loop -- measured 1.4% slower on island.  Above 64 - 28 the phases alternate strictly, so 40
+  // counts the same.  The pair 40 / 36 (40 / 44 with per-node radii) gains 4.7% in 20-frame launches and needs the
+  // bounce thresholds above changed with it: a change of its own.  The other rows were not measured and keep 1
+  uint32_t prim_batch, prim_batch_node_r;
 };
 constexpr int kNumKernels = HRT_KERNEL_BUNDLE_WQ_L2 + 1;
 inline constexpr KernelTraits kKernelTraits[kNumKernels] = {
-    // persist lists  hier   sky    pairs  fallback                  split_k sec_batch
-    {false, false, false, false, false, HRT_KERNEL_AUTO, 1, 48, 48},  // AUTO (plan_trace's ladder picks a row)
-    {false, false, false, false, false, HRT_KERNEL_LITERAL, 1, 48, 48},
-    {false, false, false, false, false, HRT_KERNEL_BRUTE, 1, 48, 48},
-    {false, false, false, false, false, HRT_KERNEL_BRUTE, 1, 48, 48},             // BRUTE_LDS
-    {false, true, false, false, false, HRT_KERNEL_BUNDLE, 1, 48, 48},
-    {false, true, false, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48},
-    {false, true, true, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48},          // BUNDLE_BVH
-    {true, true, false, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48},          // BUNDLE_CULL_LDS
-    {true, true, true, false, false, HRT_KERNEL_BUNDLE_BVH, 1, 48, 48},            // BUNDLE_BVH_LDS
-    {true, true, true, true, true, HRT_KERNEL_BUNDLE_BVH_LDS, 8, 28, 36},          // BUNDLE_WQ
-    {true, true, true, false, true, HRT_KERNEL_BUNDLE_BVH_LDS, 8, 28, 36},         // BUNDLE_WQ_L2
+    // persist lists  hier   sky    pairs  fallback                  split_k sec_batch prim_batch
+    {false, false, false, false, false, HRT_KERNEL_AUTO, 1, 48, 48, 1, 1},  // AUTO (plan_trace's ladder picks a row)
+    {false, false, false, false, false, HRT_KERNEL_LITERAL, 1, 48, 48, 1, 1},
+    {false, false, false, false, false, HRT_KERNEL_BRUTE, 1, 48, 48, 1, 1},
+    {false, false, false, false, false, HRT_KERNEL_BRUTE, 1, 48, 48, 1, 1},             // BRUTE_LDS
+    {false, true, false, false, false, HRT_KERNEL_BUNDLE, 1, 48, 48, 1, 1},
+    {false, true, false, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48, 1, 1},
+    {false, true, true, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48, 1, 1},          // BUNDLE_BVH
+    {true, true, false, false, false, HRT_KERNEL_BUNDLE_CULL, 1, 48, 48, 1, 1},          // BUNDLE_CULL_LDS
+    {true, true, true, false, false, HRT_KERNEL_BUNDLE_BVH, 1, 48, 48, 1, 1},            // BUNDLE_BVH_LDS
+    {true, true, true, true, true, HRT_KERNEL_BUNDLE_BVH_LDS, 8, 28, 36, 48, 48},        // BUNDLE_WQ
+    {true, true, true, false, true, HRT_KERNEL_BUNDLE_BVH_LDS, 8, 28, 36, 1, 1},         // BUNDLE_WQ_L2
 };
 inline const KernelTraits& kernel_traits(int k) {
   return kKernelTraits[k >= 0 && k < kNumKernels ? k : HRT_KERNEL_BRUTE];  // (launch_trace's default is trace_brute)
@@ -143,6 +151,7 @@ struct LaunchPlan {
   size_t lds_bytes;        // dynamic LDS
   uint32_t wq_ncap, wq_tcap, wq_lds_nodes;  // pair traversal: the stack capacities and LDS node slots the kernel is told
   uint32_t split_k, sec_batch;              // the row's defaults (sec_batch by the scene's bvh_node_r)
+  uint32_t prim_batch;                      // ... and its primary threshold, chosen the same way
 };
 
 // Kernel k's launch on this scene; false: the scene does not fit it -- the only place that says so.  (The
@@ -150,7 +159,8 @@ struct LaunchPlan {
 inline bool size_kernel(const PlanScene& s, int k, LaunchPlan& plan) {
   const KernelTraits& t = kernel_traits(k);
   plan = LaunchPlan{k, t.persistent || k == HRT_KERNEL_BRUTE_LDS ? 1024u : 256u, t.persistent ? 1u : 0u, 0, 0u, 0u, 0u,
-                    t.split_k, s.bvh_node_r ? t.sec_batch_node_r : t.sec_batch};
+                    t.split_k, s.bvh_node_r ? t.sec_batch_node_r : t.sec_batch,
+                    s.bvh_node_r ? t.prim_batch_node_r : t.prim_batch};
   if (t.hierarchy && (!s.bvh_nodes || s.num_meshes > 64)) return false;
   uint32_t l2[4] = {0, 0, 0, 0};
   switch (k) {
@@ -178,6 +188,8 @@ inline bool size_kernel(const PlanScene& s, int k, LaunchPlan& plan) {
   }
   return plan.lds_bytes <= kMaxLdsScene;
 }
+// A launch's batch threshold (HRT_OPT_SECONDARY_BATCH, HRT_OPT_PRIMARY_BATCH): the request, or the plan's when it is 0
+inline uint32_t batch_threshold(uint32_t request, uint32_t planned) { return request ? request : planned; }
 inline bool kernel_fits(const PlanScene& s, int k) { LaunchPlan plan; return size_kernel(s, k, plan); }
 
 inline LaunchPlan plan_trace(const PlanScene& s, int k) {  // k: the hrt_kernel requested

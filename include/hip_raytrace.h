@@ -59,6 +59,8 @@ extern "C" {
  * HRT_OPT_FOLD_RECORDS, hrt_get_fold_records, hrt_compute_until, HRT_FOLD_RECORD_RING, HRT_RGBA8_FREEZE_FRAME.
  * 6, additive (no bump: nothing existing changed): the present pass -- hrt_present_format,
  * hrt_present_info, hrt_present, hrt_accumulate_present, hrt_present_done, hrt_present_wait.
+ * 6, additive (no bump: nothing existing changed; hrt_get_diagnostics takes the caller's count):
+ * HRT_OPT_PRIMARY_BATCH, HRT_DIAG_PRIMARY_DEFERRED, HRT_DIAG_BATCH_ONLY_ITERS (HRT_NUM_DIAG 32).
  * 6, additive (no bump: hrt_get_diagnostics takes the caller's count): HRT_DIAG_DIR_LANES (HRT_NUM_DIAG 30).
  * 6 (r06): hrt_release_caches; HRT_DEBUG_OPT_STACK_LIMIT.
  * 5 (r05): HRT_DIAG_WQ_STEPS_* / WQ_MEMBERS (HRT_NUM_DIAG 29), HRT_DEBUG_OPT_TIMELINE + hrt_debug_timeline.
@@ -549,6 +551,12 @@ typedef enum hrt_option {
    * is read from global memory; n = min(n, the image's nodes, what fits beside node stacks of 128 pairs),
    * the node stacks then taking what is left.  Results do not depend on it; the other kernels ignore it. */
   HRT_OPT_WQ_LDS_NODES = 21,
+  /* bundle kernels' fused loop: an iteration that runs a bounce batch (HRT_OPT_SECONDARY_BATCH) runs the
+   * ready lanes' primary segments too only once this many lanes are ready for one; an iteration without a
+   * batch runs them whenever a lane is ready.  A lane held back starts its sample with the iteration that
+   * runs it.  1..64 (1 = in every iteration with a ready lane); default 0 = auto: 48 for BUNDLE_WQ, else 1
+   * (hrt_launch_plan.h, DESIGN.md 29: BUNDLE_WQ measured faster still at 40 with HRT_OPT_SECONDARY_BATCH 36, 44 with per-node radii).  Results do not depend on it. */
+  HRT_OPT_PRIMARY_BATCH = 22,
   /* libhip_raytrace_debug.so only (tests): the value-th device allocation of the next hrt_set_scene
    * fails with HRT_ERR_OUT_OF_MEMORY (0 = off) */
   HRT_DEBUG_OPT_FAIL_ALLOC = 1001,
@@ -573,7 +581,7 @@ typedef enum hrt_option {
 
 /* Cull diagnostics of the bundle kernels (HRT_OPT_COUNTERS = 2), summed since the last reset. */
 typedef enum hrt_diag {
-  HRT_DIAG_PRIMARY_ITERS = 0,      /* wave iterations that ran the primary bundle path */
+  HRT_DIAG_PRIMARY_ITERS = 0,      /* wave iterations that ran the primary bundle path (HRT_OPT_PRIMARY_BATCH) */
   HRT_DIAG_PRIMARY_CONSIDERED = 1, /* camera-facing triangles bounded (per wave) */
   HRT_DIAG_PRIMARY_SURVIVORS = 2,  /* ... of which survived the bundle cull */
   HRT_DIAG_BOUNCE_ITERS = 3,       /* wave iterations that ran a bounce batch */
@@ -594,8 +602,9 @@ typedef enum hrt_diag {
   HRT_DIAG_BAND_SCAN_LEN = 18,     /* ... of every bounce lane's list, summed */
   HRT_DIAG_SKY_ITEMS = 19,         /* work items (waves) whose primary list is empty: every segment a miss */
   HRT_DIAG_SKY_CYCLES = 20,        /* ... their shader clocks per wave, summed */
-  HRT_DIAG_PRIMARY_LANES = 21,     /* fused loop: primary lanes of the iterations that ran the primary path */
-  HRT_DIAG_LOOP_ITERS = 22,        /* fused-loop iterations (waves) */
+  HRT_DIAG_PRIMARY_LANES = 21,     /* fused loop: primary lanes of the iterations that ran the primary path
+                                      (each starts its sample there: one per primary segment, whatever the thresholds) */
+  HRT_DIAG_LOOP_ITERS = 22,        /* fused-loop iterations (waves) with a lane not yet done: each ran a phase */
   HRT_DIAG_LIVE_LANES = 23,        /* ... and their lanes not yet done, summed */
   HRT_DIAG_WQ_STEPS_16 = 24,       /* BUNDLE_WQ: pair steps with 1-16 node pairs (waves) */
   HRT_DIAG_WQ_STEPS_32 = 25,       /* ... 17-32 */
@@ -603,7 +612,9 @@ typedef enum hrt_diag {
   HRT_DIAG_WQ_STEPS_64 = 27,       /* ... 49-64 */
   HRT_DIAG_WQ_MEMBERS = 28,        /* ... valid members of the popped node groups, summed (vs 4 slots each) */
   HRT_DIAG_DIR_LANES = 29,         /* bounce-batch lanes whose direction the batch computed (two-phase shading) */
-  HRT_NUM_DIAG = 30
+  HRT_DIAG_PRIMARY_DEFERRED = 30,  /* fused loop: ready lanes of the iterations that ran a bounce batch without the primary path */
+  HRT_DIAG_BATCH_ONLY_ITERS = 31,  /* ... those iterations */
+  HRT_NUM_DIAG = 32
 } hrt_diag;
 
 /* What hrt_set_scene built for BUNDLE_BVH (hrt_get_scene_info). */

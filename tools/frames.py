@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--ncap", type=int, default=0)
     ap.add_argument("--probe", type=int, default=1)
     ap.add_argument("--sec-batch", type=int, default=0)
+    ap.add_argument("--prim-batch", type=int, default=0, help="HRT_OPT_PRIMARY_BATCH (0 auto, 1..64)")
     ap.add_argument("--leaf", type=int, default=0, help="> 0: BVH leaf size (HRT_OPT_BVH_LEAF_SIZE)")
     ap.add_argument("--width", type=int, default=0, help="> 0: BUNDLE_WQ group width (HRT_OPT_BVH_WIDTH)")
     ap.add_argument("--node-r", type=int, default=0, help="HRT_OPT_WQ_NODE_RADIUS (0 auto, 1 scene-wide R, 2 per node)")
@@ -46,6 +47,8 @@ def main():
                                 **({_lib.OPT_BVH_LEAF_SIZE: a.leaf} if a.leaf > 0 else {}),
                                 **({_lib.OPT_BVH_WIDTH: a.width} if a.width > 0 else {})},
                        debug=a.prio == 2)  # heavy tiles only: a libhip_raytrace_debug.so diagnostics mode
+    if a.prim_batch:  # (an older A/B library does not know the key)
+        ctx.set_option(_lib.OPT_PRIMARY_BATCH, a.prim_batch)
     if hasattr(_lib, "OPT_SKY_LANE") and a.sky_lane != -1:
         ctx.set_option(_lib.OPT_SKY_LANE, a.sky_lane)
     pc = case.push(1)
@@ -68,7 +71,7 @@ def main():
         ms.append(round(ctx.stats().total_trace_ms, 3))
     ctx.close()
     print(json.dumps({"batch": a.batch, "scene": a.scene, "variant": a.variant, "partition": a.partition, "coop": a.coop, "factor": a.factor,
-                      "split": a.split, "sec_batch": a.sec_batch, "ncap": a.ncap, "probe": a.probe, "node_r": a.node_r, "leaf": a.leaf, "width": a.width, "prio": a.prio, "ms": ms}))
+                      "split": a.split, "sec_batch": a.sec_batch, "prim_batch": a.prim_batch, "ncap": a.ncap, "probe": a.probe, "node_r": a.node_r, "leaf": a.leaf, "width": a.width, "prio": a.prio, "ms": ms}))
 
 
 if __name__ == "__main__":
