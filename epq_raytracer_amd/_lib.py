@@ -185,6 +185,21 @@ REPROJECT_NAMES = {0: "nearest", 1: "bilinear"}
 REPROJECT_DEFAULTS = (0.02, 0.9)  # HRT_REPROJECT_DEPTH_TOLERANCE / _MIN_NORMAL_DOT (hrt_reproject_defaults)
 HISTORY_MAX = 1 << 24  # HRT_HISTORY_MAX: the largest max_history of hrt_accumulate_history
 
+
+
+class FirstHitsStats(ctypes.Structure):
+    """hrt_first_hits_stats: what the last counted hrt_first_hits call ran (48 bytes)."""
+
+    _fields_ = [("method_ran", c_uint32), ("reserved", c_uint32), ("tiles", c_uint32), ("tiles_listed", c_uint32),
+                ("tiles_empty", c_uint32), ("tiles_fallback", c_uint32), ("scan_rays", c_uint64),
+                ("tri_tests", c_uint64), ("entries_tested", c_uint64)]
+
+
+assert ctypes.sizeof(FirstHitsStats) == 48
+FIRST_HITS_AUTO, FIRST_HITS_TILES, FIRST_HITS_QUERY = 0, 1, 2  # hrt_first_hits_method
+FIRST_HITS_NAMES = {0: "auto", 1: "tiles", 2: "query"}
+FIRST_HITS_COUNT = 1  # HRT_FIRST_HITS_COUNT (flags bit 0)
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -254,6 +269,7 @@ SCENE_INFO_NAMES = ("bvh_nodes", "bvh_prims", "bvh_irregular", "bvh_never", "bvh
 EXPORTED_SYMBOLS = (
     "hrt_abi_version", "hrt_build_id", "hrt_debug_build", "hrt_debug_check_guards", "hrt_create", "hrt_destroy", "hrt_set_scene", "hrt_trace", "hrt_accumulate", "hrt_compute_n",
     "hrt_compute_until", "hrt_get_fold_records", "hrt_intersect", "hrt_intersect_primary", "hrt_occluded", "hrt_radiance",
+    "hrt_first_hits", "hrt_get_first_hits_stats",
     "hrt_read_image", "hrt_load_accumulator", "hrt_get_layout", "hrt_synchronize", "hrt_get_stats", "hrt_reset_stats", "hrt_set_option",
     "hrt_get_diagnostics", "hrt_get_tile_profile", "hrt_get_scene_info", "hrt_generate_rays", "hrt_read_rays",
     "hrt_import_external_memory", "hrt_release_external_memory",
@@ -318,6 +334,8 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_intersect": (c_int32, [P, P, c_uint32, c_uint32, P, POINTER(QueryStats)]),
         "hrt_intersect_primary": (c_int32, [P, POINTER(PushConstants), c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
                                             P, POINTER(QueryStats)]),
+        "hrt_first_hits": (c_int32, [P, POINTER(PushConstants), c_uint32, c_uint32, P]),
+        "hrt_get_first_hits_stats": (c_int32, [P, POINTER(FirstHitsStats)]),
         "hrt_occluded": (c_int32, [P, P, c_uint32, c_uint32, P, POINTER(OcclusionStats)]),
         "hrt_radiance": (c_int32, [P, POINTER(PushConstants), P, c_uint32, c_uint32, P, POINTER(RadianceStats)]),
         "hrt_read_image": (c_int32, [P, c_uint32, c_uint32, P, c_size_t]),

@@ -496,6 +496,10 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->hist_cnt);
   free_dev(ctx, ctx->hist_cnt_next);
   free_dev(ctx, ctx->hist_accum_next);
+  free_dev(ctx, ctx->fh_cam_meta);
+  free_dev(ctx, ctx->fh_cam_tris);
+  free_dev(ctx, ctx->fh_cam_cull);
+  free_dev(ctx, ctx->fh_stats);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -757,6 +761,13 @@ extern "C" hrt_status hrt_set_scene(hrt_context* ctx, const hrt_ray* rays, uint3
   ctx->debug_fail_alloc = 0;
   if (!keep_rays) ctx->n_rays = n_rays;
   for (auto& l : ctx->lane) l.plan_valid = l.cam_ready = l.tl_ready = false;  // costs, camera and tile lists of the old scene
+  // the first-hit pass's camera buffers had the old scene's sizes (nothing in flight reads them: sync_all above)
+  free_dev(ctx, ctx->fh_cam_meta);
+  free_dev(ctx, ctx->fh_cam_tris);
+  free_dev(ctx, ctx->fh_cam_cull);
+  ctx->fh_cam_meta = nullptr;
+  ctx->fh_cam_tris = ctx->fh_cam_cull = nullptr;
+  ctx->fh_ready = false;
   ctx->scene_set = true;
   return HRT_OK;
 }
@@ -1212,6 +1223,103 @@ extern "C" hrt_status hrt_intersect_primary(hrt_context* ctx, const hrt_push_con
   }
   const uint32_t rect[3] = {x0, y0, w};
   return run_query(ctx, p, nullptr, (uint32_t)n, rect, method, hits, stats, "hrt_intersect_primary");
+}
+
+// ---- the first-hit pass ------------------------------------------------------------
+// The whole image's first hits enqueued on ctx->stream with no host wait.  TILES owns a fourth set of camera
+// buffers, so the pass never touches a lane's lists or their keys; QUERY is hrt_intersect_primary's AUTO kernel
+// without the synchronise.
+namespace {
+// AUTO: TILES, which beat QUERY on island and on cave at 1080p from a fresh camera with the five-run ranges
+// apart -- island 0.15 ms against 0.23, cave 0.11 against 0.53 (profiles/first_hits_rate.jsonl)
+constexpr uint32_t kFirstHitsAuto = HRT_FIRST_HITS_TILES;
+}  // namespace
+
+extern "C" hrt_status hrt_first_hits(hrt_context* ctx, const hrt_push_constants* pc, uint32_t method, uint32_t flags,
+                                     hrt_hit* hits) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string("hrt_first_hits: ") + what); };
+  if (!pc) return bad("null push block");
+  if (!hits) return bad("null hits");
+  if (method > HRT_FIRST_HITS_QUERY) return bad("unknown method");
+  if (flags & ~HRT_FIRST_HITS_COUNT) return bad("flag bits other than HRT_FIRST_HITS_COUNT");
+  if (ctx->comm || ctx->part_count > 1)
+    return bad("a context of a row-tile partition or joined to a communicator has no first-hit pass (its consumers, "
+               "hrt_reproject and hrt_denoise, refuse such a context)");
+  hrt_status st = check_dispatch(ctx, pc, "hrt_first_hits");
+  if (st != HRT_OK) return st;
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  if ((uintptr_t)hits % 16 != 0) return bad("hits must be 16-byte aligned");
+  if (!query_direct(ctx, hits) || !query_direct(ctx, hits + (ctx->npix() - 1)))
+    return bad("hits must be width x height records in memory of the context's device");
+  const bool count = (flags & HRT_FIRST_HITS_COUNT) != 0;
+  const uint32_t ran = method == HRT_FIRST_HITS_AUTO ? kFirstHitsAuto : method;
+  const char* who = "hrt_first_hits";
+  if (count) {
+    void* s = ctx->fh_stats;
+    if ((st = ensure_staging(ctx, &s, hrt::kFirstHitsStatWords * sizeof(unsigned long long), who)) != HRT_OK) return st;
+    ctx->fh_stats = static_cast<unsigned long long*>(s);
+  }
+  hrt::TraceParams p = make_params(ctx, pc, 0);
+  query_only(p);
+  const uint32_t n = ctx->width * ctx->height;  // (= the scene's ray count, a uint32)
+  if (ran == HRT_FIRST_HITS_TILES) {
+    const hrt::SceneBufs& sb = ctx->scene;
+    void *meta = ctx->fh_cam_meta, *tris = ctx->fh_cam_tris, *cull = ctx->fh_cam_cull;
+    // (the lanes' sizes: build_scene)
+    if ((st = ensure_staging(ctx, &meta, (size_t)(sb.n_meshes ? 2 * sb.n_meshes : 2) * 4, who)) != HRT_OK) return st;
+    ctx->fh_cam_meta = static_cast<uint32_t*>(meta);
+    if ((st = ensure_staging(ctx, &tris, (size_t)(sb.cam_capacity ? sb.cam_capacity : 1) * 64, who)) != HRT_OK) return st;
+    ctx->fh_cam_tris = static_cast<float4*>(tris);
+    if ((st = ensure_staging(ctx, &cull, (size_t)(sb.cam_capacity ? sb.cam_capacity : 1) * 80, who)) != HRT_OK) return st;
+    ctx->fh_cam_cull = static_cast<float4*>(cull);
+    p.cam_start = ctx->fh_cam_meta;
+    p.cam_count = ctx->fh_cam_meta + sb.n_meshes;
+    p.cam_tris = ctx->fh_cam_tris;
+    p.cam_cull = ctx->fh_cam_cull;
+    p.tl_cache = nullptr;
+    p.pc.jitter_size = 0.0f;  // the lists' reach: the un-jittered centre is each pixel's whole box
+    uint32_t key[4];
+    std::memcpy(key, pc->cam_pos, 12);
+    key[3] = (uint32_t)pc->num_meshes;
+    const bool ready = ctx->fh_ready && std::memcmp(key, ctx->fh_key, sizeof key) == 0;
+    if (count) HRT_HIP(ctx, hipMemsetAsync(ctx->fh_stats, 0, hrt::kFirstHitsStatWords * sizeof(unsigned long long), ctx->stream));
+    ctx->fh_ready = false;  // until a launch has rebuilt them
+    const hrt::FirstHitsArgs a{reinterpret_cast<float4*>(hits), count ? ctx->fh_stats : nullptr};
+    HRT_HIP(ctx, hrt::launch_first_hits_tiles(p, a, ready, ctx->stream));
+    ctx->fh_ready = true;
+    std::memcpy(ctx->fh_key, key, sizeof key);
+  } else {
+    const hrt::QueryPlan plan = hrt::plan_query(hrt::plan_scene(p), HRT_QUERY_AUTO);
+    if (count) HRT_HIP(ctx, hipMemsetAsync(ctx->fh_stats, 0, hrt::kFirstHitsStatWords * sizeof(unsigned long long), ctx->stream));
+    for (uint32_t at = 0; at < n; at += std::min(kQueryLaunch, n - at)) {
+      hrt::QueryArgs q{};
+      q.hits = reinterpret_cast<float4*>(hits + at);
+      q.stats = count ? ctx->fh_stats : nullptr;  // words 0 and 1 are hrt_query_stats' two
+      q.n = std::min(kQueryLaunch, n - at);
+      q.first = at;
+      q.w = ctx->width;
+      HRT_HIP(ctx, hrt::launch_query(p, q, plan, true, ctx->stream));
+    }
+  }
+  if (count) {
+    ctx->fh_counted_method = ran;
+    ctx->fh_counted_tiles = ran == HRT_FIRST_HITS_TILES ? (uint32_t)(((ctx->width + 7) / 8) * ((ctx->height + 7) / 8)) : 0u;
+  }
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_get_first_hits_stats(hrt_context* ctx, hrt_first_hits_stats* out) {
+  if (!ctx || !out) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  unsigned long long w[hrt::kFirstHitsStatWords] = {};
+  if (ctx->fh_counted_method != 0)
+    HRT_HIP(ctx, hipMemcpyAsync(w, ctx->fh_stats, sizeof w, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = hrt_first_hits_stats{ctx->fh_counted_method, 0u, ctx->fh_counted_tiles, (uint32_t)w[2], (uint32_t)w[3],
+                              (uint32_t)w[4], w[0], w[1], w[5]};
+  return HRT_OK;
 }
 
 // Any hit, one bit per ray.  A chunk of staged rays or bits is kQueryChunk rays -- a multiple

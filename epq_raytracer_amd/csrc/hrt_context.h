@@ -239,6 +239,17 @@ struct hrt_context {
   uint32_t* hist_cnt = nullptr;
   uint32_t* hist_cnt_next = nullptr;
   void* hist_accum_next = nullptr;
+  // The first-hit pass (hrt_first_hits): its own camera buffers (a fourth set beside the lanes', the scene's
+  // sizes), allocated by the first TILES call and dropped by hrt_set_scene; fh_key = the camera position's bits
+  // and num_meshes the records were built for (fh_ready: by a launch already enqueued on `stream`); the device
+  // record a counted call adds to (hrt::kFirstHitsStatWords words) and what the host knows of that call
+  uint32_t* fh_cam_meta = nullptr;
+  float4* fh_cam_tris = nullptr;
+  float4* fh_cam_cull = nullptr;
+  bool fh_ready = false;
+  uint32_t fh_key[4] = {};
+  unsigned long long* fh_stats = nullptr;
+  uint32_t fh_counted_method = 0, fh_counted_tiles = 0;  // method 0: no counted call yet
   hrt::Comm* comm = nullptr;  // hrt_comm_init / hrt_comm_init_all
   uint32_t comm_timeout_ms = 120000;  // HRT_OPT_COMM_TIMEOUT_MS (0: wait forever)
 

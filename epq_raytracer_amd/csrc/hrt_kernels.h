@@ -178,5 +178,19 @@ struct RadianceArgs {
   uint32_t n;                 // queries of this launch
 };
 hipError_t launch_radiance(const TraceParams& p, const RadianceArgs& q, const QueryPlan& plan, hipStream_t stream);
+// The first-hit pass (hrt_first_hits TILES): the un-jittered primary ray of every pixel of the
+// p.pc.width x p.pc.height image, one wave per 8x8 tile from the tile's primary triangle list; pixel (x, y)'s
+// hit goes to hits[2 (x + y width)], hits[2 (x + y width) + 1].  p.cam_start / cam_count / cam_tris / cam_cull
+// are the pass's own camera buffers, p.pc.jitter_size the reach the lists are built for (0).
+struct FirstHitsArgs {
+  float4* hits;
+  // [0] rays answered by the literal scan, [1] triangle tests, [2] tiles answered from their list, [3] of those
+  // the empty ones of a scene without spheres, [4] fallback tiles, [5] list entries that reached the exact test;
+  // nullptr: the kernel without counting code
+  unsigned long long* stats;
+};
+constexpr uint32_t kFirstHitsStatWords = 6;
+// camera_lists into p's camera buffers unless lists_ready, then first_hits_tiles
+hipError_t launch_first_hits_tiles(const TraceParams& p, const FirstHitsArgs& a, bool lists_ready, hipStream_t stream);
 
 }  // namespace hrt

@@ -4454,4 +4454,66 @@ hipError_t launch_radiance(const TraceParams& p0, const RadianceArgs& q, const Q
   return hipGetLastError();
 }
 
+// ---- the first-hit pass: every pixel's un-jittered primary ray from the tile lists -----------
+// hrt_intersect_primary's bytes for the whole image (S11), answered the way the frame kernels answer primary
+// segments: one wave per 8x8 tile (tile_lists' lane-to-pixel map) builds the tile's list and tests only the
+// listed records.  The lists are built for jitter reach 0 (the host passes pc.jitter_size = 0): the direction
+// here is normalize(M c) of the pixel's own centre c, so each pixel's box is that one point (the soundness
+// paragraph above refine_tile_list covers the S4 rounding).  A tile whose list is not usable -- build_tile_list
+// says not ok (more than 32 meshes, more than 64 survivors, a cap wider than c_lo > 0.5, a corner that is not
+// finite), or the scene has more meshes than world_hit_tile's octant word holds (8) -- takes world_hit_bundle,
+// the per-wave cull of the same camera records; irregular lanes (query_ray's rule) take the literal scan as in
+// query_finish.  No LDS, no persistent scheduling.  Count: the statistics of FirstHitsArgs (else no such code).
+template <bool Count>
+__global__ __launch_bounds__(256) void first_hits_tiles(TraceParams P, FirstHitsArgs A) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t W = P.pc.width, H = P.pc.height;
+  const uint32_t tiles_x = (W + 7) / 8, tiles = tiles_x * ((H + 7) / 8);
+  const uint32_t tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (tile >= tiles) return;  // wave-uniform
+  const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const uint32_t x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+  const bool active = x < W && y < H;
+  // the pass as a primary query of the whole image: ray i = pixel i (an inactive lane: past the end)
+  const QueryArgs Q{nullptr, A.hits, Count ? A.stats : nullptr, W * H, 0u, 0u, 0u, W};
+  const uint32_t i = active ? x + y * W : Q.n;
+  f3 centre = mk(0.0f, 0.0f, 0.0f);
+  if (active) {
+    const float4 rc = P.rays[i];
+    centre = mk(rc.x, rc.y, rc.z);
+  }
+  const QueryRay r = query_ray<true>(P, Q, i);
+  const bool prim = r.live && r.finite;
+  const f3 o = prim ? r.o : mk(0.0f, 0.0f, 0.0f), d = prim ? r.d : mk(0.0f, 0.0f, 1.0f);
+  const TileList tl = build_tile_list(P, active, centre, nullptr);
+  const bool listed = tl.ok && P.pc.num_meshes <= 8;
+  const Scene sc{P.rays, P.spheres, P.tris, P.meshes, P.tri_nhat};
+  uint32_t tests = 0, tested = 0;
+  Closest c{kFltMax, 0, 0u, 0u};
+  if (listed) {
+    tested = world_hit_tile(sc, P, tl, prim, o, d, tests, c);
+  } else if (__any(prim)) {
+    Diag dg;
+    world_hit_bundle<false>(sc, P, prim, o, d, tests, c, dg);
+  }
+  query_finish(sc, P, r, prim, c, tests);
+  query_store(sc, Q, i, r, c, tests);
+  if (Count && lane == 0) {
+    atomicAdd(&A.stats[listed ? 2 : 4], 1ull);
+    if (listed && tl.n == 0 && P.pc.num_spheres == 0) atomicAdd(&A.stats[3], 1ull);
+    if (tested) atomicAdd(&A.stats[5], (unsigned long long)tested);
+  }
+}
+
+hipError_t launch_first_hits_tiles(const TraceParams& p, const FirstHitsArgs& a, bool lists_ready, hipStream_t stream) {
+  const uint32_t tiles = ((p.pc.width + 7) / 8) * ((p.pc.height + 7) / 8);
+  if (tiles == 0) return hipSuccess;
+  if (p.pc.num_meshes > 0 && !lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
+  if (a.stats)
+    first_hits_tiles<true><<<(tiles + 3) / 4, 256, 0, stream>>>(p, a);
+  else
+    first_hits_tiles<false><<<(tiles + 3) / 4, 256, 0, stream>>>(p, a);
+  return hipGetLastError();
+}
+
 }  // namespace hrt

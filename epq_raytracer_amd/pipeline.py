@@ -464,6 +464,24 @@ class HrtContext:
                     "hrt_intersect_primary")
         return st if with_stats else None
 
+    # ---- the first-hit pass (hrt_first_hits) ----
+
+    def first_hits(self, pc: _lib.PushConstants, hits_device: int, method: int = _lib.FIRST_HITS_AUTO,
+                   count: bool = False) -> None:
+        """hrt_first_hits: the whole image's first hits -- ``intersect_primary_into``'s bytes -- into W x H
+        hrt_hit records at hits_device, a 16-byte aligned pointer into the context's device.  Only enqueues, on
+        the context's stream: ``reproject`` / ``denoise`` calls that follow read the result; keep the buffer
+        until the pass has run.  count=True has the device count what ``first_hits_stats`` returns."""
+        self._check(self.lib.hrt_first_hits(self.handle, ctypes.byref(pc), int(method),
+                                            _lib.FIRST_HITS_COUNT if count else 0, ctypes.c_void_p(hits_device)),
+                    "hrt_first_hits")
+
+    def first_hits_stats(self) -> _lib.FirstHitsStats:
+        """hrt_get_first_hits_stats: the record of the last ``first_hits(..., count=True)``.  Blocking."""
+        st = _lib.FirstHitsStats()
+        self._check(self.lib.hrt_get_first_hits_stats(self.handle, ctypes.byref(st)), "hrt_get_first_hits_stats")
+        return st
+
     # ---- occlusion queries (hrt_occluded) ----
 
     def occluded_into(self, rays_ptr: int, n: int, bits_ptr: int, method: int = _lib.QUERY_AUTO,
@@ -722,6 +740,13 @@ class RayTracePipeline:
         device memory of the context): the guide of ``DiffusePipeline.denoised`` /
         ``RenderPassOverFrame.render_denoised``, kept on the device."""
         self.ctx.intersect_primary_into(self.push_constants(camera, 0, False), ptr)
+
+    def first_hits_async(self, camera: Camera, hits_device: int, method: int = _lib.FIRST_HITS_AUTO,
+                         count: bool = False) -> None:
+        """``first_hits_into`` for device memory without the host wait (hrt_first_hits): enqueued on the
+        context's stream, so the ``reproject`` / ``denoised`` calls that follow read it; keep the buffer until
+        the pass has run.  count=True: ``self.ctx.first_hits_stats()`` afterwards."""
+        self.ctx.first_hits(self.push_constants(camera, 0, False), hits_device, method, count)
 
     def pick(self, camera: Camera, x: int, y: int):
         """What lies under pixel (x, y) of the view: one hit record (numpy.void of _lib.HIT_DTYPE).  x, y are

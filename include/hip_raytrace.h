@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): temporal history -- hrt_view, hrt_reproject_filter,
+/* 6, additive (no bump: nothing existing changed): the first-hit pass -- hrt_first_hits_method,
+ * HRT_FIRST_HITS_COUNT, hrt_first_hits_stats, hrt_first_hits, hrt_get_first_hits_stats.
+ * 6, additive (no bump: nothing existing changed): temporal history -- hrt_view, hrt_reproject_filter,
  * hrt_reproject_info, hrt_reproject_defaults, hrt_reproject, hrt_accumulate_history, hrt_fill_history,
  * hrt_read_history.
  * 6, additive (no bump: nothing existing changed): the denoise pass -- hrt_denoise_method, hrt_denoise_info,
@@ -342,6 +344,26 @@ typedef struct hrt_reproject_info { /* 32 bytes */
   uint32_t reserved[4];  /* ignored */
 } hrt_reproject_info;
 
+/* ---- the first-hit pass (hrt_first_hits) ---- */
+typedef enum hrt_first_hits_method {
+  HRT_FIRST_HITS_AUTO = 0,  /* TILES: it measured faster on island and on cave */
+  HRT_FIRST_HITS_TILES = 1, /* first_hits_tiles: one wave per 8x8 tile, the tile's primary triangle list */
+  HRT_FIRST_HITS_QUERY = 2  /* the primary query kernel hrt_intersect_primary's AUTO runs, not waited for */
+} hrt_first_hits_method;
+#define HRT_FIRST_HITS_COUNT 1u /* hrt_first_hits flags bit 0: count on the device (hrt_get_first_hits_stats) */
+
+typedef struct hrt_first_hits_stats { /* 48 bytes: the last call that had HRT_FIRST_HITS_COUNT */
+  uint32_t method_ran;      /* hrt_first_hits_method that ran (AUTO resolved) */
+  uint32_t reserved;        /* 0 */
+  uint32_t tiles;           /* 8x8 tiles of the image (TILES; 0 for QUERY, as the three below and entries_tested) */
+  uint32_t tiles_listed;    /* tiles answered from their list */
+  uint32_t tiles_empty;     /* listed tiles with no entry and no spheres: stored as misses, no test */
+  uint32_t tiles_fallback;  /* tiles whose list was not usable: answered by the per-wave bundle cull */
+  uint64_t scan_rays;       /* as hrt_query_stats */
+  uint64_t tri_tests;       /* as hrt_query_stats */
+  uint64_t entries_tested;  /* list entries that reached the exact test, summed over waves */
+} hrt_first_hits_stats;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -408,6 +430,13 @@ HRT_STATIC_ASSERT(sizeof(hrt_reproject_info) == 32 && offsetof(hrt_reproject_inf
                       offsetof(hrt_reproject_info, depth_tolerance) == 8 &&
                       offsetof(hrt_reproject_info, min_normal_dot) == 12 && offsetof(hrt_reproject_info, reserved) == 16,
                   "hrt_reproject_info");
+HRT_STATIC_ASSERT(sizeof(hrt_first_hits_stats) == 48 && offsetof(hrt_first_hits_stats, reserved) == 4 &&
+                      offsetof(hrt_first_hits_stats, tiles) == 8 && offsetof(hrt_first_hits_stats, tiles_listed) == 12 &&
+                      offsetof(hrt_first_hits_stats, tiles_empty) == 16 &&
+                      offsetof(hrt_first_hits_stats, tiles_fallback) == 20 &&
+                      offsetof(hrt_first_hits_stats, scan_rays) == 24 && offsetof(hrt_first_hits_stats, tri_tests) == 32 &&
+                      offsetof(hrt_first_hits_stats, entries_tested) == 40,
+                  "hrt_first_hits_stats");
 
 typedef struct hrt_context hrt_context;
 
@@ -973,6 +1002,27 @@ hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count);
 /* BLOCKING: the count image, height x width uint32 in trace-image row order, to host or device memory at dst
  * (bytes >= height * width * 4). */
 hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t bytes);
+
+/* ---- the first-hit pass ----
+ * The whole image's first hits, NON-blocking: enqueued on the context's stream after the work issued so far, so
+ * hrt_reproject / hrt_denoise* calls that follow read its result with nothing more to do.  hits: width x height
+ * records in memory of the context's device, 16-byte aligned, row-major in trace-image row order; keep the
+ * buffer until the pass has run.  The bytes are those hrt_intersect_primary(ctx, pc, 0, 0, width, height, any
+ * method, hits, ...) writes (S11: the un-jittered direction, pc's counts, the literal scan for irregular rays),
+ * whatever the method here.  The pass touches no trace lane, image, hrt_stats, counter, fold record or ticket; its
+ * camera lists are a set of its own (allocated by the first TILES call, dropped by hrt_set_scene), keyed so that a
+ * second call from the same camera and counts rebuilds nothing.
+ *
+ * flags: HRT_FIRST_HITS_COUNT zeroes a context-owned record on the stream and has the kernel add to it; without
+ * it no counting code runs.  hrt_get_first_hits_stats (BLOCKING: it synchronizes the stream) returns the last
+ * counted call's record, zeros when there was none.
+ *
+ * HRT_ERR_NO_SCENE without a scene.  Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL
+ * argument; an unknown method; flag bits other than bit 0; hits that is not memory of the context's device or
+ * not 16-byte aligned; a push block whose size or counts the context does not hold; and a context of a row-tile
+ * partition or one joined to any communicator (the rule of the pass's consumers). */
+hrt_status hrt_first_hits(hrt_context* ctx, const hrt_push_constants* pc, uint32_t method, uint32_t flags, hrt_hit* hits);
+hrt_status hrt_get_first_hits_stats(hrt_context* ctx, hrt_first_hits_stats* out);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

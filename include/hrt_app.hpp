@@ -283,6 +283,12 @@ class Context {
     const hrt_reproject_info ri = info ? *info : reproject_defaults();
     check(hrt_reproject(get(), &ri, &prev, prev_hits, &cur, cur_hits), "hrt_reproject", get());
   }
+  // the record of the last counted first-hit pass (hrt_get_first_hits_stats).  Blocking.
+  hrt_first_hits_stats first_hits_stats() {
+    hrt_first_hits_stats st{};
+    check(hrt_get_first_hits_stats(get(), &st), "hrt_get_first_hits_stats", get());
+    return st;
+  }
   void accumulate_history(uint32_t max_history) {
     check(hrt_accumulate_history(get(), max_history), "hrt_accumulate_history", get());
   }
@@ -469,6 +475,15 @@ class RayTracePipeline {  // src/raytrace_pipeline.rs:31-266
   void first_hits_into(const Camera& camera, hrt_hit* hits, uint32_t method = HRT_QUERY_AUTO) const {
     const hrt_push_constants pc = push_constants(camera, 0u, false);
     check(hrt_intersect_primary(ctx_->get(), &pc, 0, 0, size_[0], size_[1], method, hits, nullptr), "hrt_intersect_primary",
+          ctx_->get());
+  }
+  // first_hits_into for device memory without the host wait (hrt_first_hits; not a reference feature): enqueued
+  // on the context's stream, so the Context::reproject / denoised calls that follow read it; keep the buffer
+  // until the pass has run.  count: Context::first_hits_stats() afterwards.
+  void first_hits_enqueue(const Camera& camera, hrt_hit* hits_device, uint32_t method = HRT_FIRST_HITS_AUTO,
+                          bool count = false) const {
+    const hrt_push_constants pc = push_constants(camera, 0u, false);
+    check(hrt_first_hits(ctx_->get(), &pc, method, count ? HRT_FIRST_HITS_COUNT : 0u, hits_device), "hrt_first_hits",
           ctx_->get());
   }
   // What lies under pixel (x, y) of the view (trace-image coordinates: row height - 1 - y of a presented target).

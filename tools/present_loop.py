@@ -26,7 +26,9 @@ and writes profiles/present_loop_denoise.jsonl with the ratio e / c (single cont
      (max_history 32) and hrt_denoise_present guided by the new first hits
   g  f with the first hits taken on a second context of the same scene, so that the blocking query does not
      wait for the rendering context's stream
-and writes profiles/present_loop_history.jsonl with f / e, g / e and f - g.
+  h  f with hrt_first_hits (AUTO) into two alternating device buffers in place of the blocking call: every stage
+     of the frame is enqueued, the host waits for tickets only
+and writes profiles/present_loop_history.jsonl with f / e, g / e, h / e, f - g and f - h.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -43,7 +45,7 @@ sys.path.insert(0, ROOT)
 
 VARIANTS = ("a", "b", "c", "d")
 DENOISE_VARIANTS = ("c", "e")
-MOVING_VARIANTS = ("e", "f", "g")
+MOVING_VARIANTS = ("e", "f", "g", "h")
 MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
@@ -81,13 +83,14 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
-    moving = variant in ("f", "g")
+    moving = variant in ("f", "g", "h")
     if moving:
         import numpy as np
 
         # first hits of the previous and the current view: LAG + 2 buffers, so that one the enqueued passes of
         # the last LAG frames still read is never overwritten
-        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(LAG + 2)]
+        # (h: two -- its passes are ordered on the stream behind the readers of the buffer they overwrite)
+        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2 if variant == "h" else LAG + 2)]
         guide_ctx, guide_rt = ctx, raytraces[0]
         if variant == "g":
             guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
@@ -111,7 +114,10 @@ def child(variant: str, parts: int = 1) -> dict:
         cam = camera_at(frame)
         view = E.View(cam, SIZE, settings)
         prev_hits, cur_hits = guides[(frame - 1) % len(guides)], guides[frame % len(guides)]
-        guide_rt.first_hits_into(cam, cur_hits.data_ptr())  # blocking
+        if variant == "h":
+            guide_rt.first_hits_async(cam, cur_hits.data_ptr())
+        else:
+            guide_rt.first_hits_into(cam, cur_hits.data_ptr())  # blocking
         raytraces[0].compute(cam, frame)
         ctx.reproject(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
         diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY)
@@ -167,15 +173,15 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g"), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
     ap.add_argument("--denoise", action="store_true",
                     help="variants c and e (hrt_denoise_present in place of hrt_present) only, taking turns")
     ap.add_argument("--moving", action="store_true",
-                    help="variants e, f (the temporal pipeline with a moving camera) and g (f with the first hits "
-                         "taken on a second context) only, taking turns")
+                    help="variants e, f (the temporal pipeline with a moving camera), g (f with the first hits "
+                         "taken on a second context) and h (f with hrt_first_hits, nothing blocking) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -220,7 +226,9 @@ def main() -> int:
     if a.moving:
         summary.update(f_over_e=round(med["f"] / med["e"], 4), f_minus_e_ms=round(med["f"] - med["e"], 4),
                        g_over_e=round(med["g"] / med["e"], 4), g_minus_e_ms=round(med["g"] - med["e"], 4),
-                       f_minus_g_ms=round(med["f"] - med["g"], 4))
+                       f_minus_g_ms=round(med["f"] - med["g"], 4),
+                       h_over_e=round(med["h"] / med["e"], 4), h_minus_e_ms=round(med["h"] - med["e"], 4),
+                       f_minus_h_ms=round(med["f"] - med["h"], 4), g_minus_h_ms=round(med["g"] - med["h"], 4))
     elif a.denoise:
         summary.update(e_over_c=round(med["e"] / med["c"], 4), e_minus_c_ms=round(med["e"] - med["c"], 4))
     else:
