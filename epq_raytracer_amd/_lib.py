@@ -186,6 +186,20 @@ REPROJECT_DEFAULTS = (0.02, 0.9)  # HRT_REPROJECT_DEPTH_TOLERANCE / _MIN_NORMAL_
 HISTORY_MAX = 1 << 24  # HRT_HISTORY_MAX: the largest max_history of hrt_accumulate_history
 
 
+class VarianceInfo(ctypes.Structure):
+    """hrt_variance_info: one variance-guided denoise pass (32 bytes)."""
+
+    _fields_ = [("iterations", c_uint32), ("method", c_uint32), ("flags", c_uint32), ("min_history", c_uint32),
+                ("sigma_variance", c_float), ("variance_floor", c_float), ("sigma_normal", c_float),
+                ("sigma_depth", c_float)]
+
+
+assert ctypes.sizeof(VarianceInfo) == 32
+VARIANCE_AUTO, VARIANCE_DIRECT, VARIANCE_TILED = 0, 1, 2  # hrt_variance_method
+VARIANCE_NAMES = {0: "auto", 1: "direct", 2: "tiled"}
+VARIANCE_SIGMA, VARIANCE_FLOOR, VARIANCE_MIN_HISTORY = 4.0, 1e-10, 4  # HRT_VARIANCE_SIGMA / _FLOOR / _MIN_HISTORY
+VARIANCE_MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16 (0 iterations: the source and the variance estimate)
+
 
 class FirstHitsStats(ctypes.Structure):
     """hrt_first_hits_stats: what the last counted hrt_first_hits call ran (48 bytes)."""
@@ -275,6 +289,8 @@ EXPORTED_SYMBOLS = (
     "hrt_import_external_memory", "hrt_release_external_memory",
     "hrt_denoise_defaults", "hrt_denoise", "hrt_denoise_present",
     "hrt_reproject_defaults", "hrt_reproject", "hrt_accumulate_history", "hrt_fill_history", "hrt_read_history",
+    "hrt_variance_defaults", "hrt_accumulate_history_moments", "hrt_reproject_moments", "hrt_fill_moments",
+    "hrt_read_moments", "hrt_denoise_variance", "hrt_denoise_variance_present",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -362,6 +378,14 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_accumulate_history": (c_int32, [P, c_uint32]),
         "hrt_fill_history": (c_int32, [P, c_uint32]),
         "hrt_read_history": (c_int32, [P, P, c_size_t]),
+        "hrt_variance_defaults": (None, [POINTER(VarianceInfo)]),
+        "hrt_accumulate_history_moments": (c_int32, [P, c_uint32]),
+        "hrt_reproject_moments": (c_int32, [P, POINTER(ReprojectInfo), POINTER(View), P, POINTER(View), P]),
+        "hrt_fill_moments": (c_int32, [P, c_float, c_float]),
+        "hrt_read_moments": (c_int32, [P, P, c_size_t]),
+        "hrt_denoise_variance": (c_int32, [P, POINTER(VarianceInfo), P, c_uint32, P, c_size_t, P, c_size_t]),
+        "hrt_denoise_variance_present": (c_int32, [P, POINTER(VarianceInfo), P, POINTER(PresentInfo), P, c_uint64,
+                                                   POINTER(c_uint64)]),
         "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
         "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),

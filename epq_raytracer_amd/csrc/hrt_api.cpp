@@ -25,6 +25,7 @@
 #include "hrt_context.h"
 #include "hrt_denoise.h"
 #include "hrt_history.h"
+#include "hrt_variance.h"
 #include "hrt_host.h"
 #include "hrt_image.h"
 #include "hrt_kernels.h"
@@ -496,6 +497,9 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->hist_cnt);
   free_dev(ctx, ctx->hist_cnt_next);
   free_dev(ctx, ctx->hist_accum_next);
+  free_dev(ctx, ctx->hist_mom);
+  free_dev(ctx, ctx->hist_mom_next);
+  free_dev(ctx, ctx->var_stage);
   free_dev(ctx, ctx->fh_cam_meta);
   free_dev(ctx, ctx->fh_cam_tris);
   free_dev(ctx, ctx->fh_cam_cull);
@@ -2029,6 +2033,18 @@ hrt_status begin_history(hrt_context* ctx, const char* who) {
   return HRT_OK;
 }
 
+// The moments image of the variance-guided denoise (S16): allocated and zeroed (on ctx->stream) by the first call
+// that needs it, after begin_history's refusals.
+hrt_status begin_moments(hrt_context* ctx, const char* who) {
+  if (ctx->hist_mom) return HRT_OK;
+  void* p = nullptr;
+  hrt_status st = ensure_staging(ctx, &p, ctx->npix() * 8, who);
+  if (st != HRT_OK) return st;
+  ctx->hist_mom = static_cast<float*>(p);
+  HRT_HIP(ctx, hipMemsetAsync(ctx->hist_mom, 0, ctx->npix() * 8, ctx->stream));
+  return HRT_OK;
+}
+
 bool hits_on_device(hrt_context* ctx, const hrt_hit* hits) {
   return query_direct(ctx, hits) && query_direct(ctx, hits + (ctx->npix() - 1));
 }
@@ -2041,10 +2057,14 @@ extern "C" void hrt_reproject_defaults(hrt_reproject_info* info) {
                              {0u, 0u, 0u, 0u}};
 }
 
-extern "C" hrt_status hrt_reproject(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
-                                    const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
+namespace {
+
+// hrt_reproject (moments false) and hrt_reproject_moments: the same checks, order and swaps; with moments the pass
+// also writes M' into hist_mom_next, swapped with hist_mom like the other two.
+hrt_status reproject_call(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev, const hrt_hit* prev_hits,
+                          const hrt_view* cur, const hrt_hit* cur_hits, bool moments, const char* who) {
   if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
-  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string("hrt_reproject: ") + what); };
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
   if (!info) return bad("null info");
   if (!prev || !cur) return bad("null view");
   if (!prev_hits || !cur_hits) return bad("null hit array");
@@ -2053,46 +2073,73 @@ extern "C" hrt_status hrt_reproject(hrt_context* ctx, const hrt_reproject_info* 
   if (!(std::isfinite(info->depth_tolerance) && info->depth_tolerance >= 0.0f))
     return bad("depth_tolerance must be finite and not negative");
   if (!std::isfinite(info->min_normal_dot)) return bad("min_normal_dot must be finite");
-  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, "hrt_reproject");  // (the rejection)
+  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, who);  // (the rejection)
   hrt_status st = bind(ctx);
   if (st != HRT_OK) return st;
   if ((uintptr_t)prev_hits % 16 != 0 || (uintptr_t)cur_hits % 16 != 0) return bad("the hit arrays must be 16-byte aligned");
   if (!hits_on_device(ctx, prev_hits) || !hits_on_device(ctx, cur_hits))
     return bad("the hit arrays must be width x height records in memory of the context's device");
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
-  if ((st = begin_history(ctx, "hrt_reproject")) != HRT_OK) return st;
+  if ((st = begin_history(ctx, who)) != HRT_OK) return st;
   const size_t np = ctx->npix();
   void* p = ctx->hist_cnt_next;
-  if ((st = ensure_staging(ctx, &p, np * 4, "hrt_reproject")) != HRT_OK) return st;
+  if ((st = ensure_staging(ctx, &p, np * 4, who)) != HRT_OK) return st;
   ctx->hist_cnt_next = static_cast<uint32_t*>(p);
-  if ((st = ensure_staging(ctx, &ctx->hist_accum_next, np * ctx->px_bytes(), "hrt_reproject")) != HRT_OK) return st;
+  if ((st = ensure_staging(ctx, &ctx->hist_accum_next, np * ctx->px_bytes(), who)) != HRT_OK) return st;
+  if (moments) {
+    if ((st = begin_moments(ctx, who)) != HRT_OK) return st;
+    p = ctx->hist_mom_next;
+    if ((st = ensure_staging(ctx, &p, np * 8, who)) != HRT_OK) return st;
+    ctx->hist_mom_next = static_cast<float*>(p);
+  }
   const hrt::ReprojectPass pass{ctx->accum, ctx->hist_cnt, ctx->hist_accum_next, ctx->hist_cnt_next, prev_hits, cur_hits,
                                 *prev, *cur, ctx->f32(), info->filter, ctx->width, ctx->local_rows,
                                 info->depth_tolerance, info->min_normal_dot};
-  HRT_HIP(ctx, hrt::launch_reproject(pass, ctx->stream));
+  if (moments)
+    HRT_HIP(ctx, hrt::launch_reproject_moments(pass, ctx->hist_mom, ctx->hist_mom_next, ctx->stream));
+  else
+    HRT_HIP(ctx, hrt::launch_reproject(pass, ctx->stream));
   // A' and N' become the context's accumulator and count image; the old ones are the next pass's targets
   std::swap(ctx->accum, ctx->hist_accum_next);
   std::swap(ctx->hist_cnt, ctx->hist_cnt_next);
+  if (moments) std::swap(ctx->hist_mom, ctx->hist_mom_next);
   return HRT_OK;
 }
 
-extern "C" hrt_status hrt_accumulate_history(hrt_context* ctx, uint32_t max_history) {
+// hrt_accumulate_history (moments false) and hrt_accumulate_history_moments.
+hrt_status accumulate_history_call(hrt_context* ctx, uint32_t max_history, bool moments, const char* who) {
   if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
   if (max_history == 0 || max_history > hrt::kHistoryMax)
-    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_accumulate_history: max_history must be 1..2^24");
-  hrt_status st = begin_history(ctx, "hrt_accumulate_history");
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": max_history must be 1..2^24");
+  hrt_status st = begin_history(ctx, who);
   if (st != HRT_OK) return st;
+  if (moments && (st = begin_moments(ctx, who)) != HRT_OK) return st;
   const int l = ctx->cur_lane;  // next_image = the most recent trace
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // frames fold in call order
   if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
-  HRT_HIP(ctx, hrt::launch_fold_history(ctx->accum, hrt::trace_image(ctx), ctx->hist_cnt, ctx->f32(), ctx->npix(),
-                                        max_history, ctx->stream));
+  if (moments)
+    HRT_HIP(ctx, hrt::launch_fold_history_moments(ctx->accum, hrt::trace_image(ctx), ctx->hist_cnt, ctx->hist_mom, ctx->f32(),
+                                                  ctx->npix(), max_history, ctx->stream));
+  else
+    HRT_HIP(ctx, hrt::launch_fold_history(ctx->accum, hrt::trace_image(ctx), ctx->hist_cnt, ctx->f32(), ctx->npix(),
+                                          max_history, ctx->stream));
   if (ctx->cur_slot >= 0) {  // a slot of the deferred combiner's ring: its next trace waits for this fold
     HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
     ctx->fold_set = true;
   }
   ctx->accumulates++;
   return hrt::release_lane(ctx, l);
+}
+
+}  // namespace
+
+extern "C" hrt_status hrt_reproject(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
+                                    const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
+  return reproject_call(ctx, info, prev, prev_hits, cur, cur_hits, false, "hrt_reproject");
+}
+
+extern "C" hrt_status hrt_accumulate_history(hrt_context* ctx, uint32_t max_history) {
+  return accumulate_history_call(ctx, max_history, false, "hrt_accumulate_history");
 }
 
 extern "C" hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count) {
@@ -2114,6 +2161,169 @@ extern "C" hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t b
   HRT_HIP(ctx, hipMemcpyAsync(dst, ctx->hist_cnt, need, hipMemcpyDefault, ctx->stream));
   HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return HRT_OK;
+}
+
+// ---- the variance-guided denoise (kernels in hrt_variance.hip and hrt_history.hip) -----
+extern "C" hrt_status hrt_accumulate_history_moments(hrt_context* ctx, uint32_t max_history) {
+  return accumulate_history_call(ctx, max_history, true, "hrt_accumulate_history_moments");
+}
+
+extern "C" hrt_status hrt_reproject_moments(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
+                                            const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
+  return reproject_call(ctx, info, prev, prev_hits, cur, cur_hits, true, "hrt_reproject_moments");
+}
+
+extern "C" hrt_status hrt_fill_moments(hrt_context* ctx, float m1, float m2) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  hrt_status st = begin_history(ctx, "hrt_fill_moments");
+  if (st != HRT_OK) return st;
+  if ((st = begin_moments(ctx, "hrt_fill_moments")) != HRT_OK) return st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  HRT_HIP(ctx, hrt::launch_fill_moments(ctx->hist_mom, ctx->npix(), m1, m2, ctx->stream));
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_read_moments(hrt_context* ctx, float* dst, size_t bytes) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (!dst) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_read_moments: null destination");
+  const size_t need = ctx->npix() * 8;
+  if (bytes < need) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_read_moments: destination too small");
+  hrt_status st = begin_history(ctx, "hrt_read_moments");
+  if (st != HRT_OK) return st;
+  if ((st = begin_moments(ctx, "hrt_read_moments")) != HRT_OK) return st;
+  HRT_HIP(ctx, hipMemcpyAsync(dst, ctx->hist_mom, need, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HRT_OK;
+}
+
+namespace {
+
+// Every check of hrt_denoise_variance / hrt_denoise_variance_present that concerns the filter itself, on the host.
+hrt_status check_variance(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!info) return bad("null info");
+  if (ctx->comm || ctx->part_count > 1)
+    return bad("a context of a row-tile partition or joined to a communicator cannot denoise (a tap's neighbour rows "
+               "live on another part; the gathered form is out of scope)");
+  if (info->iterations > hrt::kVarianceMaxIterations) return bad("iterations must be 0..5");
+  if (info->method > HRT_VARIANCE_TILED) return bad("unknown method");
+  if (info->flags != 0) return bad("flags must be 0");
+  if (info->min_history == 0) return bad("min_history must be at least 1");
+  for (const float s : {info->sigma_variance, info->variance_floor, info->sigma_normal, info->sigma_depth})
+    if (!(std::isfinite(s) && s > 0.0f)) return bad("every sigma and the variance floor must be finite and greater than 0");
+  if (guide) {
+    hrt_status st = bind(ctx);
+    if (st != HRT_OK) return st;
+    if ((uintptr_t)guide % 16 != 0) return bad("the guide must be 16-byte aligned");
+    if (!query_direct(ctx, guide) || !query_direct(ctx, guide + (ctx->npix() - 1)))
+      return bad("the guide must be width x height records in memory of the context's device");
+  }
+  return HRT_OK;
+}
+
+// The filter on ctx->stream, after everything that wrote the accumulator, N and M (arguments already checked):
+// variance_prep, then one pass per iteration between hrt_denoise's two scratch images.  The last pass (with no
+// iterations: variance_store) writes `out` (float4 texels, or RGBA8 words when out_rgba8) when out is not null,
+// else the scratch image the pass before it did not write, and the variance to vout when that is not null;
+// *result = where the image is.
+hrt_status enqueue_variance(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide, void* out, bool out_rgba8,
+                            float* vout, void** result, const char* who) {
+  const size_t np = ctx->npix();
+  hrt_status st;
+  if ((st = begin_history(ctx, who)) != HRT_OK) return st;
+  if ((st = begin_moments(ctx, who)) != HRT_OK) return st;
+  for (void*& img : ctx->dn_img)
+    if ((st = ensure_staging(ctx, &img, np * 16, who)) != HRT_OK) return st;
+  if (guide) {
+    if ((st = ensure_staging(ctx, &ctx->dn_guide, np * 16, who)) != HRT_OK) return st;
+    if ((st = ensure_staging(ctx, &ctx->dn_keys, np * 4, who)) != HRT_OK) return st;
+  }
+  void* gd = guide ? ctx->dn_guide : nullptr;
+  void* keys = guide ? ctx->dn_keys : nullptr;
+  const void* src = hrt::local_image(ctx, HRT_IMG_ACCUM);
+  if (!src) return fail(ctx, HRT_ERR_HIP, std::string(who) + ": lane wait failed");
+  const hrt::VariancePrep prep{src, ctx->f32(), guide, ctx->hist_cnt, ctx->hist_mom, ctx->dn_img[0], gd, keys,
+                               ctx->width, ctx->local_rows, info->min_history};
+  HRT_HIP(ctx, hrt::launch_variance_prep(prep, ctx->stream));
+  const int final_kind = out_rgba8 ? hrt::kVarianceOutRgba8 : hrt::kVarianceOutFloat;
+  if (info->iterations == 0) {
+    void* to = out ? out : ctx->dn_img[1];
+    HRT_HIP(ctx, hrt::launch_variance_store(ctx->dn_img[0], to, vout, final_kind, np, ctx->stream));
+    *result = to;
+    return HRT_OK;
+  }
+  // S16's and S14's host constants, each one rounded float operation
+  const float sv2 = info->sigma_variance * info->sigma_variance, kn = 1.0f / info->sigma_normal;
+  for (uint32_t i = 0; i < info->iterations; ++i) {
+    const bool last = i + 1 == info->iterations;
+    void* to = last && out ? out : ctx->dn_img[(i + 1) & 1];
+    const hrt::VariancePass p{ctx->dn_img[i & 1], gd, keys, to, last ? vout : nullptr, last ? final_kind : hrt::kVarianceOutPass,
+                              ctx->width, ctx->local_rows, 1u << i, sv2, info->variance_floor, kn, info->sigma_depth};
+    HRT_HIP(ctx, hrt::launch_variance_atrous(p, hrt::variance_form(info->method, i), ctx->stream));
+    *result = to;
+  }
+  return HRT_OK;
+}
+
+}  // namespace
+
+extern "C" void hrt_variance_defaults(hrt_variance_info* info) {
+  if (!info) return;
+  *info = hrt_variance_info{hrt::kVarianceMaxIterations, HRT_VARIANCE_AUTO, 0u, HRT_VARIANCE_MIN_HISTORY,
+                            HRT_VARIANCE_SIGMA, HRT_VARIANCE_FLOOR, HRT_DENOISE_SIGMA_NORMAL, HRT_DENOISE_SIGMA_DEPTH};
+}
+
+extern "C" hrt_status hrt_denoise_variance(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide, uint32_t fmt,
+                                           void* dst, size_t bytes, float* variance_dst, size_t variance_bytes) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_denoise_variance";
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  hrt_status st = check_variance(ctx, info, guide, who);
+  if (st != HRT_OK) return st;
+  if (fmt != HRT_FMT_RGBA8 && fmt != HRT_FMT_RGBA32F) return bad("unknown format");
+  if (!dst) return bad("null destination");
+  const bool rgba8 = fmt == HRT_FMT_RGBA8;
+  const size_t need = ctx->npix() * (rgba8 ? 4 : 16), vneed = ctx->npix() * 4;
+  if (bytes < need) return bad("destination too small");
+  if (variance_dst && variance_bytes < vneed) return bad("variance destination too small");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  // device memory a store may address: the last pass writes it; anything else is copied from the scratch
+  const bool direct = (uintptr_t)dst % (rgba8 ? 4 : 16) == 0 && query_direct(ctx, dst) &&
+                      query_direct(ctx, static_cast<const char*>(dst) + (need - 1));
+  const bool vdirect = variance_dst && (uintptr_t)variance_dst % 4 == 0 && query_direct(ctx, variance_dst) &&
+                       query_direct(ctx, reinterpret_cast<const char*>(variance_dst) + (vneed - 1));
+  float* vout = nullptr;
+  if (variance_dst) {
+    vout = variance_dst;
+    if (!vdirect) {
+      void* p = ctx->var_stage;
+      if ((st = ensure_staging(ctx, &p, vneed, who)) != HRT_OK) return st;
+      vout = ctx->var_stage = static_cast<float*>(p);
+    }
+  }
+  void* res = nullptr;
+  if ((st = enqueue_variance(ctx, info, guide, direct ? dst : nullptr, rgba8, vout, &res, who)) != HRT_OK) return st;
+  if (!direct) HRT_HIP(ctx, hipMemcpyAsync(dst, res, need, hipMemcpyDefault, ctx->stream));
+  if (variance_dst && !vdirect) HRT_HIP(ctx, hipMemcpyAsync(variance_dst, vout, vneed, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_denoise_variance_present(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide,
+                                                   const hrt_present_info* target, void* dst, uint64_t dst_bytes,
+                                                   uint64_t* ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_denoise_variance_present";
+  hrt_status st = check_variance(ctx, info, guide, who);
+  if (st != HRT_OK) return st;
+  if ((st = check_present(ctx, target, dst, dst_bytes, ticket, true, who)) != HRT_OK) return st;
+  hipEvent_t ev = nullptr;
+  if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  void* res = nullptr;
+  if ((st = enqueue_variance(ctx, info, guide, nullptr, false, nullptr, &res, who)) != HRT_OK) return st;
+  // the filtered float image through the present pass unchanged
+  HRT_HIP(ctx, hrt::launch_present(res, true, ctx->width, ctx->local_rows, present_target(target, dst), ctx->stream));
+  return ticket_end(ctx, ev, ticket);
 }
 
 extern "C" hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done) {

@@ -239,6 +239,14 @@ struct hrt_context {
   uint32_t* hist_cnt = nullptr;
   uint32_t* hist_cnt_next = nullptr;
   void* hist_accum_next = nullptr;
+  // The variance-guided denoise (hrt_accumulate_history_moments, hrt_reproject_moments, hrt_fill_moments,
+  // hrt_read_moments, hrt_denoise_variance[_present]): the moments image M, two floats per pixel, allocated and
+  // zeroed by the first call of any of them; what hrt_reproject_moments writes M' into, swapped with hist_mom after
+  // the pass; and the staging of a variance_dst in host memory (one float per pixel).  The filter's passes run
+  // between dn_img[0] and dn_img[1], with dn_guide and dn_keys
+  float* hist_mom = nullptr;
+  float* hist_mom_next = nullptr;
+  float* var_stage = nullptr;
   // The first-hit pass (hrt_first_hits): its own camera buffers (a fourth set beside the lanes', the scene's
   // sizes), allocated by the first TILES call and dropped by hrt_set_scene; fh_key = the camera position's bits
   // and num_meshes the records were built for (fh_ready: by a launch already enqueued on `stream`); the device

@@ -1,6 +1,8 @@
 // hrt_history.hip -- gfx950 kernels of the temporal history (hrt_history.h):
 // fold_history, the combiner with a per-pixel frame number, and reproject, which carries the accumulator and
-// the count image across a change of view.
+// the count image across a change of view; and their forms that carry the luminance moments image M of the
+// variance-guided denoise beside them (hrt_variance.h): fold_history_moments and
+// reproject<.., true>.
 //
 // S15 is pinned operation by operation and the unit is built with -ffp-contract=off: every statement of the
 // reprojection below is one rounded float operation of the spec, in its order (hdot / hcross are S15's own
@@ -11,6 +13,7 @@
 
 #include "hip_raytrace.h"
 #include "hrt_history.h"
+#include "hrt_variance.h"
 #include "hrt_math.h"
 
 namespace hrt {
@@ -93,6 +96,79 @@ __global__ __launch_bounds__(256) void fold_history(T* cur, const T* nw, uint32_
   }
 }
 
+// ---- the history fold with moments (S16) -------------------------------------------------------------------
+// S14's C0 of a trace texel through the workgroup's UNORM8 table (its entries are unorm8_to_float's values).
+__device__ __forceinline__ f3 texel_c0(uint32_t v, const float* tab) {
+  return {tab[v & 255u], tab[(v >> 8) & 255u], tab[(v >> 16) & 255u]};
+}
+__device__ __forceinline__ f3 texel_c0(float4 v, const float*) { return {v.x, v.y, v.z}; }
+// The moments of one pixel after the frame whose trace texel is nw: the sample (l, l * l) folded as two channels
+// of a float texel are (n == 0: the sample itself, m not read by the caller).
+template <typename T>
+__device__ __forceinline__ float2 moments_step(float2 m, T nw, uint32_t n, const float* tab) {
+  const f3 c = texel_c0(nw, tab);
+  const float l = variance_lum(c.x, c.y, c.z);
+  const float l2 = l * l;
+  if (n == 0u) return make_float2(l, l2);
+  const float ff = (float)n, ff1 = (float)(n + 1u);
+  return make_float2((l + m.x * ff) / ff1, (l2 + m.y * ff) / ff1);
+}
+
+// fold_history with the moments image: the same lanes and the same 128-bit accesses of cur, nw and cnt; a lane of
+// the RGBA8 quads takes its four pixels' moments as two 128-bit accesses of two pixels each, a float lane (and an
+// RGBA8 remainder lane) its pixel's pair as one 64-bit access.
+template <typename T>
+__global__ __launch_bounds__(256) void fold_history_moments(T* cur, const T* nw, uint32_t* cnt, float2* mom, size_t npix,
+                                                            size_t quads, uint32_t max_history) {
+  const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if constexpr (std::is_same_v<T, uint32_t>) {
+    __shared__ float tab[256];
+    tab[threadIdx.x] = unorm8_to_float(threadIdx.x);
+    __syncthreads();
+    if (t < quads) {
+      const uint4 n = reinterpret_cast<const uint4*>(cnt)[t];
+      const uint4 v = reinterpret_cast<const uint4*>(nw)[t];
+      uint4 c = make_uint4(0u, 0u, 0u, 0u);
+      float4 ma = make_float4(0.0f, 0.0f, 0.0f, 0.0f), mb = ma;
+      if ((n.x | n.y | n.z | n.w) != 0u) {
+        c = reinterpret_cast<const uint4*>(cur)[t];
+        ma = reinterpret_cast<const float4*>(mom)[2 * t];
+        mb = reinterpret_cast<const float4*>(mom)[2 * t + 1];
+      }
+      reinterpret_cast<uint4*>(cur)[t] = make_uint4(hist_step(c.x, v.x, n.x, tab), hist_step(c.y, v.y, n.y, tab),
+                                                    hist_step(c.z, v.z, n.z, tab), hist_step(c.w, v.w, n.w, tab));
+      reinterpret_cast<uint4*>(cnt)[t] = make_uint4(hist_next(n.x, max_history), hist_next(n.y, max_history),
+                                                    hist_next(n.z, max_history), hist_next(n.w, max_history));
+      const float2 m0 = moments_step(make_float2(ma.x, ma.y), v.x, n.x, tab);
+      const float2 m1 = moments_step(make_float2(ma.z, ma.w), v.y, n.y, tab);
+      const float2 m2 = moments_step(make_float2(mb.x, mb.y), v.z, n.z, tab);
+      const float2 m3 = moments_step(make_float2(mb.z, mb.w), v.w, n.w, tab);
+      reinterpret_cast<float4*>(mom)[2 * t] = make_float4(m0.x, m0.y, m1.x, m1.y);
+      reinterpret_cast<float4*>(mom)[2 * t + 1] = make_float4(m2.x, m2.y, m3.x, m3.y);
+    }
+    const size_t i = quads * 4u + t;
+    if (i < npix) {
+      const uint32_t n = cnt[i];
+      const uint32_t v = nw[i];
+      cur[i] = hist_step(n == 0u ? 0u : cur[i], v, n, tab);
+      cnt[i] = hist_next(n, max_history);
+      mom[i] = moments_step(n == 0u ? make_float2(0.0f, 0.0f) : mom[i], v, n, tab);
+    }
+  } else {
+    if (t >= npix) return;
+    const uint32_t n = cnt[t];
+    const float4 v = nw[t];
+    cur[t] = hist_step(n == 0u ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : cur[t], v, n, nullptr);
+    cnt[t] = hist_next(n, max_history);
+    mom[t] = moments_step(n == 0u ? make_float2(0.0f, 0.0f) : mom[t], v, n, nullptr);
+  }
+}
+
+__global__ __launch_bounds__(256) void fill_moments(float2* mom, size_t npix, float m1, float m2) {
+  const size_t t = (size_t)blockIdx.x * 256u + threadIdx.x;
+  if (t < npix) mom[t] = make_float2(m1, m2);
+}
+
 // ---- the reprojection ------------------------------------------------------------------------------------
 constexpr uint32_t kTileW = 32, kTileH = 8;  // one pixel per thread of a 256-thread workgroup, a wave = 2 rows
 
@@ -152,12 +228,16 @@ __device__ __forceinline__ bool tap_accepted(const ReprojCentre& c, const uint32
 
 // One thread per pixel, row-major 32-wide workgroup rows: after a small camera move the sources of a wave's
 // two rows are neighbours again, so their texels, counts and hit records share cache lines.
-template <typename T, uint32_t Filter>
+// Moments (S16): the moments image is carried beside them -- mom_out[i] <- the same taps of mom_in with the same
+// weights, in the same order, over the same wsum; (0, 0) for a rejected pixel.  Without it the two pointers are
+// not touched.
+template <typename T, uint32_t Filter, bool Moments>
 __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, const uint32_t* __restrict__ cnt_in,
                                                  T* __restrict__ acc_out, uint32_t* __restrict__ cnt_out,
                                                  const float4* __restrict__ prev_hits,
                                                  const float4* __restrict__ cur_hits, ViewK vp, ViewK vc, uint32_t w,
-                                                 uint32_t h, float tol, float min_dot) {
+                                                 uint32_t h, float tol, float min_dot,
+                                                 const float2* __restrict__ mom_in, float2* __restrict__ mom_out) {
   const uint32_t x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1u));
   const uint32_t y = blockIdx.y * kTileH + threadIdx.x / kTileW;
   if (x >= w || y >= h) return;
@@ -192,6 +272,7 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
   const float s = hdot(vp.first, n) / hdot(q, n);
   T texel = texel_cleared<T>();
   uint32_t count = 0u;
+  float2 mom = make_float2(0.0f, 0.0f);
   if (s > 0.0f) {
     const f3 r = {q.x * s - vp.first.x, q.y * s - vp.first.y, q.z * s - vp.first.z};
     const float u = hdot(r, vp.dx) / hdot(vp.dx, vp.dx);
@@ -205,6 +286,7 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
         if (tap_accepted(c, cnt_in, prev_hits, j, nj)) {
           texel = acc_in[j];
           count = nj;
+          if constexpr (Moments) mom = mom_in[j];
         }
       }
     } else {
@@ -213,6 +295,7 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
         const float a = u - x0, b = wv - y0;
         const int64_t ix0 = (int64_t)x0, iy0 = (int64_t)y0;
         float ar = 0.0f, ag = 0.0f, ab = 0.0f, wsum = 0.0f;
+        float am1 = 0.0f, am2 = 0.0f;
         uint32_t nmin = 0xFFFFFFFFu;
         bool used = false;
 #pragma unroll
@@ -229,6 +312,11 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
           ar = ar + wt * cj.x;
           ag = ag + wt * cj.y;
           ab = ab + wt * cj.z;
+          if constexpr (Moments) {
+            const float2 mj = mom_in[j];
+            am1 = am1 + wt * mj.x;
+            am2 = am2 + wt * mj.y;
+          }
           wsum = wsum + wt;
           nmin = nj < nmin ? nj : nmin;
           used = true;
@@ -240,12 +328,14 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
           else
             texel = make_float4(r8, g8, b8, 1.0f);
           count = nmin;
+          if constexpr (Moments) mom = make_float2(am1 / wsum, am2 / wsum);
         }
       }
     }
   }
   acc_out[i] = texel;
   cnt_out[i] = count;
+  if constexpr (Moments) mom_out[i] = mom;
 }
 
 // ---- launch wrappers (host) ------------------------------------------------------------------------------
@@ -278,22 +368,24 @@ static ViewK view_k(const hrt_view& v) {
   return k;
 }
 
-template <typename T>
-static void reproject_launch(const ReprojectPass& p, dim3 grid, hipStream_t stream) {
+template <typename T, bool Moments>
+static void reproject_launch(const ReprojectPass& p, const float* mom_in, float* mom_out, dim3 grid, hipStream_t stream) {
   const T* ain = static_cast<const T*>(p.acc_in);
   T* aout = static_cast<T*>(p.acc_out);
   const float4* ph = reinterpret_cast<const float4*>(p.prev_hits);
   const float4* ch = reinterpret_cast<const float4*>(p.cur_hits);
   const ViewK vp = view_k(p.prev), vc = view_k(p.cur);
+  const float2* mi = reinterpret_cast<const float2*>(mom_in);
+  float2* mo = reinterpret_cast<float2*>(mom_out);
   if (p.filter == HRT_REPROJECT_NEAREST)
-    reproject<T, HRT_REPROJECT_NEAREST><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h,
-                                                                  p.depth_tolerance, p.min_normal_dot);
+    reproject<T, HRT_REPROJECT_NEAREST, Moments><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w,
+                                                                           p.h, p.depth_tolerance, p.min_normal_dot, mi, mo);
   else
-    reproject<T, HRT_REPROJECT_BILINEAR><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h,
-                                                                   p.depth_tolerance, p.min_normal_dot);
+    reproject<T, HRT_REPROJECT_BILINEAR, Moments><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w,
+                                                                            p.h, p.depth_tolerance, p.min_normal_dot, mi, mo);
 }
 
-hipError_t launch_reproject(const ReprojectPass& p, hipStream_t stream) {
+static hipError_t reproject_dispatch(const ReprojectPass& p, const float* mom_in, float* mom_out, hipStream_t stream) {
   if (p.w == 0 || p.h == 0) return hipSuccess;
   if (!p.acc_in || !p.cnt_in || !p.acc_out || !p.cnt_out || !p.prev_hits || !p.cur_hits) return hipErrorInvalidValue;
   if (p.acc_in == p.acc_out || p.cnt_in == p.cnt_out) return hipErrorInvalidValue;
@@ -302,10 +394,54 @@ hipError_t launch_reproject(const ReprojectPass& p, hipStream_t stream) {
   const dim3 grid((p.w + kTileW - 1) / kTileW, (p.h + kTileH - 1) / kTileH, 1);
   // (grid.y = tile rows; float(w - 1) and float(h - 1), the bounds of S15's steps 9 and 10, must be exact)
   if (grid.y > 65535u || p.w > (1u << 24)) return hipErrorInvalidValue;
-  if (p.f32)
-    reproject_launch<float4>(p, grid, stream);
-  else
-    reproject_launch<uint32_t>(p, grid, stream);
+  if (mom_in) {
+    if (p.f32)
+      reproject_launch<float4, true>(p, mom_in, mom_out, grid, stream);
+    else
+      reproject_launch<uint32_t, true>(p, mom_in, mom_out, grid, stream);
+  } else if (p.f32) {
+    reproject_launch<float4, false>(p, nullptr, nullptr, grid, stream);
+  } else {
+    reproject_launch<uint32_t, false>(p, nullptr, nullptr, grid, stream);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_reproject(const ReprojectPass& p, hipStream_t stream) {
+  return reproject_dispatch(p, nullptr, nullptr, stream);
+}
+
+hipError_t launch_reproject_moments(const ReprojectPass& p, const float* mom_in, float* mom_out, hipStream_t stream) {
+  if (p.w == 0 || p.h == 0) return hipSuccess;
+  if (!mom_in || !mom_out || mom_in == mom_out || (((uintptr_t)mom_in | (uintptr_t)mom_out) & 7u) != 0)
+    return hipErrorInvalidValue;
+  return reproject_dispatch(p, mom_in, mom_out, stream);
+}
+
+hipError_t launch_fold_history_moments(void* cur, const void* nw, uint32_t* cnt, float* mom, bool f32, size_t npix,
+                                       uint32_t max_history, hipStream_t stream) {
+  if (npix == 0) return hipSuccess;
+  if (!cur || !nw || !cnt || !mom || max_history == 0 || max_history > kHistoryMax) return hipErrorInvalidValue;
+  if (((uintptr_t)mom & 15u) != 0) return hipErrorInvalidValue;
+  float2* m = reinterpret_cast<float2*>(mom);
+  if (f32) {
+    if ((((uintptr_t)cur | (uintptr_t)nw) & 15u) != 0) return hipErrorInvalidValue;
+    fold_history_moments<float4><<<(unsigned)((npix + 255) / 256), 256, 0, stream>>>(
+        static_cast<float4*>(cur), static_cast<const float4*>(nw), cnt, m, npix, 0, max_history);
+  } else {
+    const bool vec = (((uintptr_t)cur | (uintptr_t)nw | (uintptr_t)cnt) & 15u) == 0;
+    const size_t quads = vec ? npix / 4 : 0, rest = npix - 4 * quads;
+    const size_t threads = quads > rest ? quads : rest;
+    fold_history_moments<uint32_t><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+        static_cast<uint32_t*>(cur), static_cast<const uint32_t*>(nw), cnt, m, npix, quads, max_history);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_fill_moments(float* mom, size_t npix, float m1, float m2, hipStream_t stream) {
+  if (npix == 0) return hipSuccess;
+  if (!mom || ((uintptr_t)mom & 7u) != 0) return hipErrorInvalidValue;
+  fill_moments<<<(unsigned)((npix + 255) / 256), 256, 0, stream>>>(reinterpret_cast<float2*>(mom), npix, m1, m2);
   return hipGetLastError();
 }
 

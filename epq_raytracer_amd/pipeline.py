@@ -397,6 +397,89 @@ class HrtContext:
         self.read_history_into(out.ctypes.data, out.nbytes)
         return out
 
+    # ---- the variance-guided denoise (hrt_denoise_variance and the moments calls) ----
+
+    def variance_info(self, iterations: Optional[int] = None, method: int = _lib.VARIANCE_AUTO,
+                      min_history: Optional[int] = None, sigma_variance: Optional[float] = None,
+                      variance_floor: Optional[float] = None, sigma_normal: Optional[float] = None,
+                      sigma_depth: Optional[float] = None) -> _lib.VarianceInfo:
+        """hrt_variance_defaults with the given fields replaced (None: the default)."""
+        info = _lib.VarianceInfo()
+        self.lib.hrt_variance_defaults(ctypes.byref(info))
+        info.method = int(method)
+        if iterations is not None:
+            info.iterations = int(iterations)
+        if min_history is not None:
+            info.min_history = int(min_history)
+        for name, v in (("sigma_variance", sigma_variance), ("variance_floor", variance_floor),
+                        ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+            if v is not None:
+                setattr(info, name, float(v))
+        return info
+
+    def accumulate_history_moments(self, max_history: int) -> None:
+        """hrt_accumulate_history_moments: ``accumulate_history``, and the trace image's luminance moments folded
+        into the moments image with the same per-pixel counts."""
+        self._check(self.lib.hrt_accumulate_history_moments(self.handle, int(max_history)),
+                    "hrt_accumulate_history_moments")
+
+    def reproject_moments(self, prev: "View", prev_hits_ptr: int, cur: "View", cur_hits_ptr: int,
+                          info: Optional[_lib.ReprojectInfo] = None, **fields) -> None:
+        """hrt_reproject_moments: ``reproject``, and the moments image carried through the same taps (cleared where
+        a pixel is rejected).  Mixing the plain and the moments calls leaves stale moments."""
+        info = info if info is not None else self.reproject_info(**fields)
+        self._check(self.lib.hrt_reproject_moments(self.handle, ctypes.byref(info), ctypes.byref(prev.record),
+                                                   ctypes.c_void_p(prev_hits_ptr), ctypes.byref(cur.record),
+                                                   ctypes.c_void_p(cur_hits_ptr)), "hrt_reproject_moments")
+
+    def fill_moments(self, m1: float, m2: float) -> None:
+        """hrt_fill_moments: every pixel's moments = (m1, m2)."""
+        self._check(self.lib.hrt_fill_moments(self.handle, float(m1), float(m2)), "hrt_fill_moments")
+
+    def read_moments_into(self, dst_ptr: int, nbytes: int) -> None:
+        """hrt_read_moments into caller memory (host or device pointer).  Blocking."""
+        self._check(self.lib.hrt_read_moments(self.handle, ctypes.c_void_p(dst_ptr), int(nbytes)), "hrt_read_moments")
+
+    def read_moments(self) -> np.ndarray:
+        """hrt_read_moments: the moments image as float32 (local_rows, W, 2)."""
+        out = np.empty((self.local_rows, self.width, 2), dtype=np.float32)
+        self.read_moments_into(out.ctypes.data, out.nbytes)
+        return out
+
+    def denoise_variance_into(self, dst_ptr: int, nbytes: int, fmt: int = _lib.FMT_RGBA8, guide_ptr: Optional[int] = None,
+                              variance_ptr: Optional[int] = None, variance_nbytes: int = 0,
+                              info: Optional[_lib.VarianceInfo] = None, **fields) -> None:
+        """hrt_denoise_variance into caller memory (host or device pointers): the variance-guided a-trous filter
+         of the accumulator as local_rows x W texels of fmt and, with variance_ptr, the filtered
+        variance as local_rows x W floats.  guide_ptr as ``denoise_into`` takes it; ``info`` or the fields of
+        ``variance_info``.  Blocking."""
+        info = info if info is not None else self.variance_info(**fields)
+        self._check(self.lib.hrt_denoise_variance(self.handle, ctypes.byref(info), ctypes.c_void_p(guide_ptr or 0), int(fmt),
+                                                  ctypes.c_void_p(dst_ptr), int(nbytes), ctypes.c_void_p(variance_ptr or 0),
+                                                  int(variance_nbytes)), "hrt_denoise_variance")
+
+    def denoise_variance(self, fmt: int = _lib.FMT_RGBA8, guide_ptr: Optional[int] = None, with_variance: bool = False,
+                         info: Optional[_lib.VarianceInfo] = None, **fields):
+        """hrt_denoise_variance: the filtered accumulator as uint8 or float32 (local_rows, W, 4); with_variance:
+        (image, variance float32 (local_rows, W))."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.uint8 if fmt == _lib.FMT_RGBA8 else np.float32)
+        var = np.empty((self.local_rows, self.width), dtype=np.float32) if with_variance else None
+        self.denoise_variance_into(out.ctypes.data, out.nbytes, fmt, guide_ptr, var.ctypes.data if with_variance else None,
+                                   var.nbytes if with_variance else 0, info, **fields)
+        return (out, var) if with_variance else out
+
+    def denoise_variance_present(self, dst_ptr: int, nbytes: int, width: int, height: int, pitch: Optional[int] = None,
+                                 fmt: int = _lib.PRESENT_B8G8R8A8, guide_ptr: Optional[int] = None,
+                                 info: Optional[_lib.VarianceInfo] = None, **fields) -> int:
+        """hrt_denoise_variance_present: the filter, then ``present`` of the filtered accumulator (same target
+        rules, same ticket sequence); returns the ticket without waiting."""
+        info = info if info is not None else self.variance_info(**fields)
+        target, t = self._present_info(_lib.IMG_ACCUM, width, height, pitch, fmt), ctypes.c_uint64()
+        self._check(self.lib.hrt_denoise_variance_present(self.handle, ctypes.byref(info), ctypes.c_void_p(guide_ptr or 0),
+                                                          ctypes.byref(target), ctypes.c_void_p(dst_ptr), int(nbytes),
+                                                          ctypes.byref(t)), "hrt_denoise_variance_present")
+        return t.value
+
     # ---- ray queries (hrt_intersect, hrt_intersect_primary) ----
 
     @staticmethod
@@ -681,6 +764,17 @@ class RenderPassOverFrame:
         return self.ctx.denoise_present(target.ptr, target.nbytes, target.width, target.height, target.pitch,
                                         target.format, guide_ptr, image_id=view.image_id, **fields)
 
+    def render_variance_denoised(self, view: Image, target: PresentTarget, guide_ptr: Optional[int] = None, **fields) -> int:
+        """``render`` with the variance-guided denoise between the accumulator and the quad
+        (hrt_denoise_variance_present): view must be the accumulated image, ``fields`` those of
+        ``HrtContext.variance_info``.  Returns the ticket."""
+        if view.ctx is not self.ctx or view.image_id != _lib.IMG_ACCUM:
+            raise ValueError("view must be the accumulated image of the render pass's context")
+        if target.format != self.output_format:
+            raise ValueError("the target's format differs from the render pass's output format")
+        return self.ctx.denoise_variance_present(target.ptr, target.nbytes, target.width, target.height, target.pitch,
+                                                 target.format, guide_ptr, **fields)
+
 
 # ---- pipelines ---------------------------------------------------------------------------------
 
@@ -809,13 +903,23 @@ class DiffusePipeline:
             raise ValueError("next_image must be the trace image of the same context")
         self.ctx.accumulate(frame_num)
 
-    def next_frame_history(self, next_image: Image, max_history: int = 32) -> None:
+    def next_frame_history(self, next_image: Image, max_history: int = 32, moments: bool = False) -> None:
         """``next_frame`` with per-pixel frame counts (hrt_accumulate_history; not a reference feature): after a
         camera move, ``HrtContext.reproject`` first, then this -- a pixel whose surface point the old view
-        held keeps its history, the others start again with this frame."""
+        held keeps its history, the others start again with this frame.  moments: also fold the frame's
+        luminance moments (hrt_accumulate_history_moments, with ``HrtContext.reproject_moments`` after a move),
+        what ``variance_denoised`` filters by."""
         if next_image.ctx is not self.ctx or next_image.image_id != _lib.IMG_TRACE:
             raise ValueError("next_image must be the trace image of the same context")
-        self.ctx.accumulate_history(max_history)
+        if moments:
+            self.ctx.accumulate_history_moments(max_history)
+        else:
+            self.ctx.accumulate_history(max_history)
+
+    def variance_denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **fields) -> np.ndarray:
+        """The accumulated image through the variance-guided denoise (hrt_denoise_variance), as uint8 or float32
+        (H, W, 4); ``fields`` as ``HrtContext.variance_info`` takes them."""
+        return self.ctx.denoise_variance(fmt, guide_ptr, **fields)
 
     def denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **sigmas) -> np.ndarray:
         """The accumulated image through the denoise pass (hrt_denoise), as uint8 or float32 (H, W, 4):

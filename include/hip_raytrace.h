@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): the first-hit pass -- hrt_first_hits_method,
+/* 6, additive (no bump: nothing existing changed): the variance-guided denoise -- hrt_variance_method,
+ * hrt_variance_info, hrt_variance_defaults, hrt_accumulate_history_moments, hrt_reproject_moments, hrt_fill_moments,
+ * hrt_read_moments, hrt_denoise_variance, hrt_denoise_variance_present.
+ * 6, additive (no bump: nothing existing changed): the first-hit pass -- hrt_first_hits_method,
  * HRT_FIRST_HITS_COUNT, hrt_first_hits_stats, hrt_first_hits, hrt_get_first_hits_stats.
  * 6, additive (no bump: nothing existing changed): temporal history -- hrt_view, hrt_reproject_filter,
  * hrt_reproject_info, hrt_reproject_defaults, hrt_reproject, hrt_accumulate_history, hrt_fill_history,
@@ -344,6 +347,28 @@ typedef struct hrt_reproject_info { /* 32 bytes */
   uint32_t reserved[4];  /* ignored */
 } hrt_reproject_info;
 
+/* ---- the variance-guided denoise (hrt_denoise_variance, the moments calls) ---- */
+/* hrt_variance_defaults' parameters: design parameters chosen on the CPU oracle's frames */
+#define HRT_VARIANCE_SIGMA 4.0f
+#define HRT_VARIANCE_FLOOR 1e-10f
+#define HRT_VARIANCE_MIN_HISTORY 4u
+typedef enum hrt_variance_method {
+  HRT_VARIANCE_AUTO = 0,   /* per step, the kernel that measured faster */
+  HRT_VARIANCE_DIRECT = 1, /* atrous_variance_direct: every tap a global load */
+  HRT_VARIANCE_TILED = 2   /* atrous_variance_tiled at steps 1, 2, 4: taps from a tile staged in LDS */
+} hrt_variance_method;
+
+typedef struct hrt_variance_info { /* 32 bytes */
+  uint32_t iterations;  /* 0..5: passes with steps 1, 2, 4, 8, 16; 0 returns the source and the variance estimate */
+  uint32_t method;      /* hrt_variance_method; every method gives the same bytes */
+  uint32_t flags;       /* must be 0 */
+  uint32_t min_history; /* >= 1: counts below it take the spatial estimate */
+  float sigma_variance; /* finite, > 0 */
+  float variance_floor; /* finite, > 0 */
+  float sigma_normal;   /* as hrt_denoise_info */
+  float sigma_depth;
+} hrt_variance_info;
+
 /* ---- the first-hit pass (hrt_first_hits) ---- */
 typedef enum hrt_first_hits_method {
   HRT_FIRST_HITS_AUTO = 0,  /* TILES: it measured faster on island and on cave */
@@ -426,6 +451,10 @@ HRT_STATIC_ASSERT(sizeof(hrt_view) == 128 && offsetof(hrt_view, cam_alignment_ma
                       offsetof(hrt_view, grid_first) == 80 && offsetof(hrt_view, grid_dx) == 96 &&
                       offsetof(hrt_view, grid_dy) == 112,
                   "hrt_view");
+HRT_STATIC_ASSERT(sizeof(hrt_variance_info) == 32 && offsetof(hrt_variance_info, method) == 4 &&
+                      offsetof(hrt_variance_info, min_history) == 12 && offsetof(hrt_variance_info, sigma_variance) == 16 &&
+                      offsetof(hrt_variance_info, variance_floor) == 20 && offsetof(hrt_variance_info, sigma_depth) == 28,
+                  "hrt_variance_info");
 HRT_STATIC_ASSERT(sizeof(hrt_reproject_info) == 32 && offsetof(hrt_reproject_info, flags) == 4 &&
                       offsetof(hrt_reproject_info, depth_tolerance) == 8 &&
                       offsetof(hrt_reproject_info, min_normal_dot) == 12 && offsetof(hrt_reproject_info, reserved) == 16,
@@ -1002,6 +1031,61 @@ hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count);
 /* BLOCKING: the count image, height x width uint32 in trace-image row order, to host or device memory at dst
  * (bytes >= height * width * 4). */
 hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t bytes);
+
+/* ---- the variance-guided denoise (DESIGN.md §2 S16 pins the arithmetic, §31 the kernels) ------------------
+ * Beside the accumulator and the count image N the context owns a moments image M: two floats per pixel, the
+ * running first and second moment (m1, m2) of the luminance of the frames that pixel's accumulator texel
+ * holds, float in either context mode.  It is allocated and zeroed by the first call of any function below and
+ * freed by hrt_destroy.  hrt_accumulate_history_moments and hrt_reproject_moments are hrt_accumulate_history
+ * and hrt_reproject -- the same bytes in the accumulator and in N, the same ordering, lanes and the one count in
+ * hrt_stats.accumulates -- and carry M with them: the fold adds the sample (l, l * l) of the trace texel with the
+ * pixel's own count, the reprojection carries M through the accepted taps with their weights and clears it
+ * where it rejects.  hrt_accumulate_history, hrt_reproject and hrt_fill_history neither read nor write M: a
+ * caller who mixes the plain and the moments calls gets moments that describe another accumulator (stale, never
+ * out of bounds); nothing polices it.
+ *
+ * hrt_denoise_variance is hrt_denoise's a-trous filter over HRT_IMG_ACCUM with a per-pixel colour constant: the
+ * variance of the accumulated luminance is estimated per pixel -- from M and N where N >= min_history, else from
+ * the 7 x 7 neighbourhood of the same surface -- filtered along with the colour, and each pass weighs a tap's
+ * colour distance by 1 / (sigma_variance^2 * variance + variance_floor), the variance smoothed over 3 x 3
+ * pixels: a settled pixel is left nearly alone, a pixel a move has just uncovered is filtered widely.  Every
+ * byte of every result is defined by S16: the three methods, both libraries and the numpy restatement in
+ * tests/variance_ref.py agree bit for bit.  guide: as hrt_denoise takes it.  The filter shares hrt_denoise's
+ * scratch images; M, the image hrt_reproject_moments writes M' into (swapped with M after the pass, like the
+ * accumulator's) and a staging image for a variance_dst in host memory are the context's own.
+ *
+ * hrt_accumulate_history_moments, hrt_reproject_moments, hrt_fill_moments and hrt_denoise_variance_present are
+ * NON-blocking, ordered on the context's stream after the work issued so far (deferred combines are folded
+ * first).  No fold record, ticket (but hrt_denoise_variance_present's own), counter, trace image or other field
+ * of hrt_stats is touched.
+ *
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued (the message names the reason): everything
+ * hrt_accumulate_history, hrt_reproject, hrt_denoise and hrt_denoise_present reject; iterations above 5;
+ * min_history 0; a sigma or floor that is not finite or not > 0; an unknown method; flags != 0; a too small
+ * variance_bytes or moments destination; a target whose image_id is not HRT_IMG_ACCUM; and a context of a
+ * row-tile partition or one joined to any communicator. */
+
+/* 5 iterations, AUTO, min_history 4 and the default sigmas (DESIGN.md §31 has the grid they were chosen from). */
+void hrt_variance_defaults(hrt_variance_info* info);
+/* hrt_accumulate_history, and M <- the fold of the trace texel's (l, l * l) with the pixel's count. */
+hrt_status hrt_accumulate_history_moments(hrt_context* ctx, uint32_t max_history);
+/* hrt_reproject, and M <- M carried through the same taps; (0, 0) where the pixel is rejected. */
+hrt_status hrt_reproject_moments(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
+                                 const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits);
+/* Every pixel's moments = (m1, m2). */
+hrt_status hrt_fill_moments(hrt_context* ctx, float m1, float m2);
+/* BLOCKING: the moments image, height x width x 2 floats in trace-image row order, to host or device memory at
+ * dst (bytes >= height * width * 8). */
+hrt_status hrt_read_moments(hrt_context* ctx, float* dst, size_t bytes);
+/* BLOCKING, like hrt_denoise: the filtered accumulator in fmt to host or device memory at dst, and, when
+ * variance_dst is not NULL, the filtered variance, height x width floats, to host or device memory there
+ * (variance_bytes >= height * width * 4). */
+hrt_status hrt_denoise_variance(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide, uint32_t fmt,
+                                void* dst, size_t bytes, float* variance_dst, size_t variance_bytes);
+/* NON-blocking: the filter, then hrt_present's pass over the filtered float image, with hrt_denoise_present's
+ * ticket rules.  target->image_id must be HRT_IMG_ACCUM. */
+hrt_status hrt_denoise_variance_present(hrt_context* ctx, const hrt_variance_info* info, const hrt_hit* guide,
+                                        const hrt_present_info* target, void* dst, uint64_t dst_bytes, uint64_t* ticket);
 
 /* ---- the first-hit pass ----
  * The whole image's first hits, NON-blocking: enqueued on the context's stream after the work issued so far, so

@@ -298,6 +298,48 @@ class Context {
     check(hrt_read_history(get(), out.data(), out.size() * sizeof(uint32_t)), "hrt_read_history", get());
     return out;
   }
+  // the variance-guided denoise (hrt_denoise_variance and the moments calls; not a reference feature):
+  // accumulate_history_moments / reproject_moments are accumulate_history / reproject that also carry the moments
+  // image; mixing them with the plain calls leaves stale moments.  They and fill_moments only enqueue;
+  // read_moments and denoise_variance block.
+  static hrt_variance_info variance_defaults() {
+    hrt_variance_info info;
+    hrt_variance_defaults(&info);
+    return info;
+  }
+  void accumulate_history_moments(uint32_t max_history) {
+    check(hrt_accumulate_history_moments(get(), max_history), "hrt_accumulate_history_moments", get());
+  }
+  void reproject_moments(const hrt_view& prev, const hrt_hit* prev_hits, const hrt_view& cur, const hrt_hit* cur_hits,
+                         const hrt_reproject_info* info = nullptr) {
+    const hrt_reproject_info ri = info ? *info : reproject_defaults();
+    check(hrt_reproject_moments(get(), &ri, &prev, prev_hits, &cur, cur_hits), "hrt_reproject_moments", get());
+  }
+  void fill_moments(float m1, float m2) { check(hrt_fill_moments(get(), m1, m2), "hrt_fill_moments", get()); }
+  std::vector<float> read_moments() {
+    std::vector<float> out((size_t)layout_.local_rows * layout_.width * 2);
+    check(hrt_read_moments(get(), out.data(), out.size() * sizeof(float)), "hrt_read_moments", get());
+    return out;
+  }
+  // the filtered accumulator as local_rows x width texels of fmt; variance not null: resized to local_rows x width
+  // floats, the filtered variance
+  std::vector<uint8_t> denoise_variance(const hrt_variance_info& info, const hrt_hit* guide, hrt_format fmt,
+                                        std::vector<float>* variance = nullptr) {
+    const size_t npix = (size_t)layout_.local_rows * layout_.width;
+    std::vector<uint8_t> out(npix * (fmt == HRT_FMT_RGBA8 ? 4 : 16));
+    if (variance) variance->resize(npix);
+    check(hrt_denoise_variance(get(), &info, guide, fmt, out.data(), out.size(), variance ? variance->data() : nullptr,
+                               variance ? npix * sizeof(float) : 0),
+          "hrt_denoise_variance", get());
+    return out;
+  }
+  uint64_t denoise_variance_present(const hrt_variance_info& info, const hrt_hit* guide, const hrt_present_info& target,
+                                    void* dst, uint64_t dst_bytes) {
+    uint64_t ticket = 0;
+    check(hrt_denoise_variance_present(get(), &info, guide, &target, dst, dst_bytes, &ticket),
+          "hrt_denoise_variance_present", get());
+    return ticket;
+  }
   bool present_done(uint64_t ticket) const {
     uint32_t done = 0;
     check(hrt_present_done(get(), ticket, &done), "hrt_present_done", get());
@@ -375,6 +417,19 @@ class RenderPassOverFrame {
     const hrt_present_info pi{(uint32_t)view.id, (uint32_t)target.format, target.width, target.height,
                               target.pitch ? target.pitch : target.width * 4u, 0u};
     return ctx_->denoise_present(dn, guide, pi, target.ptr, target.nbytes);
+  }
+  // render() with the variance-guided denoise between the accumulator and the quad (hrt_denoise_variance_present):
+  // view must be the accumulated image; info null: hrt_variance_defaults.
+  uint64_t render_variance_denoised(const Image& view, const PresentTarget& target, const hrt_hit* guide = nullptr,
+                                    const hrt_variance_info* info = nullptr) {
+    if (view.ctx != ctx_ || view.id != HRT_IMG_ACCUM)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: view must be the accumulated image of the pass's context");
+    if (target.format != format_)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: the target's format differs from the pass's output format");
+    const hrt_variance_info vi = info ? *info : Context::variance_defaults();
+    const hrt_present_info pi{(uint32_t)HRT_IMG_ACCUM, (uint32_t)target.format, target.width, target.height,
+                              target.pitch ? target.pitch : target.width * 4u, 0u};
+    return ctx_->denoise_variance_present(vi, guide, pi, target.ptr, target.nbytes);
   }
 
  private:
@@ -586,10 +641,20 @@ class DiffusePipeline {  // src/diffuse.rs:22-136 (image_combiner.glsl)
   // next_frame with per-pixel frame counts (hrt_accumulate_history; not a reference feature): after a camera
   // move, Context::reproject first, then this -- a pixel whose surface point the old view held keeps its
   // history, the others start again with this frame.
-  void next_frame_history(const Image& next_image, uint32_t max_history = 32) {
+  // moments: also fold the frame's luminance moments (hrt_accumulate_history_moments, with
+  // Context::reproject_moments after a move), what variance_denoised filters by.
+  void next_frame_history(const Image& next_image, uint32_t max_history = 32, bool moments = false) {
     if (next_image.ctx != ctx_ || next_image.id != HRT_IMG_TRACE)
       throw HrtError(HRT_ERR_INVALID_ARGUMENT, "next_frame_history: next_image must be the trace image of the same context");
-    ctx_->accumulate_history(max_history);
+    if (moments)
+      ctx_->accumulate_history_moments(max_history);
+    else
+      ctx_->accumulate_history(max_history);
+  }
+  // The accumulated image through the variance-guided denoise (hrt_denoise_variance; not a reference feature).
+  std::vector<uint8_t> variance_denoised(const hrt_hit* guide = nullptr, hrt_format fmt = HRT_FMT_RGBA8,
+                                         const hrt_variance_info* info = nullptr, std::vector<float>* variance = nullptr) {
+    return ctx_->denoise_variance(info ? *info : Context::variance_defaults(), guide, fmt, variance);
   }
   // The accumulated image through the denoise pass (hrt_denoise; not a reference feature): guide = the view's
   // first hits on the device (RayTracePipeline::first_hits_into) or null for the colour-only filter; info null:

@@ -29,6 +29,10 @@ and writes profiles/present_loop_denoise.jsonl with the ratio e / c (single cont
   h  f with hrt_first_hits (AUTO) into two alternating device buffers in place of the blocking call: every stage
      of the frame is enqueued, the host waits for tickets only
 and writes profiles/present_loop_history.jsonl with f / e, g / e, h / e, f - g and f - h.
+--variance runs two variants of the moving loop only, taking turns in one sitting: h, and
+  i  h with the three moments calls in place of the plain ones: hrt_reproject_moments,
+     hrt_accumulate_history_moments and hrt_denoise_variance_present (the variance-guided filter, defaults)
+and writes profiles/present_loop_variance.jsonl with i / h and i - h.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -46,6 +50,7 @@ sys.path.insert(0, ROOT)
 VARIANTS = ("a", "b", "c", "d")
 DENOISE_VARIANTS = ("c", "e")
 MOVING_VARIANTS = ("e", "f", "g", "h")
+VARIANCE_VARIANTS = ("h", "i")
 MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
@@ -83,14 +88,14 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
-    moving = variant in ("f", "g", "h")
+    moving = variant in ("f", "g", "h", "i")
     if moving:
         import numpy as np
 
         # first hits of the previous and the current view: LAG + 2 buffers, so that one the enqueued passes of
         # the last LAG frames still read is never overwritten
         # (h: two -- its passes are ordered on the stream behind the readers of the buffer they overwrite)
-        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2 if variant == "h" else LAG + 2)]
+        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2 if variant in ("h", "i") else LAG + 2)]
         guide_ctx, guide_rt = ctx, raytraces[0]
         if variant == "g":
             guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
@@ -114,14 +119,19 @@ def child(variant: str, parts: int = 1) -> dict:
         cam = camera_at(frame)
         view = E.View(cam, SIZE, settings)
         prev_hits, cur_hits = guides[(frame - 1) % len(guides)], guides[frame % len(guides)]
-        if variant == "h":
+        if variant in ("h", "i"):
             guide_rt.first_hits_async(cam, cur_hits.data_ptr())
         else:
             guide_rt.first_hits_into(cam, cur_hits.data_ptr())  # blocking
         raytraces[0].compute(cam, frame)
-        ctx.reproject(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
-        diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY)
-        tickets.append(ctx.denoise_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+        if variant == "i":
+            ctx.reproject_moments(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
+            diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY, moments=True)
+            tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+        else:
+            ctx.reproject(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
+            diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY)
+            tickets.append(ctx.denoise_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
         if len(tickets) > LAG:
             ctx.present_wait(tickets[-1 - LAG])
         prev_view = view
@@ -173,7 +183,7 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h"), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
@@ -182,6 +192,8 @@ def main() -> int:
     ap.add_argument("--moving", action="store_true",
                     help="variants e, f (the temporal pipeline with a moving camera), g (f with the first hits "
                          "taken on a second context) and h (f with hrt_first_hits, nothing blocking) only, taking turns")
+    ap.add_argument("--variance", action="store_true",
+                    help="variants h and i (h with the moments calls and the variance-guided filter) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -193,12 +205,13 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    if (a.denoise or a.moving) and a.parts > 1:
-        ap.error("--denoise and --moving run on a single context (a partitioned context cannot denoise or keep history)")
+    if (a.denoise or a.moving or a.variance) and a.parts > 1:
+        ap.error("--denoise, --moving and --variance run on a single context (a partitioned context cannot denoise or keep "
+                 "history)")
     if a.out is None:
-        name = "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        name = "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
         a.out = os.path.join(ROOT, "profiles", name)
-    variants = MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
+    variants = VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
     order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
@@ -223,7 +236,9 @@ def main() -> int:
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
                                "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
-    if a.moving:
+    if a.variance:
+        summary.update(i_over_h=round(med["i"] / med["h"], 4), i_minus_h_ms=round(med["i"] - med["h"], 4))
+    elif a.moving:
         summary.update(f_over_e=round(med["f"] / med["e"], 4), f_minus_e_ms=round(med["f"] - med["e"], 4),
                        g_over_e=round(med["g"] / med["e"], 4), g_minus_e_ms=round(med["g"] - med["e"], 4),
                        f_minus_g_ms=round(med["f"] - med["g"], 4),
