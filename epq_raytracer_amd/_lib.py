@@ -214,6 +214,30 @@ FIRST_HITS_AUTO, FIRST_HITS_TILES, FIRST_HITS_QUERY = 0, 1, 2  # hrt_first_hits_
 FIRST_HITS_NAMES = {0: "auto", 1: "tiles", 2: "query"}
 FIRST_HITS_COUNT = 1  # HRT_FIRST_HITS_COUNT (flags bit 0)
 
+
+
+class RefineRule(ctypes.Structure):
+    """hrt_refine_rule: which pixels a refinement pass selects (32 bytes)."""
+
+    _fields_ = [("min_history", c_uint32), ("max_count", c_uint32), ("radius", c_uint32), ("flags", c_uint32),
+                ("tolerance", c_float), ("luminance_floor", c_float), ("reserved", c_uint32 * 2)]
+
+
+class RefineStats(ctypes.Structure):
+    """hrt_refine_stats: what one hrt_refine pass ran (48 bytes)."""
+
+    _fields_ = [("method_ran", c_uint32), ("query_method_ran", c_uint32), ("selected", c_uint64),
+                ("scan_segments", c_uint64), ("segments", c_uint64), ("tri_tests", c_uint64), ("reserved", c_uint64)]
+
+
+assert ctypes.sizeof(RefineRule) == 32 and ctypes.sizeof(RefineStats) == 48
+REFINE_AUTO, REFINE_QUERIES, REFINE_FRAME = 0, 1, 2  # hrt_refine_method
+REFINE_NAMES = {0: "auto", 1: "queries", 2: "frame"}
+REFINE_MOMENTS = 1  # HRT_REFINE_MOMENTS (flags bit 0 of hrt_refine / hrt_refine_until)
+# HRT_REFINE_MIN_HISTORY / _MAX_COUNT / _RADIUS / _TOLERANCE / _FLOOR (hrt_refine_defaults)
+REFINE_MIN_HISTORY, REFINE_MAX_COUNT, REFINE_RADIUS, REFINE_TOLERANCE, REFINE_FLOOR = 4, 1 << 24, 1, 0.05, 0.01
+REFINE_MAX_RADIUS = 3
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -291,6 +315,7 @@ EXPORTED_SYMBOLS = (
     "hrt_reproject_defaults", "hrt_reproject", "hrt_accumulate_history", "hrt_fill_history", "hrt_read_history",
     "hrt_variance_defaults", "hrt_accumulate_history_moments", "hrt_reproject_moments", "hrt_fill_moments",
     "hrt_read_moments", "hrt_denoise_variance", "hrt_denoise_variance_present",
+    "hrt_refine_defaults", "hrt_refine_select", "hrt_refine", "hrt_refine_until",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -378,6 +403,11 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_accumulate_history": (c_int32, [P, c_uint32]),
         "hrt_fill_history": (c_int32, [P, c_uint32]),
         "hrt_read_history": (c_int32, [P, P, c_size_t]),
+        "hrt_refine_defaults": (None, [POINTER(RefineRule)]),
+        "hrt_refine_select": (c_int32, [P, POINTER(RefineRule), P, P, POINTER(c_uint64)]),
+        "hrt_refine": (c_int32, [P, POINTER(PushConstants), P, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(RefineStats)]),
+        "hrt_refine_until": (c_int32, [P, POINTER(PushConstants), POINTER(RefineRule), P, c_uint32, c_uint32, c_uint32,
+                                       c_uint32, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_uint32)]),
         "hrt_variance_defaults": (None, [POINTER(VarianceInfo)]),
         "hrt_accumulate_history_moments": (c_int32, [P, c_uint32]),
         "hrt_reproject_moments": (c_int32, [P, POINTER(ReprojectInfo), POINTER(View), P, POINTER(View), P]),

@@ -26,6 +26,7 @@
 #include "hrt_denoise.h"
 #include "hrt_history.h"
 #include "hrt_variance.h"
+#include "hrt_refine.h"
 #include "hrt_host.h"
 #include "hrt_image.h"
 #include "hrt_kernels.h"
@@ -500,6 +501,11 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->hist_mom);
   free_dev(ctx, ctx->hist_mom_next);
   free_dev(ctx, ctx->var_stage);
+  free_dev(ctx, ctx->rf_mask);
+  free_dev(ctx, ctx->rf_queries);
+  free_dev(ctx, ctx->rf_index);
+  free_dev(ctx, ctx->rf_rgba);
+  free_dev(ctx, ctx->rf_words);
   free_dev(ctx, ctx->fh_cam_meta);
   free_dev(ctx, ctx->fh_cam_tris);
   free_dev(ctx, ctx->fh_cam_cull);
@@ -2324,6 +2330,245 @@ extern "C" hrt_status hrt_denoise_variance_present(hrt_context* ctx, const hrt_v
   // the filtered float image through the present pass unchanged
   HRT_HIP(ctx, hrt::launch_present(res, true, ctx->width, ctx->local_rows, present_target(target, dst), ctx->stream));
   return ticket_end(ctx, ev, ticket);
+}
+
+// ---- adaptive refinement (kernels in hrt_refine.hip) ------------------------------------
+namespace {
+
+// AUTO: FRAME.  At 1080p, 64 spp (profiles/refine_rate.jsonl) a FRAME pass costs the frame whatever the
+// share -- island 2.9 to 3.2 ms, cave 10.2 to 10.6 -- and a QUERIES pass starts at the latency of one lane's 64 samples
+// (island 5.7 ms at 1 % of the pixels, cave 8.4) and grows with the share: on island FRAME wins at every share
+// measured with the ranges apart, on cave from 10 % on, with the ranges overlapping at 5 % and QUERIES ahead at 1 %
+// (8.4 against 10.3).  No threshold on the share serves both scenes, so AUTO does not look at it.
+constexpr uint32_t kRefineAuto = HRT_REFINE_FRAME;
+
+hrt_status check_refine_rule(hrt_context* ctx, const hrt_refine_rule* rule, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!rule) return bad("null rule");
+  if (rule->flags != 0) return bad("rule flags must be 0");
+  if (rule->min_history == 0) return bad("min_history must be at least 1");
+  if (rule->max_count < rule->min_history) return bad("max_count must be at least min_history");
+  if (rule->radius > HRT_REFINE_MAX_RADIUS) return bad("radius must be 0..3");
+  if (!(std::isfinite(rule->tolerance) && rule->tolerance > 0.0f)) return bad("tolerance must be finite and > 0");
+  if (!(std::isfinite(rule->luminance_floor) && rule->luminance_floor > 0.0f))
+    return bad("luminance_floor must be finite and > 0");
+  return HRT_OK;
+}
+
+// The guide of a selection: NULL, or width x height records of the context's device, 16-byte aligned.
+hrt_status check_refine_guide(hrt_context* ctx, const hrt_hit* guide, const char* who) {
+  if (!guide) return HRT_OK;
+  if ((uintptr_t)guide % 16 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": the guide must be 16-byte aligned");
+  if (!hits_on_device(ctx, guide))
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT,
+                std::string(who) + ": the guide must be width x height records in memory of the context's device");
+  return HRT_OK;
+}
+
+// What hrt_refine checks of its own arguments (hrt_refine_until too, before its first pass).
+hrt_status check_refine(hrt_context* ctx, const hrt_push_constants* pc, uint32_t max_history, uint32_t method,
+                        uint32_t query_method, uint32_t flags, const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!pc) return bad("null push block");
+  if (method > HRT_REFINE_FRAME) return bad("unknown method");
+  if (!known_query_method(query_method)) return bad("unknown query method");
+  if (flags & ~HRT_REFINE_MOMENTS) return bad("flag bits other than HRT_REFINE_MOMENTS");
+  if (max_history == 0 || max_history > hrt::kHistoryMax) return bad("max_history must be 1..2^24");
+  if (pc->init) return bad("pc->init must be 0");
+  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, who);  // (the rejection)
+  return check_dispatch(ctx, pc, who);
+}
+
+size_t refine_mask_words(const hrt_context* ctx) { return (ctx->npix() + 31) / 32; }
+
+// The context's staging mask and its two words.
+hrt_status ensure_refine_words(hrt_context* ctx, const char* who) {
+  void* p = ctx->rf_words;
+  hrt_status st = ensure_staging(ctx, &p, 2 * sizeof(unsigned long long), who);
+  ctx->rf_words = static_cast<unsigned long long*>(p);
+  return st;
+}
+hrt_status ensure_refine_mask(hrt_context* ctx, const char* who) {
+  void* p = ctx->rf_mask;
+  hrt_status st = ensure_staging(ctx, &p, refine_mask_words(ctx) * 4, who);
+  ctx->rf_mask = static_cast<uint32_t*>(p);
+  return st;
+}
+
+// The selection into dmask (device memory), enqueued on ctx->stream; the count lands in rf_words[0].  Every
+// argument has been checked.
+hrt_status enqueue_refine_select(hrt_context* ctx, const hrt_refine_rule* rule, const hrt_hit* guide, uint32_t* dmask,
+                                 const char* who) {
+  hrt_status st = begin_history(ctx, who);
+  if (st != HRT_OK) return st;
+  if ((st = begin_moments(ctx, who)) != HRT_OK) return st;
+  if ((st = ensure_refine_words(ctx, who)) != HRT_OK) return st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  HRT_HIP(ctx, hipMemsetAsync(ctx->rf_words, 0, sizeof(unsigned long long), ctx->stream));
+  const hrt::RefineRuleK k{rule->min_history, rule->max_count, rule->radius, rule->tolerance * rule->tolerance,
+                           rule->luminance_floor};
+  HRT_HIP(ctx, hrt::launch_refine_select(ctx->hist_cnt, ctx->hist_mom, guide, dmask, ctx->rf_words, ctx->width,
+                                         ctx->local_rows, k, ctx->stream));
+  return HRT_OK;
+}
+
+// One refinement pass over dmask (device memory).  Every argument has been checked.
+hrt_status refine_pass(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* dmask, uint32_t max_history,
+                       uint32_t method, uint32_t query_method, uint32_t flags, hrt_refine_stats* stats, const char* who) {
+  const bool moments = (flags & HRT_REFINE_MOMENTS) != 0;
+  const uint32_t np = (uint32_t)ctx->npix();
+  const uint32_t ran = method == HRT_REFINE_AUTO ? kRefineAuto : method;
+  hrt_status st = begin_history(ctx, who);
+  if (st != HRT_OK) return st;
+  if (moments && (st = begin_moments(ctx, who)) != HRT_OK) return st;
+  if ((st = ensure_refine_words(ctx, who)) != HRT_OK) return st;
+  if (ran == HRT_REFINE_QUERIES) {
+    if ((st = ensure_staging(ctx, &ctx->rf_queries, (size_t)np * sizeof(hrt_radiance_query), who)) != HRT_OK) return st;
+    void* p = ctx->rf_index;
+    if ((st = ensure_staging(ctx, &p, (size_t)np * 4, who)) != HRT_OK) return st;
+    ctx->rf_index = static_cast<uint32_t*>(p);
+    if ((st = ensure_staging(ctx, &ctx->rf_rgba, (size_t)np * 16, who)) != HRT_OK) return st;
+    if ((st = ensure_staging(ctx, reinterpret_cast<void**>(&ctx->rad_words), 4 * sizeof(unsigned long long), who)) != HRT_OK)
+      return st;
+  }
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  // the list (QUERIES) or the count alone (FRAME), and the count back to the host
+  uint32_t* next = reinterpret_cast<uint32_t*>(ctx->rf_words + 1);
+  HRT_HIP(ctx, hipMemsetAsync(next, 0, sizeof(unsigned long long), ctx->stream));
+  const bool list = ran == HRT_REFINE_QUERIES;
+  HRT_HIP(ctx, hrt::launch_refine_queries(dmask, ctx->scene.rays, list ? static_cast<float4*>(ctx->rf_queries) : nullptr,
+                                          ctx->rf_index, next, np, pc->cam_pos, pc->rng_offset * 719393u, ctx->stream));
+  uint32_t n = 0;
+  HRT_HIP(ctx, hipMemcpyAsync(&n, next, sizeof n, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) *stats = hrt_refine_stats{0u, 0u, n, 0u, 0u, 0u, 0u};
+  if (n == 0) return HRT_OK;
+  float* mom = moments ? ctx->hist_mom : nullptr;
+  if (list) {
+    hrt::TraceParams p = make_params(ctx, pc, 0);
+    const hrt::QueryPlan plan =
+        hrt::plan_query(hrt::plan_scene(p), query_method == HRT_QUERY_AUTO ? (int)HRT_QUERY_PAIRS : (int)query_method);
+    query_only(p);
+    if (stats) HRT_HIP(ctx, hipMemsetAsync(ctx->rad_words, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    for (uint32_t at = 0; at < n; at += std::min(kQueryLaunch, n - at)) {
+      hrt::RadianceArgs q{};
+      q.queries = static_cast<const float4*>(ctx->rf_queries) + 2 * (size_t)at;
+      q.out = static_cast<float4*>(ctx->rf_rgba) + at;
+      q.stats = stats ? ctx->rad_words : nullptr;
+      q.next = reinterpret_cast<uint32_t*>(ctx->rad_words + 3);
+      q.n = std::min(kQueryLaunch, n - at);
+      HRT_HIP(ctx, hrt::launch_radiance(p, q, plan, ctx->stream));
+    }
+    HRT_HIP(ctx, hrt::launch_refine_fold(ctx->accum, ctx->hist_cnt, mom, ctx->f32(), static_cast<const float4*>(ctx->rf_rgba),
+                                         ctx->rf_index, n, max_history, ctx->stream));
+    unsigned long long counts[3] = {0, 0, 0};
+    if (stats) HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->rad_words, sizeof(counts), hipMemcpyDefault, ctx->stream));
+    HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (stats) *stats = hrt_refine_stats{ran, (uint32_t)plan.method, n, counts[0], counts[1], counts[2], 0u};
+    return HRT_OK;
+  }
+  // FRAME: the frame kernel, then fold_history's lane protocol around the masked fold
+  if ((st = hrt_trace(ctx, pc)) != HRT_OK) return st;
+  const int l = ctx->cur_lane;
+  if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) return st;
+  HRT_HIP(ctx, hrt::launch_refine_fold_image(ctx->accum, hrt::trace_image(ctx), ctx->hist_cnt, mom, ctx->f32(), dmask, np,
+                                             max_history, ctx->stream));
+  if (ctx->cur_slot >= 0) {  // a slot of the deferred combiner's ring: its next trace waits for this fold
+    HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+    ctx->fold_set = true;
+  }
+  if ((st = hrt::release_lane(ctx, l)) != HRT_OK) return st;
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) stats->method_ran = ran;
+  return HRT_OK;
+}
+
+}  // namespace
+
+extern "C" void hrt_refine_defaults(hrt_refine_rule* rule) {
+  if (!rule) return;
+  *rule = hrt_refine_rule{HRT_REFINE_MIN_HISTORY, HRT_REFINE_MAX_COUNT, HRT_REFINE_RADIUS, 0u,
+                          HRT_REFINE_TOLERANCE,   HRT_REFINE_FLOOR,     {0u, 0u}};
+}
+
+extern "C" hrt_status hrt_refine_select(hrt_context* ctx, const hrt_refine_rule* rule, const hrt_hit* guide, uint32_t* mask,
+                                        uint64_t* selected) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_refine_select";
+  hrt_status st = check_refine_rule(ctx, rule, who);
+  if (st != HRT_OK) return st;
+  if (!mask) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_select: null mask");
+  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, who);  // (the rejection)
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  if ((st = check_refine_guide(ctx, guide, who)) != HRT_OK) return st;
+  const size_t words = refine_mask_words(ctx);
+  const bool direct = query_direct(ctx, mask);
+  if (direct && (uintptr_t)mask % 4 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_select: a device mask must be 4-byte aligned");
+  if (!direct && (st = ensure_refine_mask(ctx, who)) != HRT_OK) return st;
+  if ((st = enqueue_refine_select(ctx, rule, guide, direct ? mask : ctx->rf_mask, who)) != HRT_OK) return st;
+  if (direct && !selected) return HRT_OK;
+  if (!direct) HRT_HIP(ctx, hipMemcpyAsync(mask, ctx->rf_mask, words * 4, hipMemcpyDefault, ctx->stream));
+  unsigned long long count = 0;
+  HRT_HIP(ctx, hipMemcpyAsync(&count, ctx->rf_words, sizeof count, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (selected) *selected = count;
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_refine(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* mask, uint32_t max_history,
+                                 uint32_t method, uint32_t query_method, uint32_t flags, hrt_refine_stats* stats) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_refine";
+  hrt_status st = check_refine(ctx, pc, max_history, method, query_method, flags, who);
+  if (st != HRT_OK) return st;
+  if (!mask) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine: null mask");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  const bool direct = query_direct(ctx, mask);
+  if (direct && (uintptr_t)mask % 4 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine: a device mask must be 4-byte aligned");
+  if (!direct) {
+    if ((st = ensure_refine_mask(ctx, who)) != HRT_OK) return st;
+    HRT_HIP(ctx, hipMemcpyAsync(ctx->rf_mask, mask, refine_mask_words(ctx) * 4, hipMemcpyDefault, ctx->stream));
+  }
+  return refine_pass(ctx, pc, direct ? mask : ctx->rf_mask, max_history, method, query_method, flags, stats, who);
+}
+
+extern "C" hrt_status hrt_refine_until(hrt_context* ctx, const hrt_push_constants* pc, const hrt_refine_rule* rule,
+                                       const hrt_hit* guide, uint32_t max_history, uint32_t max_passes, uint32_t method,
+                                       uint32_t flags, uint32_t* passes_done, uint64_t* pixel_frames, uint32_t* settled) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_refine_until";
+  if (!passes_done || !pixel_frames)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_until: null passes_done or pixel_frames");
+  hrt_status st = check_refine_rule(ctx, rule, who);
+  if (st != HRT_OK) return st;
+  if ((st = check_refine(ctx, pc, max_history, method, HRT_QUERY_AUTO, flags, who)) != HRT_OK) return st;
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  if ((st = check_refine_guide(ctx, guide, who)) != HRT_OK) return st;
+  if ((st = ensure_refine_mask(ctx, who)) != HRT_OK) return st;
+  *passes_done = 0;
+  *pixel_frames = 0;
+  if (settled) *settled = 0;
+  hrt_push_constants frame = *pc;
+  for (uint32_t k = 0; k < max_passes; ++k) {
+    if ((st = enqueue_refine_select(ctx, rule, guide, ctx->rf_mask, who)) != HRT_OK) return st;
+    unsigned long long count = 0;
+    HRT_HIP(ctx, hipMemcpyAsync(&count, ctx->rf_words, sizeof count, hipMemcpyDefault, ctx->stream));
+    HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (count == 0) {
+      if (settled) *settled = 1;
+      break;
+    }
+    frame.rng_offset = pc->rng_offset + k;
+    if ((st = refine_pass(ctx, &frame, ctx->rf_mask, max_history, method, HRT_QUERY_AUTO, flags | HRT_REFINE_MOMENTS, nullptr,
+                          who)) != HRT_OK)
+      return st;
+    *passes_done = k + 1;
+    *pixel_frames += count;
+  }
+  return HRT_OK;
 }
 
 extern "C" hrt_status hrt_present_done(hrt_context* ctx, uint64_t ticket, uint32_t* done) {

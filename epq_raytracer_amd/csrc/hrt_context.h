@@ -247,6 +247,15 @@ struct hrt_context {
   float* hist_mom = nullptr;
   float* hist_mom_next = nullptr;
   float* var_stage = nullptr;
+  // The adaptive refinement (hrt_refine_select, hrt_refine, hrt_refine_until): the mask's staging (one bit per pixel)
+  // for a mask in host memory and for hrt_refine_until's own; the compact lists of a QUERIES pass (npix entries:
+  // hrt_radiance_query records, pixel indices, results); and two 64-bit words: the selected count, then the
+  // list's entry counter.  Each is allocated by the first call that needs it
+  uint32_t* rf_mask = nullptr;
+  void* rf_queries = nullptr;
+  uint32_t* rf_index = nullptr;
+  void* rf_rgba = nullptr;
+  unsigned long long* rf_words = nullptr;
   // The first-hit pass (hrt_first_hits): its own camera buffers (a fourth set beside the lanes', the scene's
   // sizes), allocated by the first TILES call and dropped by hrt_set_scene; fh_key = the camera position's bits
   // and num_meshes the records were built for (fh_ready: by a launch already enqueued on `stream`); the device

@@ -1,0 +1,45 @@
+// hrt_refine.h -- launch interface of the adaptive refinement (hrt_refine.hip): the
+// selection of the pixels whose estimate is still noisy (hrt_refine_select), and the pieces of one refinement
+// pass over a selection mask (hrt_refine): the compact list of radiance queries, the fold of their results into
+// the selected pixels, and the masked fold of a whole traced frame.
+//
+// The mask is hrt_occluded's layout over i = x + y W: pixel i is bit i & 31 of word i >> 5, ceil(npix / 32) words.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "hip_raytrace.h"
+
+namespace hrt {
+
+// What the selection kernel takes of an hrt_refine_rule: tol2 = tolerance * tolerance, one rounded product.
+struct RefineRuleK {
+  uint32_t min_history, max_count, radius;
+  float tol2, luminance_floor;
+};
+
+// mask <- S17's selection over a w x h image from the count image, the moments image and, when hits is not null,
+// the surface keys of w x h hrt_hit records (16-byte aligned); every word written in full, the unused high bits of
+// the last word 0.  *selected (zeroed by the caller) += the number of selected pixels.
+hipError_t launch_refine_select(const uint32_t* cnt, const float* mom, const hrt_hit* hits, uint32_t* mask,
+                                unsigned long long* selected, uint32_t w, uint32_t h, const RefineRuleK& rule,
+                                hipStream_t stream);
+
+// The selected pixels of mask as a compact list: entry e holds the pixel index[e] = i and its radiance query
+// queries[2 e], queries[2 e + 1] = (cam_pos, seed_base + i), (ray centre i, 0).  *next (zeroed by the caller)
+// += the entries.  queries == null: the count alone.  The order of the entries is free.  Lists: npix entries.
+hipError_t launch_refine_queries(const uint32_t* mask, const float4* rays, float4* queries, uint32_t* index,
+                                 uint32_t* next, uint32_t npix, const float cam_pos[3], uint32_t seed_base,
+                                 hipStream_t stream);
+
+// For every entry e < n: the texel of rgba[e] (in RGBA8 mode through S7's store, alpha 255) folded into pixel
+// index[e] of cur / cnt (/ mom when not null) as launch_fold_history[_moments] folds a trace texel.
+hipError_t launch_refine_fold(void* cur, uint32_t* cnt, float* mom, bool f32, const float4* rgba, const uint32_t* index,
+                              uint32_t n, uint32_t max_history, hipStream_t stream);
+
+// launch_fold_history[_moments] for the pixels whose bit is set in mask; every other pixel is left alone.
+hipError_t launch_refine_fold_image(void* cur, const void* nw, uint32_t* cnt, float* mom, bool f32, const uint32_t* mask,
+                                    uint32_t npix, uint32_t max_history, hipStream_t stream);
+
+}  // namespace hrt

@@ -397,6 +397,74 @@ class HrtContext:
         self.read_history_into(out.ctypes.data, out.nbytes)
         return out
 
+    # ---- adaptive refinement (hrt_refine_select, hrt_refine, hrt_refine_until) ----
+
+    @property
+    def mask_words(self) -> int:
+        """The uint32 words of a selection mask: one bit per pixel, pixel i = x + y W in bit i & 31 of word i >> 5."""
+        return (self.local_rows * self.width + 31) // 32
+
+    def refine_rule(self, min_history: Optional[int] = None, max_count: Optional[int] = None,
+                    radius: Optional[int] = None, tolerance: Optional[float] = None,
+                    luminance_floor: Optional[float] = None) -> _lib.RefineRule:
+        """hrt_refine_defaults with the given fields replaced (None: the default)."""
+        rule = _lib.RefineRule()
+        self.lib.hrt_refine_defaults(ctypes.byref(rule))
+        for name, v in (("min_history", min_history), ("max_count", max_count), ("radius", radius)):
+            if v is not None:
+                setattr(rule, name, int(v))
+        for name, v in (("tolerance", tolerance), ("luminance_floor", luminance_floor)):
+            if v is not None:
+                setattr(rule, name, float(v))
+        return rule
+
+    def refine_select_into(self, mask_ptr: int, guide_ptr: Optional[int] = None, want_count: bool = True,
+                           rule: Optional[_lib.RefineRule] = None, **fields) -> Optional[int]:
+        """hrt_refine_select into caller memory (host or 4-byte aligned device pointer, ``mask_words`` words): the
+        pixels whose pooled standard error is above the rule's tolerance.  guide_ptr as
+        ``denoise_into`` takes it.  Returns the number selected; want_count False with a device mask only enqueues."""
+        rule = rule if rule is not None else self.refine_rule(**fields)
+        n = ctypes.c_uint64()
+        self._check(self.lib.hrt_refine_select(self.handle, ctypes.byref(rule), ctypes.c_void_p(guide_ptr or 0),
+                                               ctypes.c_void_p(mask_ptr), ctypes.byref(n) if want_count else None),
+                    "hrt_refine_select")
+        return n.value if want_count else None
+
+    def refine_select(self, guide_ptr: Optional[int] = None, rule: Optional[_lib.RefineRule] = None, **fields):
+        """hrt_refine_select: (mask as uint32 (mask_words,), the number of selected pixels)."""
+        mask = np.empty(self.mask_words, dtype=np.uint32)
+        n = self.refine_select_into(mask.ctypes.data, guide_ptr, True, rule, **fields)
+        return mask, n
+
+    def refine(self, pc: _lib.PushConstants, mask, max_history: int, method: int = _lib.REFINE_AUTO,
+               query_method: int = 0, moments: bool = True, want_stats: bool = True) -> Optional[_lib.RefineStats]:
+        """hrt_refine: one new sample of frame ``pc`` for every pixel set in ``mask`` (a uint32 array in host memory or
+        an int device pointer), folded as ``accumulate_history[_moments]`` folds it; the other pixels keep their
+        bytes.  Blocking."""
+        if isinstance(mask, np.ndarray):
+            mask = np.ascontiguousarray(mask, dtype=np.uint32)
+            assert mask.size >= self.mask_words
+            ptr = mask.ctypes.data
+        else:
+            ptr = int(mask)
+        st = _lib.RefineStats()
+        self._check(self.lib.hrt_refine(self.handle, ctypes.byref(pc), ctypes.c_void_p(ptr), int(max_history), int(method),
+                                        int(query_method), _lib.REFINE_MOMENTS if moments else 0,
+                                        ctypes.byref(st) if want_stats else None), "hrt_refine")
+        return st if want_stats else None
+
+    def refine_until(self, pc: _lib.PushConstants, max_history: int, max_passes: int, guide_ptr: Optional[int] = None,
+                     method: int = _lib.REFINE_AUTO, rule: Optional[_lib.RefineRule] = None, **fields):
+        """hrt_refine_until: select-and-refine passes with rng_offset pc.rng_offset, + 1, ... until nothing is
+        selected or max_passes have run.  Returns (passes done, pixel-frames traced, settled)."""
+        rule = rule if rule is not None else self.refine_rule(**fields)
+        passes, frames, settled = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self.lib.hrt_refine_until(self.handle, ctypes.byref(pc), ctypes.byref(rule),
+                                              ctypes.c_void_p(guide_ptr or 0), int(max_history), int(max_passes),
+                                              int(method), _lib.REFINE_MOMENTS, ctypes.byref(passes), ctypes.byref(frames),
+                                              ctypes.byref(settled)), "hrt_refine_until")
+        return passes.value, frames.value, bool(settled.value)
+
     # ---- the variance-guided denoise (hrt_denoise_variance and the moments calls) ----
 
     def variance_info(self, iterations: Optional[int] = None, method: int = _lib.VARIANCE_AUTO,
@@ -915,6 +983,19 @@ class DiffusePipeline:
             self.ctx.accumulate_history_moments(max_history)
         else:
             self.ctx.accumulate_history(max_history)
+
+    def refine_until(self, pipeline: "RayTracePipeline", camera: "Camera", first_frame: int, max_passes: int,
+                     max_history: int = 1 << 24, guide_ptr: Optional[int] = None, method: int = _lib.REFINE_AUTO,
+                     **rule):
+        """Adaptive refinement of the accumulated image (hrt_refine_until; not a reference feature): passes of new
+        samples for the pixels whose estimate is still noisy, with the frames ``first_frame``, + 1, ... of
+        ``pipeline`` under ``camera`` -- frames beyond those the history already holds (``next_frame_history`` with
+        moments=True).  ``rule``: the fields of ``HrtContext.refine_rule``.  Returns (passes done, pixel-frames
+        traced, settled)."""
+        if pipeline.ctx is not self.ctx:
+            raise ValueError("pipeline must trace on the same context")
+        return self.ctx.refine_until(pipeline.push_constants(camera, first_frame, False), max_history, max_passes,
+                                     guide_ptr, method, **rule)
 
     def variance_denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **fields) -> np.ndarray:
         """The accumulated image through the variance-guided denoise (hrt_denoise_variance), as uint8 or float32

@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): the variance-guided denoise -- hrt_variance_method,
+/* 6, additive (no bump: nothing existing changed): adaptive refinement -- hrt_refine_rule, hrt_refine_method,
+ * HRT_REFINE_MOMENTS, hrt_refine_stats, hrt_refine_defaults, hrt_refine_select, hrt_refine, hrt_refine_until.
+ * 6, additive (no bump: nothing existing changed): the variance-guided denoise -- hrt_variance_method,
  * hrt_variance_info, hrt_variance_defaults, hrt_accumulate_history_moments, hrt_reproject_moments, hrt_fill_moments,
  * hrt_read_moments, hrt_denoise_variance, hrt_denoise_variance_present.
  * 6, additive (no bump: nothing existing changed): the first-hit pass -- hrt_first_hits_method,
@@ -389,6 +391,42 @@ typedef struct hrt_first_hits_stats { /* 48 bytes: the last call that had HRT_FI
   uint64_t entries_tested;  /* list entries that reached the exact test, summed over waves */
 } hrt_first_hits_stats;
 
+/* ---- adaptive refinement (hrt_refine_select, hrt_refine, hrt_refine_until) ---- */
+/* hrt_refine_defaults' parameters: design parameters chosen on the CPU oracle's frames */
+#define HRT_REFINE_TOLERANCE 0.05f
+#define HRT_REFINE_RADIUS 1u
+#define HRT_REFINE_MIN_HISTORY 4u
+#define HRT_REFINE_FLOOR 0.01f
+#define HRT_REFINE_MAX_COUNT 16777216u /* 2^24 = HRT_HISTORY_MAX: no per-pixel budget */
+#define HRT_REFINE_MAX_RADIUS 3u
+
+typedef struct hrt_refine_rule { /* 32 bytes */
+  uint32_t min_history;  /* >= 1: a pixel with fewer frames is always selected; a tap with fewer is skipped */
+  uint32_t max_count;    /* >= min_history: a pixel with this many frames is never selected (its budget) */
+  uint32_t radius;       /* 0..3: the criterion pools the (2 radius + 1)^2 window's pixels of the same surface */
+  uint32_t flags;        /* must be 0 */
+  float tolerance;       /* finite, > 0: the relative standard error of the mean a pixel is refined down to */
+  float luminance_floor; /* finite, > 0: the pooled mean luminance is not taken below this */
+  uint32_t reserved[2];  /* ignored */
+} hrt_refine_rule;
+
+typedef enum hrt_refine_method {
+  HRT_REFINE_AUTO = 0,    /* FRAME: it measured faster on island at every share, on cave from 10 % on */
+  HRT_REFINE_QUERIES = 1, /* the selected pixels as a compact list of radiance queries (hrt_radiance's kernels) */
+  HRT_REFINE_FRAME = 2    /* hrt_trace of the whole frame, folded into the selected pixels only */
+} hrt_refine_method;
+#define HRT_REFINE_MOMENTS 1u /* hrt_refine / hrt_refine_until flags bit 0: fold the moments image M too */
+
+typedef struct hrt_refine_stats { /* 48 bytes */
+  uint32_t method_ran;       /* hrt_refine_method that ran (AUTO resolved; 0 when nothing was selected) */
+  uint32_t query_method_ran; /* QUERIES: the hrt_query_method that ran, as hrt_radiance_stats; else 0 */
+  uint64_t selected;         /* pixels whose bit is set in the mask */
+  uint64_t scan_segments;    /* QUERIES: as hrt_radiance_stats; FRAME: 0 (the frame counts in hrt_stats) */
+  uint64_t segments;
+  uint64_t tri_tests;
+  uint64_t reserved;         /* 0 */
+} hrt_refine_stats;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -459,6 +497,16 @@ HRT_STATIC_ASSERT(sizeof(hrt_reproject_info) == 32 && offsetof(hrt_reproject_inf
                       offsetof(hrt_reproject_info, depth_tolerance) == 8 &&
                       offsetof(hrt_reproject_info, min_normal_dot) == 12 && offsetof(hrt_reproject_info, reserved) == 16,
                   "hrt_reproject_info");
+HRT_STATIC_ASSERT(sizeof(hrt_refine_rule) == 32 && offsetof(hrt_refine_rule, max_count) == 4 &&
+                      offsetof(hrt_refine_rule, radius) == 8 && offsetof(hrt_refine_rule, flags) == 12 &&
+                      offsetof(hrt_refine_rule, tolerance) == 16 && offsetof(hrt_refine_rule, luminance_floor) == 20 &&
+                      offsetof(hrt_refine_rule, reserved) == 24,
+                  "hrt_refine_rule");
+HRT_STATIC_ASSERT(sizeof(hrt_refine_stats) == 48 && offsetof(hrt_refine_stats, query_method_ran) == 4 &&
+                      offsetof(hrt_refine_stats, selected) == 8 && offsetof(hrt_refine_stats, scan_segments) == 16 &&
+                      offsetof(hrt_refine_stats, segments) == 24 && offsetof(hrt_refine_stats, tri_tests) == 32 &&
+                      offsetof(hrt_refine_stats, reserved) == 40,
+                  "hrt_refine_stats");
 HRT_STATIC_ASSERT(sizeof(hrt_first_hits_stats) == 48 && offsetof(hrt_first_hits_stats, reserved) == 4 &&
                       offsetof(hrt_first_hits_stats, tiles) == 8 && offsetof(hrt_first_hits_stats, tiles_listed) == 12 &&
                       offsetof(hrt_first_hits_stats, tiles_empty) == 16 &&
@@ -1107,6 +1155,64 @@ hrt_status hrt_denoise_variance_present(hrt_context* ctx, const hrt_variance_inf
  * partition or one joined to any communicator (the rule of the pass's consumers). */
 hrt_status hrt_first_hits(hrt_context* ctx, const hrt_push_constants* pc, uint32_t method, uint32_t flags, hrt_hit* hits);
 hrt_status hrt_get_first_hits_stats(hrt_context* ctx, hrt_first_hits_stats* out);
+
+/* ---- adaptive refinement (DESIGN.md §2 S17 pins the arithmetic, §32 the kernels) ----------------------------
+ * New frames only for the pixels whose estimate is still noisy.  hrt_refine_select reads the count image N, the
+ * moments image M (both allocated and zeroed by the first call that needs them, as the history calls do) and an
+ * optional guide, and marks pixel p with n = N(p):
+ *     n >= max_count                  -> not selected (the pixel's budget);
+ *     else n < min_history            -> selected (no usable estimate yet);
+ *     else                               selected iff  a > tolerance^2 * max(b, luminance_floor)^2,
+ * where a is the mean over the window's kept taps q of max(m2(q) - m1(q)^2, 0) / N(q) -- the squared standard
+ * error of q's mean luminance -- and b the mean of their m1(q); a tap is kept when it lies inside the image, on
+ * p's surface (S14's key of the guide's records; without a guide every key is 0) and has N(q) >= min_history.
+ * Pooling keeps a pixel whose own first samples happened to agree (variance 0) in the selection while its
+ * neighbours on the surface are noisy.  The mask has hrt_occluded's layout over i = x + y * width: pixel i is bit
+ * i & 31 of word i >> 5, ceil(width * height / 32) words, each written in full, the unused bits of the last 0.
+ *
+ * hrt_refine runs one pass over a mask: for every selected pixel p, with t(p) the texel hrt_trace(ctx, pc) stores
+ * at p (the radiance query (pc->cam_pos, pc->rng_offset * 719393 + i, ray centre i) of hrt_radiance, in RGBA8
+ * mode through the UNORM8 store), the accumulator, N and -- with HRT_REFINE_MOMENTS -- M at p become exactly
+ * what hrt_accumulate_history[_moments](max_history) makes of them from t(p); every other pixel keeps its bytes.
+ * Bits of the last word beyond the image are ignored.  HRT_REFINE_QUERIES traces the selected pixels alone, as a
+ * compact list through hrt_radiance's kernels (query_method: hrt_query_method, AUTO as hrt_radiance resolves it),
+ * and touches no trace lane, trace image, hrt_stats, counter, fold record or ticket.  HRT_REFINE_FRAME is
+ * hrt_trace(ctx, pc) -- the frame is left in the trace image and counts in hrt_stats as hrt_trace's -- followed
+ * by the masked fold (hrt_stats.accumulates does not count it).  Both give the same accumulator, N and M.
+ * BLOCKING: the number of selected pixels comes back to the host to size the launches.  Ordered on the context's
+ * stream after the work issued so far (deferred combines are folded first).  With nothing selected nothing is
+ * traced and nothing changes (stats: selected 0, method_ran 0).
+ *
+ * hrt_refine_until: pass k = 0, 1, ... < max_passes selects with the rule; when nothing is selected it stops with
+ * *settled = 1; else it refines with pc's rng_offset + k and HRT_REFINE_MOMENTS forced on (the rule reads M).
+ * *passes_done = the refinement passes run, *pixel_frames = the sum of their selected counts; settled may be
+ * NULL.  The caller chooses pc->rng_offset beyond the frames the history already holds (not policed: a repeated
+ * offset folds a sample twice).  BLOCKING.  With HRT_REFINE_AUTO or HRT_REFINE_FRAME the passes' frames go through the
+ * trace image and hrt_stats as hrt_trace's do; HRT_REFINE_QUERIES leaves both alone.
+ *
+ * mask: host memory, or memory of the context's device (then 4-byte aligned).  guide: NULL, or width x height
+ * hrt_hit records in memory of the context's device, 16-byte aligned (what hrt_first_hits writes).
+ * hrt_refine_select with selected == NULL and a device mask is NON-blocking (stream-ordered); otherwise BLOCKING.
+ * The calls' buffers (mask staging, the query, index and result lists: 52 bytes per pixel) belong to the context,
+ * are allocated by the first call that needs them and freed by hrt_destroy.
+ *
+ * HRT_ERR_NO_SCENE without a scene (hrt_refine, hrt_refine_until).  Rejected with HRT_ERR_INVALID_ARGUMENT before
+ * anything is enqueued (the message names the reason): a NULL argument (but the optional ones); an unknown
+ * method or query method; flag bits beyond HRT_REFINE_MOMENTS; rule->flags != 0; min_history 0; max_count below
+ * min_history; radius above 3; a tolerance or floor that is not finite or not > 0; max_history 0 or above
+ * HRT_HISTORY_MAX; pc->init; a push block whose size or counts the context does not hold; a misaligned device
+ * pointer; a guide that is not memory of the context's device; and a context of a row-tile partition or one
+ * joined to any communicator, as the history calls reject them. */
+
+/* min_history 4, max_count 2^24, radius 1, tolerance 0.05, luminance_floor 0.01 (DESIGN.md §32 has the grid). */
+void hrt_refine_defaults(hrt_refine_rule* rule);
+hrt_status hrt_refine_select(hrt_context* ctx, const hrt_refine_rule* rule, const hrt_hit* guide, uint32_t* mask,
+                             uint64_t* selected);
+hrt_status hrt_refine(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* mask, uint32_t max_history,
+                      uint32_t method, uint32_t query_method, uint32_t flags, hrt_refine_stats* stats);
+hrt_status hrt_refine_until(hrt_context* ctx, const hrt_push_constants* pc, const hrt_refine_rule* rule,
+                            const hrt_hit* guide, uint32_t max_history, uint32_t max_passes, uint32_t method,
+                            uint32_t flags, uint32_t* passes_done, uint64_t* pixel_frames, uint32_t* settled);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

@@ -340,6 +340,46 @@ class Context {
           "hrt_denoise_variance_present", get());
     return ticket;
   }
+  // adaptive refinement (hrt_refine_select, hrt_refine, hrt_refine_until; not a reference feature): new samples
+  // only for the pixels whose estimate is still noisy.  A mask is one bit per pixel, pixel i = x + y width in bit
+  // i & 31 of word i >> 5.  guide: null, or the view's first hits on the device.  All three block.
+  static hrt_refine_rule refine_defaults() {
+    hrt_refine_rule rule;
+    hrt_refine_defaults(&rule);
+    return rule;
+  }
+  size_t mask_words() const { return ((size_t)layout_.local_rows * layout_.width + 31) / 32; }
+  // the selection mask in host memory; selected not null: the number of pixels set
+  std::vector<uint32_t> refine_select(const hrt_refine_rule& rule, const hrt_hit* guide = nullptr,
+                                      uint64_t* selected = nullptr) {
+    std::vector<uint32_t> mask(mask_words());
+    uint64_t n = 0;
+    check(hrt_refine_select(get(), &rule, guide, mask.data(), &n), "hrt_refine_select", get());
+    if (selected) *selected = n;
+    return mask;
+  }
+  // one pass over a mask in host or device memory (mask_words() words)
+  hrt_refine_stats refine(const hrt_push_constants& pc, const uint32_t* mask, uint32_t max_history,
+                          uint32_t method = HRT_REFINE_AUTO, uint32_t query_method = HRT_QUERY_AUTO, bool moments = true) {
+    hrt_refine_stats st{};
+    check(hrt_refine(get(), &pc, mask, max_history, method, query_method, moments ? HRT_REFINE_MOMENTS : 0u, &st),
+          "hrt_refine", get());
+    return st;
+  }
+  struct RefineResult {
+    uint32_t passes;
+    uint64_t pixel_frames;
+    bool settled;
+  };
+  RefineResult refine_until(const hrt_push_constants& pc, const hrt_refine_rule& rule, const hrt_hit* guide,
+                            uint32_t max_history, uint32_t max_passes, uint32_t method = HRT_REFINE_AUTO) {
+    uint32_t passes = 0, settled = 0;
+    uint64_t frames = 0;
+    check(hrt_refine_until(get(), &pc, &rule, guide, max_history, max_passes, method, HRT_REFINE_MOMENTS, &passes, &frames,
+                           &settled),
+          "hrt_refine_until", get());
+    return RefineResult{passes, frames, settled != 0};
+  }
   bool present_done(uint64_t ticket) const {
     uint32_t done = 0;
     check(hrt_present_done(get(), ticket, &done), "hrt_present_done", get());
@@ -650,6 +690,17 @@ class DiffusePipeline {  // src/diffuse.rs:22-136 (image_combiner.glsl)
       ctx_->accumulate_history_moments(max_history);
     else
       ctx_->accumulate_history(max_history);
+  }
+  // Adaptive refinement of the accumulated image (hrt_refine_until; not a reference feature): passes of new samples
+  // for the pixels whose estimate is still noisy, with the frames first_frame, + 1, ... of `pipeline` under `camera`
+  // -- frames beyond those the history already holds (next_frame_history with moments).  rule null:
+  // hrt_refine_defaults.
+  Context::RefineResult refine_until(const RayTracePipeline& pipeline, const Camera& camera, uint32_t first_frame,
+                                     uint32_t max_passes, uint32_t max_history = HRT_HISTORY_MAX,
+                                     const hrt_hit* guide = nullptr, uint32_t method = HRT_REFINE_AUTO,
+                                     const hrt_refine_rule* rule = nullptr) {
+    return ctx_->refine_until(pipeline.push_constants(camera, first_frame, false), rule ? *rule : Context::refine_defaults(),
+                              guide, max_history, max_passes, method);
   }
   // The accumulated image through the variance-guided denoise (hrt_denoise_variance; not a reference feature).
   std::vector<uint8_t> variance_denoised(const hrt_hit* guide = nullptr, hrt_format fmt = HRT_FMT_RGBA8,
