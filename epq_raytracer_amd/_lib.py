@@ -238,6 +238,17 @@ REFINE_MOMENTS = 1  # HRT_REFINE_MOMENTS (flags bit 0 of hrt_refine / hrt_refine
 REFINE_MIN_HISTORY, REFINE_MAX_COUNT, REFINE_RADIUS, REFINE_TOLERANCE, REFINE_FLOOR = 4, 1 << 24, 1, 0.05, 0.01
 REFINE_MAX_RADIUS = 3
 
+
+class RefineTilesStats(ctypes.Structure):
+    """hrt_refine_tiles_stats: what one hrt_refine_tiles pass ran (40 bytes)."""
+
+    _fields_ = [("kernel_ran", c_uint32), ("whole_frame", c_uint32), ("tiles", c_uint32), ("tiles_selected", c_uint32),
+                ("items", c_uint32), ("reserved", c_uint32), ("selected", c_uint64), ("pixels_traced", c_uint64)]
+
+
+assert ctypes.sizeof(RefineTilesStats) == 40
+REFINE_TILES_MAX_FRAMES = 4096  # HRT_REFINE_TILES_MAX_FRAMES
+
 ABI_VERSION = 6  # HRT_ABI_VERSION this binding's signatures describe
 TILE_LIST_WORDS = 66  # hrt_debug_tile_lists: n, ok, 64 entries per tile
 HRT_OK = 0
@@ -316,6 +327,7 @@ EXPORTED_SYMBOLS = (
     "hrt_variance_defaults", "hrt_accumulate_history_moments", "hrt_reproject_moments", "hrt_fill_moments",
     "hrt_read_moments", "hrt_denoise_variance", "hrt_denoise_variance_present",
     "hrt_refine_defaults", "hrt_refine_select", "hrt_refine", "hrt_refine_until",
+    "hrt_refine_tiles", "hrt_refine_tiles_until",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -408,6 +420,9 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_refine": (c_int32, [P, POINTER(PushConstants), P, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(RefineStats)]),
         "hrt_refine_until": (c_int32, [P, POINTER(PushConstants), POINTER(RefineRule), P, c_uint32, c_uint32, c_uint32,
                                        c_uint32, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_uint32)]),
+        "hrt_refine_tiles": (c_int32, [P, POINTER(PushConstants), P, c_uint32, c_uint32, c_uint32, POINTER(RefineTilesStats)]),
+        "hrt_refine_tiles_until": (c_int32, [P, POINTER(PushConstants), POINTER(RefineRule), P, c_uint32, c_uint32, c_uint32,
+                                             c_uint32, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_uint32)]),
         "hrt_variance_defaults": (None, [POINTER(VarianceInfo)]),
         "hrt_accumulate_history_moments": (c_int32, [P, c_uint32]),
         "hrt_reproject_moments": (c_int32, [P, POINTER(ReprojectInfo), POINTER(View), P, POINTER(View), P]),

@@ -506,6 +506,11 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->rf_index);
   free_dev(ctx, ctx->rf_rgba);
   free_dev(ctx, ctx->rf_words);
+  free_dev(ctx, ctx->rt_bits);
+  free_dev(ctx, ctx->rt_counts);
+  free_dev(ctx, ctx->rt_sched);
+  free_dev(ctx, ctx->rt_items);
+  free_dev(ctx, ctx->rt_cost);
   free_dev(ctx, ctx->fh_cam_meta);
   free_dev(ctx, ctx->fh_cam_tris);
   free_dev(ctx, ctx->fh_cam_cull);
@@ -887,8 +892,10 @@ hrt::TraceParams make_params(hrt_context* ctx, const hrt_push_constants* pc, int
 }
 
 // One trace launch of p.n_frames frames on `stream` with lane l's planner buffers (timed by a HIP
-// event pair counted as that many traces).
-hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stream, int l) {
+// event pair counted as that many traces).  masked: a tile-masked launch of a persistent kernel (hrt_refine_tiles):
+// no probe, and the lane's costs and plan_valid stay as they are.
+hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stream, int l,
+                         const hrt::MaskedPlan* masked = nullptr) {
   if (ctx->diag_on)
     HRT_HIP(ctx, hipMemsetAsync(ctx->tile_cycles, 0, ctx->num_tiles() * 4 * sizeof(unsigned long long), stream));
   if (ctx->timeline) HRT_HIP(ctx, hipMemsetAsync(ctx->timeline_count, 0, sizeof(uint32_t), stream));  // this launch's
@@ -929,7 +936,7 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
   // First trace of a persistent kernel on this lane (no tile costs yet): a 1-sample probe trace into the
   // lane's own image (fully overwritten by the trace that follows on the same stream) measures the
   // tiles' relative costs so that this trace already follows a plan (HRT_OPT_PROBE).
-  if (ctx->probe && !lane.plan_valid && ctx->num_tiles() >= 1024 && kernel.persistent) {
+  if (ctx->probe && !lane.plan_valid && ctx->num_tiles() >= 1024 && kernel.persistent && !masked) {
     hrt::TraceParams q = p;
     q.pc.num_samples = 1;
     q.n_frames = 1;
@@ -988,10 +995,10 @@ hrt_status launch_frames(hrt_context* ctx, hrt::TraceParams& p, hipStream_t stre
   HRT_HIP(ctx, hipEventRecord(ev.start, stream));
   ctx->last_kernel = plan.kernel;
   ctx->last_block = (int)plan.block;
-  hipError_t e = hrt::launch_trace(p, plan, stream, want_sky ? &sky : nullptr);
+  hipError_t e = hrt::launch_trace(p, plan, stream, want_sky ? &sky : nullptr, masked);
   if (e == hipSuccess) ctx->last_frames = ev.frames;
   // the persistent kernels recorded this trace's tile costs: the lane's next trace can follow a plan
-  lane.plan_valid = e == hipSuccess && kernel.persistent;
+  if (!masked) lane.plan_valid = e == hipSuccess && kernel.persistent;  // (a masked launch recorded into its own image)
   // (only a kernel that built the lists leaves them valid: a LITERAL / BRUTE trace from this position
   // followed by a bundle kernel must rebuild them)
   if (e == hipSuccess && kernel.camera_lists) {
@@ -1522,7 +1529,8 @@ hrt_status begin_batch(hrt_context* ctx, const hrt_push_constants* pc, uint32_t 
 
 // One trace launch of the nf frames from frame0 (u32, wrapping like the per-frame loop's pushes);
 // *stack: where it left them -- the frame stack, or lane 0's image for a single frame.
-hrt_status launch_batch(hrt_context* ctx, const Batch& b, uint32_t frame0, uint32_t nf, const char** stack) {
+hrt_status launch_batch(hrt_context* ctx, const Batch& b, uint32_t frame0, uint32_t nf, const char** stack,
+                        const hrt::MaskedPlan* masked = nullptr) {
   hrt::Lane& lane = ctx->lane[0];
   hrt::TraceParams q = b.p;
   q.pc.rng_offset = frame0;
@@ -1530,7 +1538,7 @@ hrt_status launch_batch(hrt_context* ctx, const Batch& b, uint32_t frame0, uint3
   q.plan_valid = lane.plan_valid ? 1u : 0u;
   if (nf > 1) set_image(q, ctx, ctx->frame_stack);
   *stack = static_cast<const char*>(nf > 1 ? ctx->frame_stack : lane.trace);
-  return launch_frames(ctx, q, ctx->stream, 0);
+  return launch_frames(ctx, q, ctx->stream, 0, masked);
 }
 
 // The trace image holds the last frame folded (frame s - 1 of a launch of nf), as after the per-frame loop.
@@ -2567,6 +2575,146 @@ extern "C" hrt_status hrt_refine_until(hrt_context* ctx, const hrt_push_constant
       return st;
     *passes_done = k + 1;
     *pixel_frames += count;
+  }
+  return HRT_OK;
+}
+
+// ---- tile-masked refinement (kernels in hrt_refine.hip) ----------------------------------
+namespace {
+
+constexpr uint32_t kMaskedTilesMax = (1u << 22) - 1u;  // the item word's tile field (hrt_plan.h kItemTileMask)
+
+// The pass's buffers: the tile bitmap and its counts, and -- plan -- the masked launches' own sched, items and costs.
+hrt_status ensure_refine_tiles(hrt_context* ctx, bool plan, const char* who) {
+  const size_t tiles = ctx->num_tiles();
+  auto ensure = [&](auto*& field, size_t bytes) {
+    void* p = field;
+    hrt_status st = ensure_staging(ctx, &p, bytes, who);
+    field = static_cast<std::remove_reference_t<decltype(field)>>(p);
+    return st;
+  };
+  hrt_status st = ensure(ctx->rt_bits, (tiles + 31) / 32 * 4);
+  if (st == HRT_OK) st = ensure(ctx->rt_counts, 3 * sizeof(unsigned long long));
+  if (plan && st == HRT_OK) st = ensure(ctx->rt_sched, hrt::kSchedWords * 4);
+  if (plan && st == HRT_OK) st = ensure(ctx->rt_items, tiles * 64 * 4);
+  if (plan && st == HRT_OK) st = ensure(ctx->rt_cost, tiles * 4);
+  return st;
+}
+
+// What hrt_refine_tiles checks beyond check_refine.
+hrt_status check_refine_tiles(hrt_context* ctx, const hrt_push_constants* pc, uint32_t max_history, uint32_t frames,
+                              uint32_t flags, const char* who) {
+  hrt_status st = check_refine(ctx, pc, max_history, HRT_REFINE_FRAME, HRT_QUERY_AUTO, flags, who);
+  if (st != HRT_OK) return st;
+  if (frames == 0 || frames > HRT_REFINE_TILES_MAX_FRAMES)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": frames must be 1..HRT_REFINE_TILES_MAX_FRAMES");
+  return HRT_OK;
+}
+
+// One tile-masked pass of `frames` frames over dmask (device memory).  Every argument has been checked.
+hrt_status refine_tiles_pass(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* dmask, uint32_t max_history,
+                             uint32_t frames, uint32_t flags, hrt_refine_tiles_stats* stats, const char* who) {
+  const bool moments = (flags & HRT_REFINE_MOMENTS) != 0;
+  hrt_status st = begin_history(ctx, who);
+  if (st != HRT_OK) return st;
+  if (moments && (st = begin_moments(ctx, who)) != HRT_OK) return st;
+  // host side: the kernel the request resolves to decides between the masked launches and whole frames
+  const hrt::TraceParams p0 = make_params(ctx, pc, 0);
+  const hrt::LaunchPlan plan = hrt::plan_trace(hrt::plan_scene(p0), ctx->variant);
+  const uint32_t tiles = (uint32_t)ctx->num_tiles();
+  const bool whole = !hrt::kernel_traits(plan.kernel).persistent || ctx->num_tiles() > kMaskedTilesMax || ctx->diag_on;
+  if ((st = ensure_refine_tiles(ctx, !whole, who)) != HRT_OK) return st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
+  // the tile bitmap and the counts, back to the host
+  HRT_HIP(ctx, hipMemsetAsync(ctx->rt_counts, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  HRT_HIP(ctx, hrt::launch_refine_tile_bits(dmask, ctx->rt_bits, ctx->rt_counts, ctx->width, ctx->local_rows, ctx->stream));
+  unsigned long long counts[3] = {0, 0, 0};
+  HRT_HIP(ctx, hipMemcpyAsync(counts, ctx->rt_counts, sizeof counts, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) *stats = hrt_refine_tiles_stats{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (counts[0] == 0) return HRT_OK;
+  Batch b;
+  if ((st = begin_batch(ctx, pc, frames, UINT32_MAX, &b)) != HRT_OK) return st;
+  hrt::Lane& lane = ctx->lane[0];
+  const hrt::MaskedPlan mp{ctx->rt_bits, ctx->rt_sched, ctx->rt_items, ctx->rt_cost, (uint32_t)counts[1], lane.plan_valid};
+  float* mom = moments ? ctx->hist_mom : nullptr;
+  for (uint32_t done = 0; done < frames;) {
+    // hrt_compute_n's near-equal launches
+    const uint32_t left = frames - done, launches = (left + b.lcap - 1) / b.lcap;
+    const uint32_t nf = (left + launches - 1) / launches, frame0 = pc->rng_offset + done;
+    const char* stack = nullptr;
+    if ((st = launch_batch(ctx, b, frame0, nf, &stack, whole ? nullptr : &mp)) != HRT_OK) return st;
+    // the fold under the mask; a masked launch's last frame goes to lane 0's image tile by tile, a whole one's whole
+    void* trace = !whole && nf > 1 ? lane.trace : nullptr;
+    HRT_HIP(ctx, hrt::launch_refine_fold_frames(ctx->accum, stack, ctx->npix(), nf, ctx->hist_cnt, mom, ctx->f32(), dmask,
+                                                trace ? ctx->rt_bits : nullptr, trace, ctx->width, ctx->local_rows,
+                                                max_history, ctx->stream));
+    if (whole && (st = keep_last_frame(ctx, stack, nf, nf)) != HRT_OK) return st;
+    done += nf;
+  }
+  if ((st = end_batch(ctx)) != HRT_OK) return st;
+  uint32_t items = 0;
+  if (!whole && stats) HRT_HIP(ctx, hipMemcpyAsync(&items, ctx->rt_sched + 1, sizeof items, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats)
+    *stats = hrt_refine_tiles_stats{(uint32_t)plan.kernel, whole ? 1u : 0u, tiles, (uint32_t)counts[1], items, 0u, counts[0],
+                                    whole ? (uint64_t)ctx->npix() : counts[2]};
+  return HRT_OK;
+}
+
+}  // namespace
+
+extern "C" hrt_status hrt_refine_tiles(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* mask, uint32_t max_history,
+                                       uint32_t frames, uint32_t flags, hrt_refine_tiles_stats* stats) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_refine_tiles";
+  hrt_status st = check_refine_tiles(ctx, pc, max_history, frames, flags, who);
+  if (st != HRT_OK) return st;
+  if (!mask) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_tiles: null mask");
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  const bool direct = query_direct(ctx, mask);
+  if (direct && (uintptr_t)mask % 4 != 0)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_tiles: a device mask must be 4-byte aligned");
+  if (!direct) {
+    if ((st = ensure_refine_mask(ctx, who)) != HRT_OK) return st;
+    HRT_HIP(ctx, hipMemcpyAsync(ctx->rf_mask, mask, refine_mask_words(ctx) * 4, hipMemcpyDefault, ctx->stream));
+  }
+  return refine_tiles_pass(ctx, pc, direct ? mask : ctx->rf_mask, max_history, frames, flags, stats, who);
+}
+
+extern "C" hrt_status hrt_refine_tiles_until(hrt_context* ctx, const hrt_push_constants* pc, const hrt_refine_rule* rule,
+                                             const hrt_hit* guide, uint32_t max_history, uint32_t max_passes,
+                                             uint32_t frames_per_pass, uint32_t flags, uint32_t* passes_done,
+                                             uint64_t* pixel_frames, uint32_t* settled) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_refine_tiles_until";
+  if (!passes_done || !pixel_frames)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_refine_tiles_until: null passes_done or pixel_frames");
+  hrt_status st = check_refine_rule(ctx, rule, who);
+  if (st != HRT_OK) return st;
+  if ((st = check_refine_tiles(ctx, pc, max_history, frames_per_pass, flags, who)) != HRT_OK) return st;
+  if ((st = bind(ctx)) != HRT_OK) return st;
+  if ((st = check_refine_guide(ctx, guide, who)) != HRT_OK) return st;
+  if ((st = ensure_refine_mask(ctx, who)) != HRT_OK) return st;
+  *passes_done = 0;
+  *pixel_frames = 0;
+  if (settled) *settled = 0;
+  hrt_push_constants frame = *pc;
+  for (uint32_t k = 0; k < max_passes; ++k) {
+    if ((st = enqueue_refine_select(ctx, rule, guide, ctx->rf_mask, who)) != HRT_OK) return st;
+    unsigned long long count = 0;
+    HRT_HIP(ctx, hipMemcpyAsync(&count, ctx->rf_words, sizeof count, hipMemcpyDefault, ctx->stream));
+    HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (count == 0) {
+      if (settled) *settled = 1;
+      break;
+    }
+    frame.rng_offset = pc->rng_offset + k * frames_per_pass;
+    if ((st = refine_tiles_pass(ctx, &frame, ctx->rf_mask, max_history, frames_per_pass, flags | HRT_REFINE_MOMENTS, nullptr,
+                                who)) != HRT_OK)
+      return st;
+    *passes_done = k + 1;
+    *pixel_frames += count * frames_per_pass;
   }
   return HRT_OK;
 }

@@ -256,6 +256,14 @@ struct hrt_context {
   uint32_t* rf_index = nullptr;
   void* rf_rgba = nullptr;
   unsigned long long* rf_words = nullptr;
+  // The tile-masked refinement (hrt_refine_tiles): one bit per 8x8 tile, three 64-bit counts (selected pixels,
+  // selected tiles, their real pixels), and the masked launches' own plan -- sched words, item list and a scratch
+  // cost image, so that lane 0's are never written.  Allocated by the first call, freed by hrt_destroy
+  uint32_t* rt_bits = nullptr;
+  unsigned long long* rt_counts = nullptr;
+  uint32_t* rt_sched = nullptr;
+  uint32_t* rt_items = nullptr;
+  uint32_t* rt_cost = nullptr;
   // The first-hit pass (hrt_first_hits): its own camera buffers (a fourth set beside the lanes', the scene's
   // sizes), allocated by the first TILES call and dropped by hrt_set_scene; fh_key = the camera position's bits
   // and num_meshes the records were built for (fh_ready: by a launch already enqueued on `stream`); the device

@@ -115,6 +115,17 @@ struct SkyLane {
              // exist before the first launch that forks to it (a one-time cost of tens of ms)
 };
 constexpr uint32_t kTlRecWords = 136;
+// The plan of a tile-masked launch (hrt_refine_tiles): the persistent kernel runs only the tiles
+// whose bit is set, from a plan made in buffers of the context's own -- p's sched, tile_cost and item_buf (the
+// lane's) are read for the plan's input and never written.  Host side only: TraceParams is unchanged.
+struct MaskedPlan {
+  const uint32_t* tile_bits;  // tile t = tx + ty tiles_x is bit t & 31 of word t >> 5
+  uint32_t* sched;            // kSchedWords words
+  uint32_t* items;            // tiles x 64 item words
+  uint32_t* cost;             // tiles words: where the launch's kernels leave their tile costs (scratch)
+  uint32_t tiles_selected;    // set bits of tile_bits, > 0 (the auto split factor's tile count)
+  bool costs_valid;           // p.tile_cost holds a previous trace's costs (else every selected tile costs 1)
+};
 
 // Per device, once: the dynamic-LDS limits of the persistent kernels (hipFuncSetAttribute).
 hipError_t ensure_kernel_attributes(int device);
@@ -125,7 +136,9 @@ PlanScene plan_scene(const TraceParams& p);
 // sky: BUNDLE_WQ's product kernels run a planned launch's sky items on trace_sky beside the main kernel
 // (forked from `stream` after the planner kernels, joined back into it before launch_trace returns);
 // nullptr: every item runs on the main kernel.
-hipError_t launch_trace(const TraceParams& p, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky = nullptr);
+// masked: a persistent kernel's launch over the selected tiles only (above); the tile count must fit the item word.
+hipError_t launch_trace(const TraceParams& p, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky = nullptr,
+                        const MaskedPlan* masked = nullptr);
 // hrt_debug_tile_lists: camera_lists, then tile_lists into p.tl_cache (tiles x kTlRecWords); refine 0: the
 // cap rule alone, else the product's lists (cap, then corner directions per tile and per pixel).
 hipError_t launch_tile_lists(const TraceParams& p, uint32_t refine, hipStream_t stream);

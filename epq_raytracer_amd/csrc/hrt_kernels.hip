@@ -27,6 +27,8 @@
 #include "hrt_bvh.h"
 #include "hrt_kernels.h"
 #include "hrt_math.h"
+#include "hrt_plan.h"
+#include "hrt_refine.h"
 
 namespace hrt {
 
@@ -2918,7 +2920,6 @@ __device__ __forceinline__ void stage_tris(const TraceParams& P, float4* dst, ui
 // to P.tile_cost[tile] for the next plan: deterministic work units (Coop::work: survivor tests,
 // culled chunks, primary list entries, iterations; the same with or without cooperation) in
 // BUNDLE_CULL_LDS, shader clocks / 16 in BUNDLE_BVH_LDS.
-constexpr uint32_t kItemTileMask = (1u << 22) - 1u;  // planned traces need fewer than 2^22 tiles
 // The work queue: one u64 word, the front cursor (tile_loop) in its low half and the back cursor
 // (trace_sky) in its high half, both in work units (item x frame) -- the back cursor counted down from
 // the plan's end n; sched[kSchedSky] = the number of sky items the plan ends in (plan_scan; 0 without a
@@ -2933,8 +2934,7 @@ constexpr uint32_t kItemTileMask = (1u << 22) - 1u;  // planned traces need fewe
 //    nothing and the wave ends.  Back claims past S only raise a count that front claims clamp to S, so
 //    trace_sky never takes a unit below the sky items.
 // So every unit has exactly one owner whichever side arrives first, and either side finishes the other's end.
-constexpr uint32_t kSchedSky = 1000, kSchedQueue = 1002;
-static_assert(kSchedQueue + 2 <= kSchedWords && kSchedQueue % 2 == 0, "sched buffer");
+// (kItemTileMask, kSchedSky, kSchedQueue and the planner's helpers: hrt_plan.h)
 // Sky: the kernel may run beside trace_sky and makes front claims as above; otherwise nothing ever raises
 // the word's high half and the loop counts on its low half alone.
 template <int BLOCK, bool CoopOk, bool Sky = false, class Body>
@@ -3105,32 +3105,7 @@ __device__ __forceinline__ void tile_loop(const TraceParams& P, unsigned long lo
 // factor x (sum of costs / resident waves), to the bucket, i.e. a tile that alone would take `factor`
 // times a wave's fair share of the frame; each runs as 2, 4 or 8 items (bucket_items, <= split_k).  sched[8..71] histogram, [72..135] bucket offsets,
 // [136..199] bucket cursors, [3] first heavy bucket.
-#ifndef HRT_PLAN_SUB
-// log2 of the planner's cost buckets per octave: eighth-octave buckets put a rank's long items nearer to
-// their exact longest-first order (r06p: the slowest of ranks 3 and 6 -1.7% per run on island, -1.1% on
-// cave; half-octave buckets left tiles up to 1.41x apart in arbitrary order)
-#define HRT_PLAN_SUB 3
-#endif
-constexpr uint32_t kPlanSub = HRT_PLAN_SUB, kPlanBuckets = 32u << kPlanSub;
-__device__ __forceinline__ uint32_t cost_bucket(unsigned long long c) {
-  if (c < (2u << kPlanSub)) return (uint32_t)c;  // (floor(log2 c) <= kPlanSub: the value itself)
-  if (c > 0xFFFFFFFFull) return kPlanBuckets;
-  const uint32_t v = (uint32_t)c, l = 31 - __clz(v);  // floor(log2 c) > kPlanSub
-  return min((l << kPlanSub) + ((v >> (l - kPlanSub)) & ((1u << kPlanSub) - 1u)), kPlanBuckets - 1);
-}
-// sched words: [8, 8 + B) histogram, [8 + B, 8 + 2B) bucket offsets, [8 + 2B, 8 + 3B) cursors
-constexpr uint32_t kSchedHist = 8, kSchedOff = 8 + kPlanBuckets, kSchedCur = 8 + 2 * kPlanBuckets;
-static_assert(kSchedCur + kPlanBuckets <= kSchedSky, "sched buffer");
-// A tile's bucket.  With a sky lane (tl_cache: the launch's tile_lists records, a scene without spheres)
-// bucket 0 holds exactly the tiles whose whole-tile item is a sky item (trace_fused_split's rule: list
-// ok and empty), whatever they cost, and no other tile: the descending scan puts them at the plan's far
-// end, where trace_sky takes them, and sched[kSchedHist] is their number.
-__device__ __forceinline__ uint32_t plan_bucket(const uint32_t* cost, const uint32_t* tl_cache, uint32_t i) {
-  const uint32_t b = cost_bucket(cost[i]);
-  if (!tl_cache) return b;
-  const uint32_t* rec = tl_cache + (size_t)i * kTlRecWords;
-  return (rec[128] == 0u && rec[129] != 0u) ? 0u : max(b, 1u);
-}
+// The cost buckets, the sched words and a tile's bucket (plan_bucket, its sky rule): hrt_plan.h.
 // Both passes count in LDS first: a frame's tiles crowd a few buckets, and per-tile global atomics
 // on those few words serialize (0.3 ms per pass at 1080p).
 __global__ __launch_bounds__(256) void plan_hist(uint32_t* sched, const uint32_t* cost, uint32_t tiles,
@@ -3142,11 +3117,6 @@ __global__ __launch_bounds__(256) void plan_hist(uint32_t* sched, const uint32_t
   if (i < tiles) atomicAdd(&h[plan_bucket(cost, tl_cache, i)], 1u);
   __syncthreads();
   if (threadIdx.x < kPlanBuckets && h[threadIdx.x]) atomicAdd(&sched[kSchedHist + threadIdx.x], h[threadIdx.x]);
-}
-// Items of a heavy tile in bucket b >= hb: doubling per octave above the threshold (costs [1, 2) x
-// threshold: 2 items, [2, 4): 4, ... up to 64 single pixels), at most kmax; kmax = 1: never split.
-__device__ __forceinline__ uint32_t bucket_items(uint32_t b, uint32_t hb, uint32_t kmax) {
-  return b < hb ? 1u : min(kmax, 2u << min((b - hb) >> kPlanSub, 5u));
 }
 // factor4: the heavy threshold in quarters of a resident wave's share of the launch's work
 __global__ __launch_bounds__(64) void plan_scan(uint32_t* sched, uint32_t waves, uint32_t factor4, uint32_t kmax,
@@ -3701,11 +3671,36 @@ static uint32_t tiles_of(const TraceParams& p) { return ((p.pc.width + 7) / 8) *
 
 // Persistent kernels: plan this trace from the last one's tile costs (when p.plan_valid and
 // splitting is on), then reset the counters the trace fills.  q.items = nullptr: plain tile order.
-static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream) {
+// m: a tile-masked launch (MaskedPlan): always planned, over the selected tiles only, from the lane's costs (read)
+// into the context's own sched / item / cost buffers, which the launch then runs from and records into.
+static hipError_t prepare_schedule(TraceParams& q, hipStream_t stream, const MaskedPlan* m) {
   // (q.sky_lane: requested by launch_trace; kept only for a planned launch whose work indices and item
   // count leave the queue word's halves apart)
   const uint32_t nf = q.n_frames > 1 ? q.n_frames : 1u;
   const uint32_t tiles = tiles_of(q);
+  if (m) {
+    if (tiles == 0 || tiles > kItemTileMask || !m->tile_bits || !m->sched || !m->items || !m->cost) return hipErrorInvalidValue;
+    if ((uint64_t)tiles * 8u * nf >= (1ull << 31)) q.sky_lane = 0;
+    const uint32_t* sky_cache = q.sky_lane ? q.tl_cache : nullptr;
+    const uint32_t* cost_in = m->costs_valid ? q.tile_cost : nullptr;
+    hipError_t e;
+    if ((e = hipMemsetAsync(m->sched + kSchedHist, 0, 3 * kPlanBuckets * 4, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(m->sched + 5, 0, 12, stream)) != hipSuccess) return e;  // (the cost sum the histogram pass adds to)
+    if ((e = launch_plan_hist_masked(m->sched, cost_in, m->tile_bits, tiles, sky_cache, stream)) != hipSuccess) return e;
+    const uint32_t waves = plan_waves(q.num_cus, nf);
+    const uint32_t factor4 = plan_factor4(m->tiles_selected, waves, SplitFactor{q.split_factor, q.split_factor4});
+    plan_scan<<<1, 64, 0, stream>>>(m->sched, waves, factor4, q.split_k, q.split_prio, q.sky_lane);
+    if ((e = launch_plan_fill_masked(m->sched, cost_in, m->tile_bits, tiles, q.split_k, q.split_prio, m->items, sky_cache,
+                                     stream)) != hipSuccess)
+      return e;
+    q.sched = m->sched;
+    q.tile_cost = m->cost;
+    q.item_buf = m->items;
+    q.items = m->items;
+    if ((e = hipMemsetAsync(q.tile_cost, 0, (size_t)tiles * 4, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(q.sched + 5, 0, 12, stream)) != hipSuccess) return e;
+    return hipMemsetAsync(q.sched + kSchedQueue, 0, 8, stream);
+  }
   // longest-first order whenever last trace's costs are known (and tile indices fit the item word)
   const bool plan = q.plan_valid && tiles > 0 && tiles <= kItemTileMask;
   q.items = plan ? q.item_buf : nullptr;
@@ -3778,13 +3773,15 @@ hipError_t ensure_kernel_attributes(int device) {
 #ifndef HRT_SKY_GRID
 #define HRT_SKY_GRID 1u  // trace_sky workgroups per CU
 #endif
-hipError_t launch_trace(const TraceParams& p0, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky) {
+hipError_t launch_trace(const TraceParams& p0, const LaunchPlan& plan, hipStream_t stream, const SkyLane* sky,
+                        const MaskedPlan* masked) {
   TraceParams p = p0;
   const int k = plan.kernel;
   const KernelTraits& kt = kernel_traits(k);
   p.sec_batch = batch_threshold(p.sec_batch, plan.sec_batch);
   p.prim_batch = batch_threshold(p.prim_batch, plan.prim_batch);
   if (kt.camera_lists && p.pc.num_meshes > 0 && !p.cam_lists_ready) camera_lists<<<p.pc.num_meshes, 256, 0, stream>>>(p);
+  if (masked && (!kt.persistent || p0.diag || p0.probe)) return hipErrorInvalidValue;  // (the caller falls back to whole frames)
   if (!kt.persistent) {
     const int px = plan.block == 1024 ? 32 : 16;  // a workgroup's square of pixels
     const dim3 grid((p.pc.width + px - 1) / px, (p.local_rows + px - 1) / px, 1);
@@ -3819,7 +3816,7 @@ hipError_t launch_trace(const TraceParams& p0, const LaunchPlan& plan, hipStream
   const bool d = p.diag || p.probe;
   q.sky_lane = kt.sky_lane && sky && sky->run && !HRT_TIMELINE && HRT_TL_PREPASS && HRT_SKY_LOOP && !d && p.tl_cache &&
                p.pc.num_spheres == 0;
-  if (hipError_t e = prepare_schedule(q, stream); e != hipSuccess) return e;
+  if (hipError_t e = prepare_schedule(q, stream, masked); e != hipSuccess) return e;
   if (q.sky_lane) {
     if (hipError_t e = hipEventRecord(sky->fork, stream); e != hipSuccess) return e;
     if (hipError_t e = hipStreamWaitEvent(sky->stream, sky->fork, 0); e != hipSuccess) return e;

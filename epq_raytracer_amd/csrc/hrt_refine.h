@@ -42,4 +42,25 @@ hipError_t launch_refine_fold(void* cur, uint32_t* cnt, float* mom, bool f32, co
 hipError_t launch_refine_fold_image(void* cur, const void* nw, uint32_t* cnt, float* mom, bool f32, const uint32_t* mask,
                                     uint32_t npix, uint32_t max_history, hipStream_t stream);
 
+// ---- the tile-masked pass (hrt_refine_tiles) ----
+// bits <- one bit per 8x8 tile of a w x h image, set when any real pixel of the tile has its mask bit set:
+// ceil(tiles / 32) words, each written in full, the unused high bits of the last word 0.  counts[0..2] (zeroed by
+// the caller) += the set bits of real pixels, the selected tiles, the real pixels of the selected tiles.
+hipError_t launch_refine_tile_bits(const uint32_t* mask, uint32_t* bits, unsigned long long* counts, uint32_t w, uint32_t h,
+                                   hipStream_t stream);
+
+// The planner's histogram and fill passes over the selected tiles (hrt_kernels.hip's plan_hist / plan_fill otherwise;
+// plan_scan runs between them).  cost: a previous trace's tile costs, or null: 1 for every tile.  sched's histogram,
+// cursors and words 6..7 are zeroed by the caller; the histogram pass adds the selected tiles' costs to words 6..7.
+hipError_t launch_plan_hist_masked(uint32_t* sched, const uint32_t* cost, const uint32_t* bits, uint32_t tiles,
+                                   const uint32_t* tl_cache, hipStream_t stream);
+hipError_t launch_plan_fill_masked(uint32_t* sched, const uint32_t* cost, const uint32_t* bits, uint32_t tiles, uint32_t kmax,
+                                   uint32_t prio, uint32_t* items, const uint32_t* tl_cache, hipStream_t stream);
+
+// launch_refine_fold_image for the nf frames at stack + f * stride pixels, f = 0 .. nf - 1 in order, in one pass.
+// trace (may be null; then tile_bits is not read): every pixel whose tile's bit is set gets frame nf - 1's texel.
+hipError_t launch_refine_fold_frames(void* cur, const void* stack, size_t stride, uint32_t nf, uint32_t* cnt, float* mom,
+                                     bool f32, const uint32_t* mask, const uint32_t* tile_bits, void* trace, uint32_t w,
+                                     uint32_t h, uint32_t max_history, hipStream_t stream);
+
 }  // namespace hrt

@@ -20,7 +20,9 @@
 #include "hrt_history.h"
 #include "hrt_history_fold.h"
 #include "hrt_math.h"
+#include "hrt_plan.h"
 #include "hrt_refine.h"
+#include "hrt_refine_tile_bits.h"
 
 namespace hrt {
 
@@ -174,6 +176,138 @@ __global__ __launch_bounds__(256) void refine_fold_image(T* cur, const T* __rest
   refine_fold_pixel<T, Moments>(cur, cnt, mom, i, nw[i], max_history, tab);
 }
 
+// ---- the tile-masked pass (hrt_refine_tiles) --------------------------------------------
+// Pixel mask -> one bit per 8x8 tile: one lane per tile, so a wave's ballot is the two bit words of its 64 tiles
+// (each written in full).  counts (zeroed by the caller) += {the set bits of real pixels, the selected tiles, the
+// real pixels of the selected tiles}.
+__global__ __launch_bounds__(256) void refine_tile_bits(const uint32_t* __restrict__ mask, uint32_t* __restrict__ bits,
+                                                        unsigned long long* __restrict__ counts, uint32_t w, uint32_t h) {
+  const uint32_t tiles_x = (w + 7u) / 8u, tiles = tiles_x * ((h + 7u) / 8u);
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  uint32_t sel = 0u, real = 0u;
+  if (t < tiles) {
+    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
+    sel = tile_selected_pixels(mask, w, h, tx, ty, &real);
+  }
+  const unsigned long long on = __ballot(sel != 0u);
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t base = t - lane;  // the wave's first tile: a multiple of 64
+  if (lane == 0u && base < tiles) bits[base >> 5] = (uint32_t)on;
+  if (lane == 32u && base + 32u < tiles) bits[(base >> 5) + 1u] = (uint32_t)(on >> 32);
+  if (on == 0ull) return;  // (the same in every lane)
+  uint32_t traced = sel != 0u ? real : 0u;  // (a wave's sums are at most 64 x 64)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sel += __shfl_xor(sel, off, 64);
+    traced += __shfl_xor(traced, off, 64);
+  }
+  if (lane == 0u) {
+    atomicAdd(&counts[0], (unsigned long long)sel);
+    atomicAdd(&counts[1], (unsigned long long)__popcll(on));
+    atomicAdd(&counts[2], (unsigned long long)traced);
+  }
+}
+
+// plan_hist / plan_fill (hrt_kernels.hip) over the tiles whose bit is set: the same buckets, sky rule, heavy
+// split, priority flag and item words (hrt_plan.h), with the tile's input cost from `cost`, or 1 for every tile
+// when cost is null.  The histogram pass also sums the selected tiles' input costs into sched[6..7], the u64 a
+// whole frame's trace leaves there and plan_scan reads (zeroed by the caller).
+__device__ __forceinline__ bool tile_bit(const uint32_t* bits, uint32_t t) { return ((bits[t >> 5] >> (t & 31u)) & 1u) != 0u; }
+__global__ __launch_bounds__(256) void plan_hist_masked(uint32_t* sched, const uint32_t* __restrict__ cost,
+                                                        const uint32_t* __restrict__ bits, uint32_t tiles,
+                                                        const uint32_t* tl_cache) {
+  __shared__ uint32_t h[kPlanBuckets];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (threadIdx.x < kPlanBuckets) h[threadIdx.x] = 0;
+  __syncthreads();
+  const bool sel = i < tiles && tile_bit(bits, i);
+  unsigned long long c = 0ull;
+  if (sel) {
+    const uint32_t ci = cost ? cost[i] : 1u;
+    atomicAdd(&h[plan_bucket_of(ci, tl_cache, i)], 1u);
+    c = ci;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((threadIdx.x & 63u) == 0u && c) atomicAdd(reinterpret_cast<unsigned long long*>(sched + 6), c);
+  __syncthreads();
+  if (threadIdx.x < kPlanBuckets && h[threadIdx.x]) atomicAdd(&sched[kSchedHist + threadIdx.x], h[threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void plan_fill_masked(uint32_t* sched, const uint32_t* __restrict__ cost,
+                                                        const uint32_t* __restrict__ bits, uint32_t tiles, uint32_t kmax,
+                                                        uint32_t prio, uint32_t* items, const uint32_t* tl_cache) {
+  __shared__ uint32_t cnt[kPlanBuckets], base[kPlanBuckets];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (threadIdx.x < kPlanBuckets) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t hb = sched[3];
+  const bool sel = i < tiles && tile_bit(bits, i);
+  const uint32_t b = sel ? plan_bucket_of(cost ? cost[i] : 1u, tl_cache, i) : 0u;
+  const bool heavy = b >= hb;
+  const uint32_t k = bucket_items(b, hb, kmax);
+  const uint32_t local = sel ? atomicAdd(&cnt[b], k) : 0u;
+  __syncthreads();
+  if (threadIdx.x < kPlanBuckets && cnt[threadIdx.x])
+    base[threadIdx.x] = sched[kSchedOff + threadIdx.x] + atomicAdd(&sched[kSchedCur + threadIdx.x], cnt[threadIdx.x]);
+  __syncthreads();
+  if (!sel) return;
+  const uint32_t at = base[b] + local;  // < the plan's items <= 64 x the selected tiles: inside the item list
+  if (!heavy) {
+    items[at] = i;
+  } else {
+    const uint32_t flag = prio ? 0x80000000u : 0u;
+    if (k == 1) {
+      items[at] = i | flag;
+    } else {
+      const uint32_t lk = (uint32_t)__builtin_ctz(k);
+      for (uint32_t s = 0; s < k; ++s) items[at + s] = i | (lk << 22) | (s << 25) | flag;
+    }
+  }
+}
+
+// One lane per pixel.  A pixel whose bit is set folds the launch's nf frames (frame f's texel at stack[f stride +
+// i]) in order, in registers -- refine_fold_pixel's statements nf times -- and stores A, N and M once; nf = 1 is
+// refine_fold_image.  trace (null: the stack is the trace image already) gets the last frame's texel of every
+// pixel whose tile's bit is set; no other byte of it is touched.
+template <typename T, bool Moments>
+__global__ __launch_bounds__(256) void refine_fold_frames(T* cur, const T* __restrict__ stack, size_t stride, uint32_t nf,
+                                                          uint32_t* cnt, float2* mom, const uint32_t* __restrict__ mask,
+                                                          const uint32_t* __restrict__ tile_bits, T* __restrict__ trace,
+                                                          uint32_t w, uint32_t npix, uint32_t max_history) {
+  __shared__ float tab_s[std::is_same_v<T, uint32_t> ? 256 : 1];
+  const float* tab = fold_table<T>(tab_s);
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= npix) return;
+  const bool sel = ((mask[i >> 5] >> (i & 31u)) & 1u) != 0u;
+  bool copy = false;
+  if (trace) {
+    const uint32_t y = i / w, x = i - y * w;
+    copy = tile_bit(tile_bits, (x >> 3) + (y >> 3) * ((w + 7u) / 8u));
+  }
+  if (!sel && !copy) return;
+  T v;
+  if (sel) {
+    uint32_t n = cnt[i];
+    T a = n == 0u ? texel_zero<T>() : cur[i];
+    float2 m = make_float2(0.0f, 0.0f);
+    if constexpr (Moments) {
+      if (n != 0u) m = mom[i];
+    }
+    for (uint32_t f = 0; f < nf; ++f) {
+      v = stack[(size_t)f * stride + i];
+      a = hist_step(a, v, n, tab);
+      if constexpr (Moments) m = moments_step(m, v, n, tab);
+      n = hist_next(n, max_history);
+    }
+    cur[i] = a;
+    cnt[i] = n;
+    if constexpr (Moments) mom[i] = m;
+  } else {
+    v = stack[(size_t)(nf - 1u) * stride + i];
+  }
+  if (copy) trace[i] = v;
+}
+
 // ---- launch wrappers (host) ----------------------------------------------------------------------------------
 static uint32_t blocks_of(uint32_t n) { return (uint32_t)(((uint64_t)n + 255u) / 256u); }
 
@@ -260,6 +394,61 @@ hipError_t launch_refine_fold_image(void* cur, const void* nw, uint32_t* cnt, fl
       refine_fold_image<uint32_t, true><<<blocks, 256, 0, stream>>>(c, v, cnt, m, mask, npix, max_history);
     else
       refine_fold_image<uint32_t, false><<<blocks, 256, 0, stream>>>(c, v, cnt, nullptr, mask, npix, max_history);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_refine_tile_bits(const uint32_t* mask, uint32_t* bits, unsigned long long* counts, uint32_t w, uint32_t h,
+                                   hipStream_t stream) {
+  if (w == 0 || h == 0) return hipSuccess;
+  if (!mask || !bits || !counts || ((uintptr_t)mask & 3u) != 0 || (uint64_t)w * h > 0x80000000ull) return hipErrorInvalidValue;
+  const uint32_t tiles = ((w + 7u) / 8u) * ((h + 7u) / 8u);
+  refine_tile_bits<<<blocks_of(tiles), 256, 0, stream>>>(mask, bits, counts, w, h);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_hist_masked(uint32_t* sched, const uint32_t* cost, const uint32_t* bits, uint32_t tiles,
+                                   const uint32_t* tl_cache, hipStream_t stream) {
+  if (!sched || !bits || tiles == 0 || tiles > kItemTileMask) return hipErrorInvalidValue;
+  plan_hist_masked<<<blocks_of(tiles), 256, 0, stream>>>(sched, cost, bits, tiles, tl_cache);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_fill_masked(uint32_t* sched, const uint32_t* cost, const uint32_t* bits, uint32_t tiles, uint32_t kmax,
+                                   uint32_t prio, uint32_t* items, const uint32_t* tl_cache, hipStream_t stream) {
+  if (!sched || !bits || !items || tiles == 0 || tiles > kItemTileMask || kmax == 0 || kmax > 64u) return hipErrorInvalidValue;
+  plan_fill_masked<<<blocks_of(tiles), 256, 0, stream>>>(sched, cost, bits, tiles, kmax, prio, items, tl_cache);
+  return hipGetLastError();
+}
+
+hipError_t launch_refine_fold_frames(void* cur, const void* stack, size_t stride, uint32_t nf, uint32_t* cnt, float* mom,
+                                     bool f32, const uint32_t* mask, const uint32_t* tile_bits, void* trace, uint32_t w,
+                                     uint32_t h, uint32_t max_history, hipStream_t stream) {
+  if (w == 0 || h == 0 || nf == 0) return hipSuccess;
+  if (!fold_args_ok(cur, cnt, mom, f32, max_history) || !stack || !mask || ((uintptr_t)mask & 3u) != 0 ||
+      (uint64_t)w * h > 0x80000000ull || (trace && !tile_bits) || (nf > 1 && stride < (size_t)w * h))
+    return hipErrorInvalidValue;
+  if (f32 && ((((uintptr_t)stack | (uintptr_t)trace) & 15u) != 0)) return hipErrorInvalidValue;
+  float2* m = reinterpret_cast<float2*>(mom);
+  const uint32_t npix = w * h, blocks = blocks_of(npix);
+  if (f32) {
+    float4* c = static_cast<float4*>(cur);
+    const float4* s = static_cast<const float4*>(stack);
+    float4* t = static_cast<float4*>(trace);
+    if (mom)
+      refine_fold_frames<float4, true><<<blocks, 256, 0, stream>>>(c, s, stride, nf, cnt, m, mask, tile_bits, t, w, npix, max_history);
+    else
+      refine_fold_frames<float4, false><<<blocks, 256, 0, stream>>>(c, s, stride, nf, cnt, nullptr, mask, tile_bits, t, w, npix,
+                                                                    max_history);
+  } else {
+    uint32_t* c = static_cast<uint32_t*>(cur);
+    const uint32_t* s = static_cast<const uint32_t*>(stack);
+    uint32_t* t = static_cast<uint32_t*>(trace);
+    if (mom)
+      refine_fold_frames<uint32_t, true><<<blocks, 256, 0, stream>>>(c, s, stride, nf, cnt, m, mask, tile_bits, t, w, npix, max_history);
+    else
+      refine_fold_frames<uint32_t, false><<<blocks, 256, 0, stream>>>(c, s, stride, nf, cnt, nullptr, mask, tile_bits, t, w, npix,
+                                                                      max_history);
   }
   return hipGetLastError();
 }

@@ -465,6 +465,36 @@ class HrtContext:
                                               ctypes.byref(settled)), "hrt_refine_until")
         return passes.value, frames.value, bool(settled.value)
 
+    def refine_tiles(self, pc: _lib.PushConstants, mask, max_history: int, frames: int = 1, moments: bool = True,
+                     want_stats: bool = True) -> Optional[_lib.RefineTilesStats]:
+        """hrt_refine_tiles: ``frames`` new frames (rng_offset pc.rng_offset, + 1, ...) for every pixel set in
+        ``mask`` (a uint32 array in host memory or an int device pointer) -- the state ``frames`` FRAME passes of
+        ``refine`` leave, traced over the 8x8 tiles that hold a selected pixel only.  Blocking."""
+        if isinstance(mask, np.ndarray):
+            mask = np.ascontiguousarray(mask, dtype=np.uint32)
+            assert mask.size >= self.mask_words
+            ptr = mask.ctypes.data
+        else:
+            ptr = int(mask)
+        st = _lib.RefineTilesStats()
+        self._check(self.lib.hrt_refine_tiles(self.handle, ctypes.byref(pc), ctypes.c_void_p(ptr), int(max_history),
+                                              int(frames), _lib.REFINE_MOMENTS if moments else 0,
+                                              ctypes.byref(st) if want_stats else None), "hrt_refine_tiles")
+        return st if want_stats else None
+
+    def refine_tiles_until(self, pc: _lib.PushConstants, max_history: int, max_passes: int, frames_per_pass: int = 1,
+                           guide_ptr: Optional[int] = None, rule: Optional[_lib.RefineRule] = None, **fields):
+        """hrt_refine_tiles_until: select, then one tile-masked pass of ``frames_per_pass`` frames, until nothing is
+        selected or max_passes have run; pass k starts at rng_offset pc.rng_offset + k * frames_per_pass.  Returns
+        (passes done, pixel-frames folded, settled)."""
+        rule = rule if rule is not None else self.refine_rule(**fields)
+        passes, frames, settled = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(self.lib.hrt_refine_tiles_until(self.handle, ctypes.byref(pc), ctypes.byref(rule),
+                                                    ctypes.c_void_p(guide_ptr or 0), int(max_history), int(max_passes),
+                                                    int(frames_per_pass), _lib.REFINE_MOMENTS, ctypes.byref(passes),
+                                                    ctypes.byref(frames), ctypes.byref(settled)), "hrt_refine_tiles_until")
+        return passes.value, frames.value, bool(settled.value)
+
     # ---- the variance-guided denoise (hrt_denoise_variance and the moments calls) ----
 
     def variance_info(self, iterations: Optional[int] = None, method: int = _lib.VARIANCE_AUTO,
@@ -996,6 +1026,16 @@ class DiffusePipeline:
             raise ValueError("pipeline must trace on the same context")
         return self.ctx.refine_until(pipeline.push_constants(camera, first_frame, False), max_history, max_passes,
                                      guide_ptr, method, **rule)
+
+    def refine_tiles_until(self, pipeline: "RayTracePipeline", camera: "Camera", first_frame: int, max_passes: int,
+                           frames_per_pass: int = 1, max_history: int = 1 << 24, guide_ptr: Optional[int] = None, **rule):
+        """``refine_until`` through the tile-masked passes (hrt_refine_tiles_until): each pass traces only the 8x8
+        tiles that hold a selected pixel, ``frames_per_pass`` frames at once; pass k uses the frames ``first_frame +
+        k * frames_per_pass`` onwards.  Returns (passes done, pixel-frames folded, settled)."""
+        if pipeline.ctx is not self.ctx:
+            raise ValueError("pipeline must trace on the same context")
+        return self.ctx.refine_tiles_until(pipeline.push_constants(camera, first_frame, False), max_history, max_passes,
+                                           frames_per_pass, guide_ptr, **rule)
 
     def variance_denoised(self, guide_ptr: Optional[int] = None, fmt: int = _lib.FMT_RGBA8, **fields) -> np.ndarray:
         """The accumulated image through the variance-guided denoise (hrt_denoise_variance), as uint8 or float32

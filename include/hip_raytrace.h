@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): adaptive refinement -- hrt_refine_rule, hrt_refine_method,
+/* 6, additive (no bump: nothing existing changed): tile-masked refinement -- HRT_REFINE_TILES_MAX_FRAMES,
+ * hrt_refine_tiles_stats, hrt_refine_tiles, hrt_refine_tiles_until.
+ * 6, additive (no bump: nothing existing changed): adaptive refinement -- hrt_refine_rule, hrt_refine_method,
  * HRT_REFINE_MOMENTS, hrt_refine_stats, hrt_refine_defaults, hrt_refine_select, hrt_refine, hrt_refine_until.
  * 6, additive (no bump: nothing existing changed): the variance-guided denoise -- hrt_variance_method,
  * hrt_variance_info, hrt_variance_defaults, hrt_accumulate_history_moments, hrt_reproject_moments, hrt_fill_moments,
@@ -427,6 +429,18 @@ typedef struct hrt_refine_stats { /* 48 bytes */
   uint64_t reserved;         /* 0 */
 } hrt_refine_stats;
 
+/* What one hrt_refine_tiles pass ran. */
+typedef struct hrt_refine_tiles_stats { /* 40 bytes */
+  uint32_t kernel_ran;     /* hrt_kernel of the pass's launches; 0: nothing was selected, nothing ran */
+  uint32_t whole_frame;    /* 1: the launches ran every tile (the fallback) */
+  uint32_t tiles;          /* 8x8 tiles of the image */
+  uint32_t tiles_selected; /* tiles with at least one selected real pixel */
+  uint32_t items;          /* work items of the masked plan per frame (0 when whole_frame) */
+  uint32_t reserved;       /* 0 */
+  uint64_t selected;       /* pixels whose bit is set */
+  uint64_t pixels_traced;  /* real pixels of the selected tiles (the image's pixels when whole_frame) */
+} hrt_refine_tiles_stats;
+
 /* The layouts every binding relies on (the Rust declarations in INTEGRATION.md are checked against
  * these by tests/test_rust_binding.py): std430 record sizes, the push block, and the host structs. */
 #ifdef __cplusplus
@@ -507,6 +521,11 @@ HRT_STATIC_ASSERT(sizeof(hrt_refine_stats) == 48 && offsetof(hrt_refine_stats, q
                       offsetof(hrt_refine_stats, segments) == 24 && offsetof(hrt_refine_stats, tri_tests) == 32 &&
                       offsetof(hrt_refine_stats, reserved) == 40,
                   "hrt_refine_stats");
+HRT_STATIC_ASSERT(sizeof(hrt_refine_tiles_stats) == 40 && offsetof(hrt_refine_tiles_stats, whole_frame) == 4 &&
+                      offsetof(hrt_refine_tiles_stats, tiles) == 8 && offsetof(hrt_refine_tiles_stats, tiles_selected) == 12 &&
+                      offsetof(hrt_refine_tiles_stats, items) == 16 && offsetof(hrt_refine_tiles_stats, reserved) == 20 &&
+                      offsetof(hrt_refine_tiles_stats, selected) == 24 && offsetof(hrt_refine_tiles_stats, pixels_traced) == 32,
+                  "hrt_refine_tiles_stats");
 HRT_STATIC_ASSERT(sizeof(hrt_first_hits_stats) == 48 && offsetof(hrt_first_hits_stats, reserved) == 4 &&
                       offsetof(hrt_first_hits_stats, tiles) == 8 && offsetof(hrt_first_hits_stats, tiles_listed) == 12 &&
                       offsetof(hrt_first_hits_stats, tiles_empty) == 16 &&
@@ -1213,6 +1232,41 @@ hrt_status hrt_refine(hrt_context* ctx, const hrt_push_constants* pc, const uint
 hrt_status hrt_refine_until(hrt_context* ctx, const hrt_push_constants* pc, const hrt_refine_rule* rule,
                             const hrt_hit* guide, uint32_t max_history, uint32_t max_passes, uint32_t method,
                             uint32_t flags, uint32_t* passes_done, uint64_t* pixel_frames, uint32_t* settled);
+
+/* ---- tile-masked refinement -----------------------------------------------------------
+ * hrt_refine_tiles(mask, frames = F) leaves the accumulator, N and -- with HRT_REFINE_MOMENTS -- M byte for byte
+ * as F successive hrt_refine(ctx, pc_f, mask, max_history, HRT_REFINE_FRAME, 0, flags, NULL) calls do, pc_f being
+ * pc with rng_offset + f, f = 0 .. F - 1 in order -- but its trace launches run only the 8x8 tiles that hold a
+ * selected real pixel (x < width, y < local rows), several frames per launch.  The mask is hrt_refine's in every
+ * respect.  The pass runs as hrt_compute_n's launches do: on lane 0's buffers and the context's stream, after the
+ * deferred combines and every lane's last trace, at most HRT_OPT_FRAMES_PER_LAUNCH frames per launch through the
+ * frame stack.  Every real pixel of a selected tile is traced (the fold stays per pixel under the mask); no pixel
+ * of any other tile is.  hrt_stats: traces grows by F, accumulates is unchanged, segments and tri_tests grow by
+ * the traced pixels' sums, last_kernel / last_block / last_frames are the last launch's.  No fold record is
+ * appended and no ticket is taken.  Afterwards HRT_IMG_TRACE is lane 0's image: the real pixels of the selected
+ * tiles hold frame rng_offset + F - 1's texels (exactly hrt_trace's), every other byte of it keeps what it held.
+ * Lane 0's tile costs and plan are read, never written: the masked launches plan in buffers of the context's own
+ * (allocated by the first call, freed by hrt_destroy), from lane 0's costs where it has them, else from a cost
+ * of 1 per tile; a later hrt_trace or hrt_compute_n plans as if the pass had not happened.
+ * stats->whole_frame = 1: the launches ran every tile (the same accumulator, N and M; the trace image is then
+ * frame rng_offset + F - 1 whole, and a persistent kernel's launches record lane 0's costs as hrt_compute_n's
+ * do) -- when the kernel the request resolves to is not persistent, the image has more than 2^22 - 1 tiles, or
+ * HRT_OPT_COUNTERS = 2 diagnostics are on.  With nothing selected nothing is enqueued beyond the count, the
+ * stats are zero and hrt_stats is untouched.  BLOCKING, as hrt_refine.  Rejected as hrt_refine rejects, before
+ * anything is enqueued; also frames 0 or above HRT_REFINE_TILES_MAX_FRAMES.
+ *
+ * hrt_refine_tiles_until is hrt_refine_until's loop with one hrt_refine_tiles pass of frames_per_pass frames
+ * (HRT_REFINE_MOMENTS forced) per selection: pass k starts at rng_offset + k * frames_per_pass, *pixel_frames
+ * grows by the selected count x frames_per_pass per pass.  With frames_per_pass = 1 every output and every byte
+ * of state is hrt_refine_until(..., HRT_REFINE_FRAME, ...)'s.  The selection is made once per pass, so a pixel
+ * can pass rule->max_count by up to frames_per_pass - 1 frames. */
+#define HRT_REFINE_TILES_MAX_FRAMES 4096u
+hrt_status hrt_refine_tiles(hrt_context* ctx, const hrt_push_constants* pc, const uint32_t* mask, uint32_t max_history,
+                            uint32_t frames, uint32_t flags, hrt_refine_tiles_stats* stats);
+hrt_status hrt_refine_tiles_until(hrt_context* ctx, const hrt_push_constants* pc, const hrt_refine_rule* rule,
+                                  const hrt_hit* guide, uint32_t max_history, uint32_t max_passes,
+                                  uint32_t frames_per_pass, uint32_t flags, uint32_t* passes_done,
+                                  uint64_t* pixel_frames, uint32_t* settled);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

@@ -380,6 +380,25 @@ class Context {
           "hrt_refine_until", get());
     return RefineResult{passes, frames, settled != 0};
   }
+  // tile-masked refinement (hrt_refine_tiles, hrt_refine_tiles_until): `frames` new frames for the pixels of a mask
+  // -- the state that many FRAME passes of refine leave -- traced over the 8x8 tiles that hold a selected pixel only
+  hrt_refine_tiles_stats refine_tiles(const hrt_push_constants& pc, const uint32_t* mask, uint32_t max_history,
+                                      uint32_t frames = 1, bool moments = true) {
+    hrt_refine_tiles_stats st{};
+    check(hrt_refine_tiles(get(), &pc, mask, max_history, frames, moments ? HRT_REFINE_MOMENTS : 0u, &st), "hrt_refine_tiles",
+          get());
+    return st;
+  }
+  // pass k selects, then runs one tile-masked pass of the frames pc.rng_offset + k frames_per_pass onwards
+  RefineResult refine_tiles_until(const hrt_push_constants& pc, const hrt_refine_rule& rule, const hrt_hit* guide,
+                                  uint32_t max_history, uint32_t max_passes, uint32_t frames_per_pass = 1) {
+    uint32_t passes = 0, settled = 0;
+    uint64_t frames = 0;
+    check(hrt_refine_tiles_until(get(), &pc, &rule, guide, max_history, max_passes, frames_per_pass, HRT_REFINE_MOMENTS,
+                                 &passes, &frames, &settled),
+          "hrt_refine_tiles_until", get());
+    return RefineResult{passes, frames, settled != 0};
+  }
   bool present_done(uint64_t ticket) const {
     uint32_t done = 0;
     check(hrt_present_done(get(), ticket, &done), "hrt_present_done", get());

@@ -4,7 +4,7 @@
 Input per side: the build directory `make asm` wrote its .s files into (epq_raytracer_amd/build) and the log of
 that `make asm` run (its -Rpass-analysis=kernel-resource-usage remarks).  Output: a record in the form of
 profiles/history_resources.txt -- for every kernel of the parent its resource row on both sides and whether its
-instruction stream (labels, directives and comments stripped) is the parent's line for line, then the kernels
+instruction stream (labels, directives and comments stripped, branch targets without the function's index) is the parent's line for line, then the kernels
 only the new build has.
 
   python tools/kernel_resources_diff.py PARENT_BUILD PARENT_LOG NEW_BUILD NEW_LOG > profiles/NAME.txt
@@ -52,7 +52,9 @@ def streams(build):
                 continue
             if not s or s.startswith(".") or s.endswith(":"):
                 continue
-            body.append(s)
+            # a branch target .LBB<f>_<b> names block b of the unit's f-th function: f moves when a kernel is added
+            # to the unit ahead of this one, the code does not
+            body.append(re.sub(r"\.LBB\d+_(\d+)", r".LBB_\1", s))
     return out
 
 
