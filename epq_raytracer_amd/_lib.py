@@ -201,6 +201,18 @@ VARIANCE_SIGMA, VARIANCE_FLOOR, VARIANCE_MIN_HISTORY = 4.0, 1e-10, 4  # HRT_VARI
 VARIANCE_MAX_ITERATIONS = 5  # steps 1, 2, 4, 8, 16 (0 iterations: the source and the variance estimate)
 
 
+class UpsampleInfo(ctypes.Structure):
+    """hrt_upsample_info: one guided upsample (32 bytes)."""
+
+    _fields_ = [("image_id", c_uint32), ("width", c_uint32), ("height", c_uint32), ("footprint", c_uint32),
+                ("flags", c_uint32), ("sigma_normal", c_float), ("sigma_depth", c_float), ("reserved", c_uint32)]
+
+
+assert ctypes.sizeof(UpsampleInfo) == 32
+UPSAMPLE_FOOTPRINT = 2  # HRT_UPSAMPLE_FOOTPRINT (hrt_upsample_defaults)
+UPSAMPLE_MAX_DIM = 16384  # the largest width / height of a result
+
+
 class FirstHitsStats(ctypes.Structure):
     """hrt_first_hits_stats: what the last counted hrt_first_hits call ran (48 bytes)."""
 
@@ -328,6 +340,7 @@ EXPORTED_SYMBOLS = (
     "hrt_read_moments", "hrt_denoise_variance", "hrt_denoise_variance_present",
     "hrt_refine_defaults", "hrt_refine_select", "hrt_refine", "hrt_refine_until",
     "hrt_refine_tiles", "hrt_refine_tiles_until",
+    "hrt_upsample_defaults", "hrt_upsample", "hrt_upsample_present", "hrt_order_after",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -431,6 +444,12 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_denoise_variance": (c_int32, [P, POINTER(VarianceInfo), P, c_uint32, P, c_size_t, P, c_size_t]),
         "hrt_denoise_variance_present": (c_int32, [P, POINTER(VarianceInfo), P, POINTER(PresentInfo), P, c_uint64,
                                                    POINTER(c_uint64)]),
+        "hrt_upsample_defaults": (None, [POINTER(UpsampleInfo), c_uint32, c_uint32]),
+        "hrt_upsample": (c_int32, [P, POINTER(UpsampleInfo), POINTER(DenoiseInfo), POINTER(VarianceInfo), P, P, c_uint32, P,
+                                   c_size_t]),
+        "hrt_upsample_present": (c_int32, [P, POINTER(UpsampleInfo), POINTER(DenoiseInfo), POINTER(VarianceInfo), P, P,
+                                           POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
+        "hrt_order_after": (c_int32, [P, P]),
         "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
         "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),

@@ -25,6 +25,7 @@
 #include "hrt_context.h"
 #include "hrt_denoise.h"
 #include "hrt_history.h"
+#include "hrt_upsample.h"
 #include "hrt_variance.h"
 #include "hrt_refine.h"
 #include "hrt_host.h"
@@ -501,6 +502,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->hist_mom);
   free_dev(ctx, ctx->hist_mom_next);
   free_dev(ctx, ctx->var_stage);
+  free_dev(ctx, ctx->up_stage);
   free_dev(ctx, ctx->rf_mask);
   free_dev(ctx, ctx->rf_queries);
   free_dev(ctx, ctx->rf_index);
@@ -516,6 +518,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->fh_cam_cull);
   free_dev(ctx, ctx->fh_stats);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
+  if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) {
@@ -2338,6 +2341,161 @@ extern "C" hrt_status hrt_denoise_variance_present(hrt_context* ctx, const hrt_v
   // the filtered float image through the present pass unchanged
   HRT_HIP(ctx, hrt::launch_present(res, true, ctx->width, ctx->local_rows, present_target(target, dst), ctx->stream));
   return ticket_end(ctx, ev, ticket);
+}
+
+// ---- guided upsampling (kernel in hrt_upsample.hip) ------------------------------------
+namespace {
+
+constexpr uint32_t kUpsampleMaxDim = 16384;
+
+// Every check of hrt_upsample / hrt_upsample_present that concerns the pass itself, on the host: its own
+// arguments, then the given filter's (check_denoise / check_variance with low_hits as the guide).
+hrt_status check_upsample(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                          const hrt_variance_info* variance, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                          const char* who) {
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!info) return bad("null info");
+  if (!low_hits || !high_hits) return bad("null low_hits or high_hits");
+  if (denoise && variance) return bad("at most one of denoise and variance may be given");
+  if (ctx->comm || ctx->part_count > 1)
+    return bad("a context of a row-tile partition or joined to a communicator cannot upsample (a tap's neighbour rows "
+               "live on another part; the gathered form is out of scope)");
+  if (info->image_id != HRT_IMG_ACCUM && info->image_id != HRT_IMG_TRACE) return bad("unknown image id");
+  if (info->footprint != 2 && info->footprint != 4) return bad("footprint must be 2 or 4");
+  if (info->flags != 0) return bad("flags must be 0");
+  for (const float s : {info->sigma_normal, info->sigma_depth})
+    if (!(std::isfinite(s) && s > 0.0f)) return bad("every sigma must be finite and greater than 0");
+  if (info->width == 0 || info->height == 0 || info->width > kUpsampleMaxDim || info->height > kUpsampleMaxDim)
+    return bad("width / height must be 1..16384");
+  if (ctx->width > (1u << 24) || ctx->local_rows > (1u << 24)) return bad("the context's image is wider or taller than 2^24");
+  if (denoise && denoise->image_id != info->image_id) return bad("the denoise filter's image_id differs from info's");
+  if (variance && info->image_id != HRT_IMG_ACCUM) return bad("the variance filter reads the accumulator: image_id must be HRT_IMG_ACCUM");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if ((uintptr_t)low_hits % 16 != 0 || (uintptr_t)high_hits % 16 != 0) return bad("low_hits and high_hits must be 16-byte aligned");
+  if (!query_direct(ctx, low_hits) || !query_direct(ctx, low_hits + (ctx->npix() - 1)))
+    return bad("low_hits must be the context's width x height records in memory of the context's device");
+  const size_t nt = (size_t)info->width * info->height;
+  if (!query_direct(ctx, high_hits) || !query_direct(ctx, high_hits + (nt - 1)))
+    return bad("high_hits must be info->width x info->height records in memory of the context's device");
+  if (denoise) return check_denoise(ctx, denoise, low_hits, who);
+  if (variance) return check_variance(ctx, variance, low_hits, who);
+  return HRT_OK;
+}
+
+// The pass on ctx->stream, after everything that wrote the source image (arguments already checked): the given
+// filter as enqueue_denoise / enqueue_variance run it with out = nullptr, or launch_denoise_prep alone; then the
+// kernel, from the float image and the compact guide and keys in the context's scratch, into `out`.
+hrt_status enqueue_upsample(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                            const hrt_variance_info* variance, const hrt_hit* low_hits, const hrt_hit* high_hits, void* out,
+                            int out_kind, uint32_t pitch, uint32_t bgra, const char* who) {
+  hrt_status st;
+  void* low = nullptr;
+  if (denoise) {
+    if ((st = enqueue_denoise(ctx, denoise, low_hits, nullptr, false, &low, who)) != HRT_OK) return st;
+  } else if (variance) {
+    if ((st = enqueue_variance(ctx, variance, low_hits, nullptr, false, nullptr, &low, who)) != HRT_OK) return st;
+  } else {
+    const size_t np = ctx->npix();
+    if ((st = ensure_staging(ctx, &ctx->dn_img[0], np * 16, who)) != HRT_OK) return st;
+    if ((st = ensure_staging(ctx, &ctx->dn_guide, np * 16, who)) != HRT_OK) return st;
+    if ((st = ensure_staging(ctx, &ctx->dn_keys, np * 4, who)) != HRT_OK) return st;
+    const void* src = hrt::local_image(ctx, info->image_id);
+    if (!src) return fail(ctx, HRT_ERR_HIP, std::string(who) + ": lane wait failed");
+    HRT_HIP(ctx, hrt::launch_denoise_prep(src, ctx->f32(), low_hits, ctx->dn_img[0], ctx->dn_guide, ctx->dn_keys, np, ctx->stream));
+    if (info->image_id == HRT_IMG_TRACE) {
+      // prep was the source's only reader: the trace image's next writer follows it (enqueue_denoise's rule)
+      if (ctx->cur_slot >= 0) {
+        HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+        ctx->fold_set = true;
+      }
+      if ((st = hrt::release_lane(ctx, ctx->cur_lane)) != HRT_OK) return st;
+    }
+    low = ctx->dn_img[0];
+  }
+  // S19's host constant, one rounded float operation
+  const hrt::UpsamplePass p{low, ctx->dn_guide, ctx->dn_keys, high_hits, out, out_kind, ctx->width, ctx->local_rows,
+                            info->width, info->height, pitch, bgra, info->footprint, 1.0f / info->sigma_normal,
+                            info->sigma_depth};
+  HRT_HIP(ctx, hrt::launch_upsample(p, ctx->stream));
+  return HRT_OK;
+}
+
+}  // namespace
+
+extern "C" void hrt_upsample_defaults(hrt_upsample_info* info, uint32_t width, uint32_t height) {
+  if (!info) return;
+  *info = hrt_upsample_info{HRT_IMG_ACCUM, width, height, HRT_UPSAMPLE_FOOTPRINT, 0u, HRT_DENOISE_SIGMA_NORMAL,
+                            HRT_DENOISE_SIGMA_DEPTH, 0u};
+}
+
+extern "C" hrt_status hrt_upsample(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                                   const hrt_variance_info* variance, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                                   uint32_t fmt, void* dst, size_t bytes) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_upsample";
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  hrt_status st = check_upsample(ctx, info, denoise, variance, low_hits, high_hits, who);
+  if (st != HRT_OK) return st;
+  if (fmt != HRT_FMT_RGBA8 && fmt != HRT_FMT_RGBA32F) return bad("unknown format");
+  if (!dst) return bad("null destination");
+  const bool rgba8 = fmt == HRT_FMT_RGBA8;
+  const size_t need = (size_t)info->width * info->height * (rgba8 ? 4 : 16);
+  if (bytes < need) return bad("destination too small");
+  // device memory a texel store may address: the kernel writes it; anything else is copied from the staging image
+  const bool direct = (uintptr_t)dst % (rgba8 ? 4 : 16) == 0 && query_direct(ctx, dst) &&
+                      query_direct(ctx, static_cast<const char*>(dst) + (need - 1));
+  void* out = dst;
+  if (!direct) {
+    if (ctx->up_stage && ctx->up_stage_bytes < need) {  // (the call is blocking: no earlier result is in flight)
+      free_dev(ctx, ctx->up_stage);
+      ctx->up_stage_bytes = 0;
+    }
+    if ((st = ensure_staging(ctx, &ctx->up_stage, need, who)) != HRT_OK) return st;
+    if (ctx->up_stage_bytes < need) ctx->up_stage_bytes = need;
+    out = ctx->up_stage;
+  }
+  if ((st = enqueue_upsample(ctx, info, denoise, variance, low_hits, high_hits, out,
+                             rgba8 ? hrt::kUpsampleOutRgba8 : hrt::kUpsampleOutFloat, 0u, 0u, who)) != HRT_OK)
+    return st;
+  if (!direct) HRT_HIP(ctx, hipMemcpyAsync(dst, out, need, hipMemcpyDefault, ctx->stream));
+  HRT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_upsample_present(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                                           const hrt_variance_info* variance, const hrt_hit* low_hits,
+                                           const hrt_hit* high_hits, const hrt_present_info* target, void* dst,
+                                           uint64_t dst_bytes, uint64_t* ticket) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_upsample_present";
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  hrt_status st = check_upsample(ctx, info, denoise, variance, low_hits, high_hits, who);
+  if (st != HRT_OK) return st;
+  if ((st = check_present(ctx, target, dst, dst_bytes, ticket, false, who)) != HRT_OK) return st;
+  if (target->image_id != info->image_id) return bad("the target's image_id differs from info's");
+  if (target->width != info->width || target->height != info->height) return bad("the target's size differs from info's");
+  hipEvent_t ev = nullptr;
+  if ((st = ticket_begin(ctx, &ev)) != HRT_OK) return st;
+  // the kernel writes the flipped, swizzled target pixel: the result is never written to memory and read back
+  if ((st = enqueue_upsample(ctx, info, denoise, variance, low_hits, high_hits, dst, hrt::kUpsampleOutPresent, target->pitch,
+                             target->format == HRT_PRESENT_B8G8R8A8 ? 1u : 0u, who)) != HRT_OK)
+    return st;
+  return ticket_end(ctx, ev, ticket);
+}
+
+extern "C" hrt_status hrt_order_after(hrt_context* ctx, hrt_context* producer) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  if (!producer) return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_order_after: null producer");
+  if (ctx == producer) return HRT_OK;
+  if (ctx->device != producer->device)
+    return fail(ctx, HRT_ERR_INVALID_ARGUMENT, "hrt_order_after: the two contexts are on different devices");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if (!producer->order_ev) HRT_HIP(ctx, hipEventCreateWithFlags(&producer->order_ev, hipEventDisableTiming));
+  HRT_HIP(ctx, hipEventRecord(producer->order_ev, producer->stream));
+  HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, producer->order_ev, 0));
+  return HRT_OK;
 }
 
 // ---- adaptive refinement (kernels in hrt_refine.hip) ------------------------------------

@@ -247,6 +247,12 @@ struct hrt_context {
   float* hist_mom = nullptr;
   float* hist_mom_next = nullptr;
   float* var_stage = nullptr;
+  // Guided upsampling (hrt_upsample, hrt_upsample_present, hrt_order_after): the staging image of a result that
+  // goes to host memory (up_stage_bytes of it, grown when a larger result comes), and the event hrt_order_after
+  // records on this context's stream when it is the producer.  Each is made by the first call that needs it
+  void* up_stage = nullptr;
+  size_t up_stage_bytes = 0;
+  hipEvent_t order_ev = nullptr;
   // The adaptive refinement (hrt_refine_select, hrt_refine, hrt_refine_until): the mask's staging (one bit per pixel)
   // for a mask in host memory and for hrt_refine_until's own; the compact lists of a QUERIES pass (npix entries:
   // hrt_radiance_query records, pixel indices, results); and two 64-bit words: the selected count, then the

@@ -352,6 +352,67 @@ class HrtContext:
                                                  ctypes.byref(t)), "hrt_denoise_present")
         return t.value
 
+    # ---- guided upsampling (hrt_upsample, hrt_upsample_present, hrt_order_after) ----
+
+    def upsample_info(self, width: int, height: int, image_id: int = _lib.IMG_ACCUM, footprint: Optional[int] = None,
+                      sigma_normal: Optional[float] = None, sigma_depth: Optional[float] = None) -> _lib.UpsampleInfo:
+        """hrt_upsample_defaults for a width x height result with the given fields replaced (None: the default)."""
+        info = _lib.UpsampleInfo()
+        self.lib.hrt_upsample_defaults(ctypes.byref(info), int(width), int(height))
+        info.image_id = int(image_id)
+        if footprint is not None:
+            info.footprint = int(footprint)
+        for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+            if v is not None:
+                setattr(info, name, float(v))
+        return info
+
+    def upsample_into(self, dst_ptr: int, nbytes: int, width: int, height: int, low_hits_ptr: int, high_hits_ptr: int,
+                      fmt: int = _lib.FMT_RGBA8, denoise: Optional[_lib.DenoiseInfo] = None,
+                      variance: Optional[_lib.VarianceInfo] = None, info: Optional[_lib.UpsampleInfo] = None, **fields):
+        """hrt_upsample into caller memory (host or device pointer): this context's image at width x height, a
+        joint-bilateral reconstruction guided by low_hits_ptr (this context's W x H hrt_hit records)
+        and high_hits_ptr (width x height records of the same view), both 16-byte aligned device pointers.
+        ``denoise`` or ``variance`` (at most one): that filter runs over the low image first.  ``info`` or the
+        fields of ``upsample_info``.  Blocking."""
+        info = info if info is not None else self.upsample_info(width, height, **fields)
+        self._check(self.lib.hrt_upsample(self.handle, ctypes.byref(info),
+                                          ctypes.byref(denoise) if denoise is not None else None,
+                                          ctypes.byref(variance) if variance is not None else None,
+                                          ctypes.c_void_p(low_hits_ptr or 0), ctypes.c_void_p(high_hits_ptr or 0), int(fmt),
+                                          ctypes.c_void_p(dst_ptr), int(nbytes)), "hrt_upsample")
+
+    def upsample(self, width: int, height: int, low_hits_ptr: int, high_hits_ptr: int, fmt: int = _lib.FMT_RGBA8,
+                 denoise: Optional[_lib.DenoiseInfo] = None, variance: Optional[_lib.VarianceInfo] = None,
+                 info: Optional[_lib.UpsampleInfo] = None, **fields) -> np.ndarray:
+        """hrt_upsample: the reconstructed image as uint8 or float32 (height, width, 4)."""
+        out = np.empty((int(height), int(width), 4), dtype=np.uint8 if fmt == _lib.FMT_RGBA8 else np.float32)
+        self.upsample_into(out.ctypes.data, out.nbytes, width, height, low_hits_ptr, high_hits_ptr, fmt, denoise, variance,
+                           info, **fields)
+        return out
+
+    def upsample_present(self, dst_ptr: int, nbytes: int, width: int, height: int, low_hits_ptr: int, high_hits_ptr: int,
+                         pitch: Optional[int] = None, fmt: int = _lib.PRESENT_B8G8R8A8,
+                         denoise: Optional[_lib.DenoiseInfo] = None, variance: Optional[_lib.VarianceInfo] = None,
+                         info: Optional[_lib.UpsampleInfo] = None, **fields) -> int:
+        """hrt_upsample_present: the reconstruction written straight into the width x height target as ``present``
+        writes an image of the target's size (same target rules, same ticket sequence); returns the ticket without
+        waiting."""
+        info = info if info is not None else self.upsample_info(width, height, **fields)
+        target, t = self._present_info(info.image_id, width, height, pitch, fmt), ctypes.c_uint64()
+        self._check(self.lib.hrt_upsample_present(self.handle, ctypes.byref(info),
+                                                  ctypes.byref(denoise) if denoise is not None else None,
+                                                  ctypes.byref(variance) if variance is not None else None,
+                                                  ctypes.c_void_p(low_hits_ptr or 0), ctypes.c_void_p(high_hits_ptr or 0),
+                                                  ctypes.byref(target), ctypes.c_void_p(dst_ptr), int(nbytes),
+                                                  ctypes.byref(t)), "hrt_upsample_present")
+        return t.value
+
+    def order_after(self, producer: "HrtContext"):
+        """hrt_order_after: work issued on this context from now on follows everything issued so far on
+        ``producer``'s stream (an event and a stream wait; no host wait).  Both must be on one device."""
+        self._check(self.lib.hrt_order_after(self.handle, producer.handle), "hrt_order_after")
+
     # ---- temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history) ----
 
     def reproject_info(self, filter: Optional[int] = None, depth_tolerance: Optional[float] = None,  # noqa: A002
@@ -872,6 +933,23 @@ class RenderPassOverFrame:
             raise ValueError("the target's format differs from the render pass's output format")
         return self.ctx.denoise_variance_present(target.ptr, target.nbytes, target.width, target.height, target.pitch,
                                                  target.format, guide_ptr, **fields)
+
+
+    def render_upsampled(self, view: Image, target: PresentTarget, low_hits_ptr: int, high_hits_ptr: int,
+                         producer: Optional[HrtContext] = None, **fields) -> int:
+        """``render`` of a view traced below the target's size (hrt_upsample_present): the image reconstructed at
+        target.width x target.height, guided by the view's own first hits (low_hits_ptr) and the target-size ones
+        (high_hits_ptr) of the same camera.  ``producer``: the context whose stream wrote high_hits_ptr -- the pass
+        is ordered after it (``HrtContext.order_after``).  ``fields`` as ``HrtContext.upsample_present`` takes them
+        (footprint, sigmas, denoise, variance).  Returns the ticket."""
+        if view.ctx is not self.ctx:
+            raise ValueError("view must be an image of the render pass's context")
+        if target.format != self.output_format:
+            raise ValueError("the target's format differs from the render pass's output format")
+        if producer is not None:
+            self.ctx.order_after(producer)
+        return self.ctx.upsample_present(target.ptr, target.nbytes, target.width, target.height, low_hits_ptr,
+                                         high_hits_ptr, target.pitch, target.format, image_id=view.image_id, **fields)
 
 
 # ---- pipelines ---------------------------------------------------------------------------------

@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): tile-masked refinement -- HRT_REFINE_TILES_MAX_FRAMES,
+/* 6, additive (no bump: nothing existing changed): guided upsampling -- HRT_UPSAMPLE_FOOTPRINT, hrt_upsample_info,
+ * hrt_upsample_defaults, hrt_upsample, hrt_upsample_present, hrt_order_after.
+ * 6, additive (no bump: nothing existing changed): tile-masked refinement -- HRT_REFINE_TILES_MAX_FRAMES,
  * hrt_refine_tiles_stats, hrt_refine_tiles, hrt_refine_tiles_until.
  * 6, additive (no bump: nothing existing changed): adaptive refinement -- hrt_refine_rule, hrt_refine_method,
  * HRT_REFINE_MOMENTS, hrt_refine_stats, hrt_refine_defaults, hrt_refine_select, hrt_refine, hrt_refine_until.
@@ -373,6 +375,19 @@ typedef struct hrt_variance_info { /* 32 bytes */
   float sigma_depth;
 } hrt_variance_info;
 
+/* ---- guided upsampling (hrt_upsample, hrt_upsample_present) ---- */
+#define HRT_UPSAMPLE_FOOTPRINT 2u /* hrt_upsample_defaults' footprint */
+typedef struct hrt_upsample_info { /* 32 bytes */
+  uint32_t image_id;  /* HRT_IMG_ACCUM / HRT_IMG_TRACE: the low image; a filter given with it must read the same */
+  uint32_t width;     /* the result's and the high guide's size, each 1..16384 */
+  uint32_t height;
+  uint32_t footprint; /* 2 or 4: the taps per axis */
+  uint32_t flags;     /* must be 0 */
+  float sigma_normal; /* finite, > 0; as hrt_denoise_info */
+  float sigma_depth;
+  uint32_t reserved;  /* ignored */
+} hrt_upsample_info;
+
 /* ---- the first-hit pass (hrt_first_hits) ---- */
 typedef enum hrt_first_hits_method {
   HRT_FIRST_HITS_AUTO = 0,  /* TILES: it measured faster on island and on cave */
@@ -503,6 +518,10 @@ HRT_STATIC_ASSERT(sizeof(hrt_view) == 128 && offsetof(hrt_view, cam_alignment_ma
                       offsetof(hrt_view, grid_first) == 80 && offsetof(hrt_view, grid_dx) == 96 &&
                       offsetof(hrt_view, grid_dy) == 112,
                   "hrt_view");
+HRT_STATIC_ASSERT(sizeof(hrt_upsample_info) == 32 && offsetof(hrt_upsample_info, width) == 4 &&
+                      offsetof(hrt_upsample_info, footprint) == 12 && offsetof(hrt_upsample_info, flags) == 16 &&
+                      offsetof(hrt_upsample_info, sigma_normal) == 20 && offsetof(hrt_upsample_info, reserved) == 28,
+                  "hrt_upsample_info");
 HRT_STATIC_ASSERT(sizeof(hrt_variance_info) == 32 && offsetof(hrt_variance_info, method) == 4 &&
                       offsetof(hrt_variance_info, min_history) == 12 && offsetof(hrt_variance_info, sigma_variance) == 16 &&
                       offsetof(hrt_variance_info, variance_floor) == 20 && offsetof(hrt_variance_info, sigma_depth) == 28,
@@ -1267,6 +1286,47 @@ hrt_status hrt_refine_tiles_until(hrt_context* ctx, const hrt_push_constants* pc
                                   const hrt_hit* guide, uint32_t max_history, uint32_t max_passes,
                                   uint32_t frames_per_pass, uint32_t flags, uint32_t* passes_done,
                                   uint64_t* pixel_frames, uint32_t* settled);
+/* ---- guided upsampling ----
+ * hrt_upsample shows the context's width x height image at info->width x info->height: a joint-bilateral
+ * reconstruction guided by the first hits of both resolutions.  low_hits are the context's own width x height
+ * records, high_hits info->width x info->height records in trace-image row order, both in memory of the context's
+ * device, 16-byte aligned -- typically hrt_first_hits of this context and of a second context of the target's size.
+ * The mapping assumes that both grids come from the same viewport (hrt_host_ray_grid puts pixel centres at
+ * (i + 0.5) / W): the caller must give both contexts the same camera, focal length and viewport height.  Nothing
+ * polices it.  A target pixel takes the footprint x footprint low texels around its centre, each weighted by a tent
+ * and S14's normal and depth weights against the pixel's own high record, taps of another surface key skipped; a
+ * pixel that keeps no weight takes hrt_present's nearest texel.  Sizes larger, equal and smaller than the source are
+ * all defined.
+ *
+ * denoise and variance are optional and at most one may be given: that filter runs first over the low image with
+ * low_hits as its guide, exactly as hrt_denoise / hrt_denoise_variance run it, and the upsample reads its float
+ * result; its image (denoise->image_id; the accumulator for variance) must be info->image_id and all of its own
+ * rejections apply.  With neither, the low image is info->image_id's texels as float (S14's C0).
+ *
+ * hrt_upsample is BLOCKING, like hrt_denoise: it writes height x width texels in fmt (HRT_FMT_RGBA8 by S7's store
+ * with alpha 255, HRT_FMT_RGBA32F with alpha 1.0f) to host or device memory -- directly when dst is addressable
+ * device memory, else through a context-owned staging image.  hrt_upsample_present is NON-blocking; tickets and
+ * the writable-memory rule are hrt_present's; target->width / height must equal info->width / height and
+ * target->image_id info->image_id; the target holds what hrt_present's equal-size rule makes of the result,
+ * dst(x, y) = U(x, height - 1 - y) in target->format's byte order.  The kernel writes the target directly.
+ * Neither changes an image, hrt_stats, a counter, a fold record, N or M; the scratch is the denoise pass's.
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL info, low_hits, high_hits or
+ * destination; both filters; a footprint other than 2 or 4; flags != 0; a sigma that is not finite or not > 0; a
+ * size of 0 or above 16384; an unknown fmt or image id; hit arrays that are not memory of the context's device or
+ * not 16-byte aligned; a destination that is too small; a target whose size or image_id disagrees; a context of a
+ * row-tile partition or joined to a communicator. */
+void hrt_upsample_defaults(hrt_upsample_info* info, uint32_t width, uint32_t height);
+hrt_status hrt_upsample(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                        const hrt_variance_info* variance, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                        uint32_t fmt, void* dst, size_t bytes);
+hrt_status hrt_upsample_present(hrt_context* ctx, const hrt_upsample_info* info, const hrt_denoise_info* denoise,
+                                const hrt_variance_info* variance, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                                const hrt_present_info* target, void* dst, uint64_t dst_bytes, uint64_t* ticket);
+/* Work issued on ctx after the call is ordered after everything issued so far on producer's context stream: one
+ * event that producer owns, recorded on its stream, and a stream wait on ctx's.  No host wait.  A no-op when the
+ * two are the same context; two contexts on different devices are rejected.  (A context that upsamples takes its
+ * high-resolution first hits from a second context: this orders the two without hrt_synchronize.) */
+hrt_status hrt_order_after(hrt_context* ctx, hrt_context* producer);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

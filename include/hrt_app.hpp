@@ -269,6 +269,38 @@ class Context {
     check(hrt_denoise_present(get(), &info, guide, &target, dst, dst_bytes, &ticket), "hrt_denoise_present", get());
     return ticket;
   }
+  // guided upsampling (hrt_upsample; not a reference feature): this context's image at info.width x info.height, a
+  // joint-bilateral reconstruction guided by low_hits (this context's width x height records) and high_hits
+  // (info.width x info.height records of the same view: the first hits of a second context of that size with the
+  // same camera, focal length and viewport height), both in memory of the context's device, 16-byte aligned.
+  // denoise / variance: at most one, run over the low image first.  Blocking.
+  static hrt_upsample_info upsample_defaults(uint32_t width, uint32_t height, hrt_image_id image = HRT_IMG_ACCUM) {
+    hrt_upsample_info info;
+    hrt_upsample_defaults(&info, width, height);
+    info.image_id = (uint32_t)image;
+    return info;
+  }
+  std::vector<uint8_t> upsample(const hrt_upsample_info& info, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                                hrt_format fmt, const hrt_denoise_info* denoise = nullptr,
+                                const hrt_variance_info* variance = nullptr) {
+    std::vector<uint8_t> out((size_t)info.height * info.width * (fmt == HRT_FMT_RGBA8 ? 4 : 16));
+    check(hrt_upsample(get(), &info, denoise, variance, low_hits, high_hits, fmt, out.data(), out.size()), "hrt_upsample",
+          get());
+    return out;
+  }
+  // ... written straight into a target of info's size as the present pass writes it (hrt_upsample_present):
+  // enqueued, not waited for; returns the ticket
+  uint64_t upsample_present(const hrt_upsample_info& info, const hrt_hit* low_hits, const hrt_hit* high_hits,
+                            const hrt_present_info& target, void* dst, uint64_t dst_bytes,
+                            const hrt_denoise_info* denoise = nullptr, const hrt_variance_info* variance = nullptr) {
+    uint64_t ticket = 0;
+    check(hrt_upsample_present(get(), &info, denoise, variance, low_hits, high_hits, &target, dst, dst_bytes, &ticket),
+          "hrt_upsample_present", get());
+    return ticket;
+  }
+  // work issued on this context from now on follows everything issued so far on producer's stream (hrt_order_after:
+  // an event and a stream wait, no host wait) -- e.g. the first_hits_enqueue that writes high_hits
+  void order_after(Context& producer) { check(hrt_order_after(get(), producer.get()), "hrt_order_after", get()); }
   // temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history; not a reference
   // feature).  The hit arrays are width x height hrt_hit records in memory of the context's device, 16-byte
   // aligned (RayTracePipeline::first_hits_into under each view); reproject, accumulate_history and fill_history
@@ -489,6 +521,24 @@ class RenderPassOverFrame {
     const hrt_present_info pi{(uint32_t)HRT_IMG_ACCUM, (uint32_t)target.format, target.width, target.height,
                               target.pitch ? target.pitch : target.width * 4u, 0u};
     return ctx_->denoise_variance_present(vi, guide, pi, target.ptr, target.nbytes);
+  }
+  // render() of a view traced below the target's size (hrt_upsample_present): reconstructed at the target's size,
+  // guided by the view's own first hits and the target-size ones of the same camera; info null:
+  // hrt_upsample_defaults (its size and image_id are set to the target's and the view's either way).  producer: the
+  // context whose stream wrote high_hits -- the pass is ordered after it.
+  uint64_t render_upsampled(const Image& view, const PresentTarget& target, const hrt_hit* low_hits,
+                            const hrt_hit* high_hits, Context* producer = nullptr, const hrt_upsample_info* info = nullptr) {
+    if (view.ctx != ctx_) throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: view must be an image of the pass's context");
+    if (target.format != format_)
+      throw HrtError(HRT_ERR_INVALID_ARGUMENT, "render: the target's format differs from the pass's output format");
+    hrt_upsample_info up = info ? *info : Context::upsample_defaults(target.width, target.height);
+    up.image_id = (uint32_t)view.id;
+    up.width = target.width;
+    up.height = target.height;
+    const hrt_present_info pi{(uint32_t)view.id, (uint32_t)target.format, target.width, target.height,
+                              target.pitch ? target.pitch : target.width * 4u, 0u};
+    if (producer) ctx_->order_after(*producer);
+    return ctx_->upsample_present(up, low_hits, high_hits, pi, target.ptr, target.nbytes);
   }
 
  private:

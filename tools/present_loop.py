@@ -33,6 +33,12 @@ and writes profiles/present_loop_history.jsonl with f / e, g / e, h / e, f - g a
   i  h with the three moments calls in place of the plain ones: hrt_reproject_moments,
      hrt_accumulate_history_moments and hrt_denoise_variance_present (the variance-guided filter, defaults)
 and writes profiles/present_loop_variance.jsonl with i / h and i - h.
+--upsample runs two variants of the moving loop only, taking turns in one sitting: i, and
+  j  i with the trace, the history and the filter on a context of half the size (960x540): hrt_first_hits of the
+     half-size view on that context, hrt_first_hits of the full-size view on a second, full-size context of the same
+     scene into two alternating buffers, hrt_order_after between the two, and hrt_upsample_present (the variance-guided
+     filter first, default footprint) in place of the present
+and writes profiles/present_loop_upsample.jsonl with j / i, j - i and whether the two ranges are apart.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -51,6 +57,7 @@ VARIANTS = ("a", "b", "c", "d")
 DENOISE_VARIANTS = ("c", "e")
 MOVING_VARIANTS = ("e", "f", "g", "h")
 VARIANCE_VARIANTS = ("h", "i")
+UPSAMPLE_VARIANTS = ("i", "j")
 MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
@@ -64,17 +71,18 @@ def child(variant: str, parts: int = 1) -> dict:
     import epq_raytracer_amd as E
     from epq_raytracer_amd import _lib
 
-    W, H = SIZE
+    W, H = SIZE  # the targets' size
+    size = (W // 2, H // 2) if variant == "j" else SIZE  # the rendering context's
     camera, settings = E.preset(SCENE)
     settings.num_samples, settings.max_bounces = SPP, BOUNCES
     if parts > 1:
         ctxs = [E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8, partition=(ROW_TILE, p, parts))
                 for p in range(parts)]
     else:
-        ctxs = [E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)]
+        ctxs = [E.HrtContext(size, device=0, mode=_lib.MODE_RGBA8)]
     ctx = ctxs[0]  # the root: presents, reads and holds the tickets
-    raytraces = [E.RayTracePipeline(c, SIZE, settings) for c in ctxs]
-    diffuses = [E.DiffusePipeline(c, SIZE) for c in ctxs]
+    raytraces = [E.RayTracePipeline(c, size, settings) for c in ctxs]
+    diffuses = [E.DiffusePipeline(c, size) for c in ctxs]
     if parts > 1:
         E.HrtContext.comm_init_all(ctxs)
     targets = [torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0") for _ in range(LAG + 1)]
@@ -88,18 +96,24 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
-    moving = variant in ("f", "g", "h", "i")
+    moving = variant in ("f", "g", "h", "i", "j")
     if moving:
         import numpy as np
 
         # first hits of the previous and the current view: LAG + 2 buffers, so that one the enqueued passes of
         # the last LAG frames still read is never overwritten
         # (h: two -- its passes are ordered on the stream behind the readers of the buffer they overwrite)
-        guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2 if variant in ("h", "i") else LAG + 2)]
+        guides = [torch.empty((size[0] * size[1], 8), dtype=torch.float32, device="cuda:0")
+                  for _ in range(2 if variant in ("h", "i", "j") else LAG + 2)]
         guide_ctx, guide_rt = ctx, raytraces[0]
         if variant == "g":
             guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
             guide_rt = E.RayTracePipeline(guide_ctx, SIZE, settings)
+        if variant == "j":  # the full-size view's first hits: a second context, two alternating buffers
+            high_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
+            high_rt = E.RayTracePipeline(high_ctx, SIZE, settings)
+            high_guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2)]
+            vinfo = ctx.variance_info()
         d0 = np.asarray(camera.direction, np.float64) / np.linalg.norm(camera.direction)
         side = np.cross(d0, np.asarray(camera.up, np.float64))
         side /= np.linalg.norm(side)
@@ -110,24 +124,34 @@ def child(variant: str, parts: int = 1) -> dict:
             pos = [float(c + 0.01 * k * s) for c, s in zip(camera.position, side)]
             return E.Camera(pos, [float(v) for v in d0 + sway * side], camera.up)
 
-        prev_view = E.View(camera, SIZE, settings)
+        prev_view = E.View(camera, size, settings)
         guide_rt.first_hits_into(camera, guides[0].data_ptr())
 
     def step_moving():
         nonlocal frame, prev_view
         dst = targets[frame % len(targets)].data_ptr()
         cam = camera_at(frame)
-        view = E.View(cam, SIZE, settings)
+        view = E.View(cam, size, settings)
         prev_hits, cur_hits = guides[(frame - 1) % len(guides)], guides[frame % len(guides)]
-        if variant in ("h", "i"):
+        if variant == "j":
+            # the buffer's last reader was this context's upsample of two frames back: the writer follows it
+            high_hits = high_guides[frame % 2]
+            high_ctx.order_after(ctx)
+            high_rt.first_hits_async(cam, high_hits.data_ptr())
+        if variant in ("h", "i", "j"):
             guide_rt.first_hits_async(cam, cur_hits.data_ptr())
         else:
             guide_rt.first_hits_into(cam, cur_hits.data_ptr())  # blocking
         raytraces[0].compute(cam, frame)
-        if variant == "i":
+        if variant in ("i", "j"):
             ctx.reproject_moments(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
             diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY, moments=True)
-            tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+            if variant == "j":
+                ctx.order_after(high_ctx)
+                tickets.append(ctx.upsample_present(dst, nbytes, W, H, cur_hits.data_ptr(), high_hits.data_ptr(),
+                                                    variance=vinfo))
+            else:
+                tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
         else:
             ctx.reproject(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
             diffuses[0].next_frame_history(raytraces[0].image(), MAX_HISTORY)
@@ -166,16 +190,20 @@ def child(variant: str, parts: int = 1) -> dict:
     t0 = time.perf_counter()
     for _ in range(FRAMES):
         step()
+    if variant == "j":
+        high_ctx.synchronize()
     for c in reversed(ctxs):  # (the root last: its tickets follow every part's copy)
         c.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / FRAMES
     st = ctx.stats()
     assert all(c.stats().accumulates == st.accumulates for c in ctxs)
     out = {"variant": variant, "parts": parts, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
-           "width": W, "height": H, "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
+           "width": W, "height": H, "render_width": size[0], "render_height": size[1], "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
            "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
     if variant == "g":
         guide_ctx.close()
+    if variant == "j":
+        high_ctx.close()
     for c in ctxs:
         c.close()
     return out
@@ -183,7 +211,7 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i"), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i", "j"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
@@ -194,6 +222,8 @@ def main() -> int:
                          "taken on a second context) and h (f with hrt_first_hits, nothing blocking) only, taking turns")
     ap.add_argument("--variance", action="store_true",
                     help="variants h and i (h with the moments calls and the variance-guided filter) only, taking turns")
+    ap.add_argument("--upsample", action="store_true",
+                    help="variants i and j (i rendered at half size and shown through hrt_upsample_present) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -205,13 +235,13 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    if (a.denoise or a.moving or a.variance) and a.parts > 1:
+    if (a.denoise or a.moving or a.variance or a.upsample) and a.parts > 1:
         ap.error("--denoise, --moving and --variance run on a single context (a partitioned context cannot denoise or keep "
                  "history)")
     if a.out is None:
-        name = "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        name = "present_loop_upsample.jsonl" if a.upsample else "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
         a.out = os.path.join(ROOT, "profiles", name)
-    variants = VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
+    variants = UPSAMPLE_VARIANTS if a.upsample else VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
     order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
@@ -236,7 +266,10 @@ def main() -> int:
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
                                "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
-    if a.variance:
+    if a.upsample:
+        summary.update(j_over_i=round(med["j"] / med["i"], 4), j_minus_i_ms=round(med["j"] - med["i"], 4),
+                       ranges_apart=max(runs["j"]) < min(runs["i"]) or max(runs["i"]) < min(runs["j"]))
+    elif a.variance:
         summary.update(i_over_h=round(med["i"] / med["h"], 4), i_minus_h_ms=round(med["i"] - med["h"], 4))
     elif a.moving:
         summary.update(f_over_e=round(med["f"] / med["e"], 4), f_minus_e_ms=round(med["f"] - med["e"], 4),
