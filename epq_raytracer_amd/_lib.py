@@ -213,6 +213,18 @@ UPSAMPLE_FOOTPRINT = 2  # HRT_UPSAMPLE_FOOTPRINT (hrt_upsample_defaults)
 UPSAMPLE_MAX_DIM = 16384  # the largest width / height of a result
 
 
+class ResolveInfo(ctypes.Structure):
+    """hrt_resolve_info: one fold across resolutions (32 bytes)."""
+
+    _fields_ = [("offset_x", c_float), ("offset_y", c_float), ("max_history", c_uint32), ("flags", c_uint32),
+                ("reserved", c_uint32 * 4)]
+
+
+assert ctypes.sizeof(ResolveInfo) == 32
+RESOLVE_FILL, RESOLVE_MOMENTS = 1, 2  # HRT_RESOLVE_* (flags of hrt_resolve_info)
+RESOLVE_MAX_HISTORY = 32  # hrt_resolve_defaults' max_history
+
+
 class FirstHitsStats(ctypes.Structure):
     """hrt_first_hits_stats: what the last counted hrt_first_hits call ran (48 bytes)."""
 
@@ -341,6 +353,7 @@ EXPORTED_SYMBOLS = (
     "hrt_refine_defaults", "hrt_refine_select", "hrt_refine", "hrt_refine_until",
     "hrt_refine_tiles", "hrt_refine_tiles_until",
     "hrt_upsample_defaults", "hrt_upsample", "hrt_upsample_present", "hrt_order_after",
+    "hrt_resolve_defaults", "hrt_set_ray_grid", "hrt_history_phase", "hrt_accumulate_history_from",
     "hrt_present", "hrt_accumulate_present", "hrt_present_done", "hrt_present_wait", "hrt_debug_export_memory", "hrt_debug_unmap_memory", "hrt_debug_math_check", "hrt_debug_math_check_rng", "hrt_debug_band_flatten", "hrt_debug_wq_protocol",
     "hrt_debug_timeline", "hrt_debug_band_records", "hrt_debug_tile_costs", "hrt_debug_sky_units",
     "hrt_debug_tile_lists",
@@ -450,6 +463,11 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_upsample_present": (c_int32, [P, POINTER(UpsampleInfo), POINTER(DenoiseInfo), POINTER(VarianceInfo), P, P,
                                            POINTER(PresentInfo), P, c_uint64, POINTER(c_uint64)]),
         "hrt_order_after": (c_int32, [P, P]),
+        "hrt_resolve_defaults": (None, [POINTER(ResolveInfo)]),
+        "hrt_set_ray_grid": (c_int32, [P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+        "hrt_history_phase": (None, [c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(c_float),
+                                     POINTER(c_float)]),
+        "hrt_accumulate_history_from": (c_int32, [P, P, POINTER(ResolveInfo), P, P]),
         "hrt_present_done": (c_int32, [P, c_uint64, POINTER(c_uint32)]),
         "hrt_present_wait": (c_int32, [P, c_uint64]),
         "hrt_debug_export_memory": (c_int32, [c_int32, c_uint64, POINTER(c_int32), POINTER(c_void_p),

@@ -26,6 +26,8 @@
 #include "hrt_denoise.h"
 #include "hrt_history.h"
 #include "hrt_upsample.h"
+#include "hrt_resolve.h"
+#include "hrt_resolve_map.h"
 #include "hrt_variance.h"
 #include "hrt_refine.h"
 #include "hrt_host.h"
@@ -469,6 +471,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
     free_dev(ctx, l.tl_cache);
     if (l.done) (void)hipEventDestroy(l.done);
     if (l.free) (void)hipEventDestroy(l.free);
+    if (l.foreign) (void)hipEventDestroy(l.foreign);
     if (l.sky_stream) (void)hipStreamSynchronize(l.sky_stream);
     if (l.sky_fork) (void)hipEventDestroy(l.sky_fork);
     if (l.sky_join) (void)hipEventDestroy(l.sky_join);
@@ -518,6 +521,7 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->fh_cam_cull);
   free_dev(ctx, ctx->fh_stats);
   if (ctx->fold_done) (void)hipEventDestroy(ctx->fold_done);
+  if (ctx->fold_foreign) (void)hipEventDestroy(ctx->fold_foreign);
   if (ctx->order_ev) (void)hipEventDestroy(ctx->order_ev);
   for (hipEvent_t ev : ctx->present_ev)  // (the streams were drained above: every ticket is complete)
     if (ev) (void)hipEventDestroy(ev);
@@ -1047,6 +1051,8 @@ hrt_status begin_lane(hrt_context* ctx, int* out) {
   const int l = ctx->lane_used ? (ctx->cur_lane + 1) % n : 0;
   hrt::Lane& lane = ctx->lane[l];
   if (lane.free_set) HRT_HIP(ctx, hipStreamWaitEvent(lane.stream, lane.free, 0));
+  // ... and after a reader on another context's stream (hrt_accumulate_history_from)
+  if (lane.foreign_set) HRT_HIP(ctx, hipStreamWaitEvent(lane.stream, lane.foreign, 0));
   *out = l;
   return HRT_OK;
 }
@@ -1088,6 +1094,7 @@ extern "C" hrt_status hrt_trace(hrt_context* ctx, const hrt_push_constants* pc) 
     hrt::TraceParams p = make_params(ctx, pc, l);
     if (slot >= 0) {  // after the fold that last read the slot
       if (ctx->fold_set) HRT_HIP(ctx, hipStreamWaitEvent(lane.stream, ctx->fold_done, 0));
+      if (ctx->fold_foreign_set) HRT_HIP(ctx, hipStreamWaitEvent(lane.stream, ctx->fold_foreign, 0));
       set_image(p, ctx, static_cast<char*>(ctx->ring) + (size_t)slot * ctx->npix() * ctx->px_bytes());
     }
     // Throughput mode: when another lane's trace is still running, this one shares the chip with it
@@ -1519,6 +1526,8 @@ hrt_status begin_batch(hrt_context* ctx, const hrt_push_constants* pc, uint32_t 
   hrt_status st;
   if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;
   if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
+  // lane 0's image is written on this stream: after another context's fold that still reads it
+  if (ctx->lane[0].foreign_set) HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lane[0].foreign, 0));
   b->p = make_params(ctx, pc, 0);
   const size_t np = ctx->npix(), px_bytes = ctx->px_bytes();
   const uint32_t cap = (uint32_t)std::max<size_t>(
@@ -2495,6 +2504,125 @@ extern "C" hrt_status hrt_order_after(hrt_context* ctx, hrt_context* producer) {
   if (!producer->order_ev) HRT_HIP(ctx, hipEventCreateWithFlags(&producer->order_ev, hipEventDisableTiming));
   HRT_HIP(ctx, hipEventRecord(producer->order_ev, producer->stream));
   HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, producer->order_ev, 0));
+  return HRT_OK;
+}
+
+// ---- temporal upsampling (kernel in hrt_resolve.hip) -------------------------------------
+extern "C" void hrt_resolve_defaults(hrt_resolve_info* info) {
+  if (!info) return;
+  *info = hrt_resolve_info{0.0f, 0.0f, 32u, HRT_RESOLVE_FILL, {0u, 0u, 0u, 0u}};
+}
+
+extern "C" void hrt_history_phase(uint32_t ws, uint32_t w, uint32_t hs, uint32_t h, uint32_t k, float* ox, float* oy) {
+  const uint32_t nx = hrt::resolve_phases(ws, w), ny = hrt::resolve_phases(hs, h);
+  if (ox) *ox = hrt::resolve_phase_offset(k % nx, nx);
+  if (oy) *oy = hrt::resolve_phase_offset((k / nx) % ny, ny);
+}
+
+// The ray centres are read by the traces on the lane streams and by everything else on the context's stream: the
+// write runs on the context's stream after every lane's latest trace (join_lanes), and every lane's next trace
+// waits for it through the lane's `free` event, as it waits for the last reader of its buffers.
+extern "C" hrt_status hrt_set_ray_grid(hrt_context* ctx, const float first[3], const float dx[3], const float dy[3]) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string("hrt_set_ray_grid: ") + what); };
+  if (!first || !dx || !dy) return bad("null first, dx or dy");
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(first[c]) || !std::isfinite(dx[c]) || !std::isfinite(dy[c])) return bad("a component is not finite");
+  if (ctx->comm || ctx->part_count > 1)
+    return bad("a context of a row-tile partition or joined to a communicator takes its rays from hrt_set_scene or "
+               "hrt_generate_rays (the stream-ordered passes that need a shifted grid refuse such a context)");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  const size_t want = (size_t)ctx->width * ctx->height;
+  if (!ctx->scene.rays || ctx->n_rays != want) {  // (no buffer of this size: nothing in flight reads one)
+    free_dev(ctx, ctx->scene.rays);
+    ctx->n_rays = 0;
+    HRT_HIP(ctx, hrt::dev_alloc(ctx, (void**)&ctx->scene.rays, (want ? want : 1) * sizeof(float4)));
+  }
+  if ((st = hrt::join_lanes(ctx)) != HRT_OK) return st;
+  for (auto& l : ctx->lane) l.tl_ready = false;  // the tile lists were built from the old ray centres
+  HRT_HIP(ctx, hrt::launch_make_rays(ctx->scene.rays, ctx->width, ctx->height, first, dx, dy, ctx->stream));
+  ctx->n_rays = (uint32_t)want;
+  for (int l = 0; l < hrt::kLanes; ++l)
+    if ((st = hrt::release_lane(ctx, l)) != HRT_OK) return st;
+  return HRT_OK;
+}
+
+extern "C" hrt_status hrt_accumulate_history_from(hrt_context* ctx, hrt_context* source, const hrt_resolve_info* info,
+                                                  const hrt_hit* source_hits, const hrt_hit* hits) {
+  if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
+  const char* who = "hrt_accumulate_history_from";
+  auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
+  if (!source) return bad("null source");
+  if (!info) return bad("null info");
+  if (ctx->device != source->device) return bad("the two contexts are on different devices");
+  if (ctx->mode != source->mode) return bad("the two contexts are in different modes");
+  if (!(std::isfinite(info->offset_x) && std::isfinite(info->offset_y) && info->offset_x >= -0.5f && info->offset_x <= 0.5f &&
+        info->offset_y >= -0.5f && info->offset_y <= 0.5f))
+    return bad("the offsets must be finite and in [-0.5, 0.5]");
+  if (info->max_history == 0 || info->max_history > hrt::kHistoryMax) return bad("max_history must be 1..2^24");
+  if (info->flags & ~(HRT_RESOLVE_FILL | HRT_RESOLVE_MOMENTS)) return bad("unknown flag bits");
+  if ((source_hits == nullptr) != (hits == nullptr)) return bad("source_hits and hits must both be given or both be NULL");
+  if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, who);  // (the rejection)
+  if (source->comm || source->part_count > 1)
+    return bad("the source is a context of a row-tile partition or joined to a communicator (its trace image is not a frame)");
+  if (source != ctx && !source->scene_set) return fail(ctx, HRT_ERR_NO_SCENE, std::string(who) + ": the source has no scene (no trace image to fold)");
+  if (ctx->width > (1u << 24) || ctx->height > (1u << 24) || source->width > (1u << 24) || source->height > (1u << 24))
+    return bad("an image is wider or taller than 2^24");
+  hrt_status st = bind(ctx);
+  if (st != HRT_OK) return st;
+  if (hits) {
+    if ((uintptr_t)source_hits % 16 != 0 || (uintptr_t)hits % 16 != 0) return bad("source_hits and hits must be 16-byte aligned");
+    if (!hits_on_device(source, source_hits))
+      return bad("source_hits must be the source's width x height records in memory of the contexts' device");
+    if (!hits_on_device(ctx, hits)) return bad("hits must be width x height records in memory of the contexts' device");
+  }
+  const bool moments = (info->flags & HRT_RESOLVE_MOMENTS) != 0;
+  if ((st = begin_history(ctx, who)) != HRT_OK) return st;
+  if (moments && (st = begin_moments(ctx, who)) != HRT_OK) return st;
+  if ((st = hrt::flush_combines(ctx)) != HRT_OK) return st;  // frames fold in call order
+  // T: after the source's deferred combines and its latest trace, as accumulate_history_call orders them on the
+  // source's stream; then this stream follows the source's
+  const int l = source->cur_lane;
+  if (source != ctx) {
+    if ((st = hrt::flush_combines(source)) != HRT_OK) return fail(ctx, st, std::string(who) + ": " + source->err);
+    if ((st = hrt::wait_lane(source, l)) != HRT_OK) return fail(ctx, st, std::string(who) + ": " + source->err);
+    if (!source->order_ev) HRT_HIP(ctx, hipEventCreateWithFlags(&source->order_ev, hipEventDisableTiming));
+    HRT_HIP(ctx, hipEventRecord(source->order_ev, source->stream));
+    HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, source->order_ev, 0));
+  } else if ((st = hrt::wait_lane(ctx, l)) != HRT_OK) {
+    return st;
+  }
+  const hrt::ResolvePass pass{ctx->accum, ctx->hist_cnt, moments ? ctx->hist_mom : nullptr, hrt::trace_image(source),
+                              source_hits, hits, ctx->f32(), source->width, source->local_rows, ctx->width, ctx->local_rows,
+                              info->offset_x, info->offset_y, info->max_history, info->flags & HRT_RESOLVE_FILL};
+  HRT_HIP(ctx, hrt::launch_resolve(pass, ctx->stream));
+  ctx->accumulates++;
+  // T's next writer -- the source's next trace into this lane or ring slot -- waits for the kernel
+  if (source == ctx) {  // accumulate_history_call's own steps
+    if (ctx->cur_slot >= 0) {
+      HRT_HIP(ctx, hipEventRecord(ctx->fold_done, ctx->stream));
+      ctx->fold_set = true;
+    }
+    return hrt::release_lane(ctx, l);
+  }
+  // A reader on another stream: the source's `free` and `fold_done` cannot carry it, because the source's own
+  // calls (hrt_set_ray_grid, hrt_accumulate, a read of the trace image, a flush of its combines) re-record them
+  // on its own stream, which does not wait for this one, and the newer record would hide this reader.  So the
+  // lane and the ring have an event of their own for such readers, recorded only here, and every writer of the
+  // image waits for both.  An earlier record of it (another target's fold) is waited for first, so that the one
+  // event stands for every foreign reader so far.
+  hrt::Lane& sl = source->lane[l];
+  if (!sl.foreign) HRT_HIP(ctx, hipEventCreateWithFlags(&sl.foreign, hipEventDisableTiming));
+  if (sl.foreign_set) HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.foreign, 0));
+  HRT_HIP(ctx, hipEventRecord(sl.foreign, ctx->stream));
+  sl.foreign_set = true;
+  if (source->cur_slot >= 0) {
+    if (!source->fold_foreign) HRT_HIP(ctx, hipEventCreateWithFlags(&source->fold_foreign, hipEventDisableTiming));
+    if (source->fold_foreign_set) HRT_HIP(ctx, hipStreamWaitEvent(ctx->stream, source->fold_foreign, 0));
+    HRT_HIP(ctx, hipEventRecord(source->fold_foreign, ctx->stream));
+    source->fold_foreign_set = true;
+  }
   return HRT_OK;
 }
 

@@ -95,6 +95,12 @@ struct Lane {
   hipEvent_t done = nullptr;      // recorded on `stream` after each trace / clear of the lane
   hipEvent_t free = nullptr;      // recorded on the context stream after the lane's last reader
   bool done_set = false, free_set = false;
+  // recorded on ANOTHER context's stream after its last read of this lane's trace image
+  // (hrt_accumulate_history_from with this context as the source): a second event, because `free` is
+  // re-recorded by this context's own calls on its own stream, which never waits for the other's.  The
+  // lane's next writer waits for both.  Created by the first such read
+  hipEvent_t foreign = nullptr;
+  bool foreign_set = false;
   // the lane's sky lane (HRT_OPT_SKY_LANE, hrt_kernels.h SkyLane): created by the first launch that uses it
   hipStream_t sky_stream = nullptr;
   hipEvent_t sky_fork = nullptr, sky_join = nullptr;
@@ -203,6 +209,10 @@ struct hrt_context {
   std::vector<Pend> pend;      // recorded, not yet folded (consecutive slots and frames)
   hipEvent_t fold_done = nullptr;  // recorded on `stream` after the last fold (a slot's next trace waits)
   bool fold_set = false;
+  // fold_done's counterpart for a reader on another context's stream (Lane::foreign): recorded there after
+  // hrt_accumulate_history_from has read a ring slot of this context; a slot's next trace waits for both
+  hipEvent_t fold_foreign = nullptr;
+  bool fold_foreign_set = false;
   uint32_t defer = 0;          // HRT_OPT_DEFER_COMBINE (off: measured slower, hip_raytrace.h)
   // Fold records (HRT_OPT_FOLD_RECORDS, hrt_compute_until).  Record t (0-based since the option was set)
   // lives in fold_ring[t % HRT_FOLD_RECORD_RING]: the host zeroes the slot on `stream` before the fold

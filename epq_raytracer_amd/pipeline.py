@@ -85,17 +85,47 @@ def sphere_records(spheres: List[Sphere]) -> np.ndarray:
     return np.array([s.record() for s in spheres], dtype=_lib.SPHERE_DTYPE)
 
 
+def ray_grid(image_size, camera_focal_length, viewport_height, up):
+    """hrt_host_ray_grid: (first, dx, dy, default jitter) of an image's ray centres, ray (x, y) = (first + dx * x)
+    + dy * y; the three vectors as float32 arrays of 3."""
+    first, dx, dy = ((ctypes.c_float * 3)() for _ in range(3))
+    jit = ctypes.c_float()
+    _lib.load().hrt_host_ray_grid(int(image_size[0]), int(image_size[1]), float(np.float32(camera_focal_length)),
+                                  float(np.float32(viewport_height)), _lib.f3(up), first, dx, dy, ctypes.byref(jit))
+    return (np.array(first[:], np.float32), np.array(dx[:], np.float32), np.array(dy[:], np.float32), jit.value)
+
+
+def shifted_first(first, dx, dy, ox, oy) -> np.ndarray:
+    """The first ray centre of a grid shifted by (ox, oy) pixels: (first + ox * dx) + oy * dy, every operation in
+    binary32 -- what hrt_set_ray_grid takes as ``first`` for frame k's ``history_phase`` offset."""
+    first, dx, dy = (np.asarray(v, np.float32)[:3] for v in (first, dx, dy))
+    ox, oy = np.float32(ox), np.float32(oy)
+    return ((first + ox * dx).astype(np.float32) + (oy * dy).astype(np.float32)).astype(np.float32)
+
+
+def history_phase(source_size, target_size, k: int):
+    """hrt_history_phase: the sub-pixel offset (ox, oy) of frame k of a source_size grid that feeds a target_size
+    history through ``HrtContext.accumulate_history_from``."""
+    ox, oy = ctypes.c_float(), ctypes.c_float()
+    _lib.load().hrt_history_phase(int(source_size[0]), int(target_size[0]), int(source_size[1]), int(target_size[1]),
+                                  int(k) & 0xFFFFFFFF, ctypes.byref(ox), ctypes.byref(oy))
+    return ox.value, oy.value
+
+
 class View:
     """hrt_view of a camera: its position and view matrix as ``RayTracePipeline.push_constants`` writes them,
     and the affine grid of the ray centres (hrt_host_ray_grid) of an image of ``image_size`` under
     ``settings`` (anything with camera_focal_length, viewport_height and up).  ``record`` is the
-    _lib.View that hrt_reproject takes."""
+    _lib.View that hrt_reproject takes.  ``offset`` = (ox, oy): the view of a grid shifted by that many pixels
+    (``shifted_first``), as ``HrtContext.shift_ray_grid`` sets it."""
 
-    def __init__(self, camera: Camera, image_size, settings):
+    def __init__(self, camera: Camera, image_size, settings, offset=None):
         lib = _lib.load()
         first, dx, dy = ((ctypes.c_float * 3)() for _ in range(3))
         lib.hrt_host_ray_grid(int(image_size[0]), int(image_size[1]), float(np.float32(settings.camera_focal_length)),
                               float(np.float32(settings.viewport_height)), _lib.f3(settings.up), first, dx, dy, None)
+        if offset is not None:
+            first = shifted_first(first[:], dx[:], dy[:], offset[0], offset[1])
         rec = _lib.View()
         pos = np.asarray(camera.position, np.float32)
         rec.cam_pos[:] = [float(pos[0]), float(pos[1]), float(pos[2]), 1.0]
@@ -412,6 +442,51 @@ class HrtContext:
         """hrt_order_after: work issued on this context from now on follows everything issued so far on
         ``producer``'s stream (an event and a stream wait; no host wait).  Both must be on one device."""
         self._check(self.lib.hrt_order_after(self.handle, producer.handle), "hrt_order_after")
+
+    # ---- temporal upsampling (hrt_set_ray_grid, hrt_accumulate_history_from) ----
+
+    def set_ray_grid(self, first, dx, dy):
+        """hrt_set_ray_grid: the ray centres become (first + dx * x) + dy * y, written on the device in stream
+        order -- no host wait.  The grid is remembered as the base of ``shift_ray_grid``."""
+        self._check(self.lib.hrt_set_ray_grid(self.handle, _lib.f3(first), _lib.f3(dx), _lib.f3(dy)), "hrt_set_ray_grid")
+        self.base_grid = tuple(np.asarray(v, np.float32)[:3].copy() for v in (first, dx, dy))
+
+    def shift_ray_grid(self, ox: float, oy: float, grid=None):
+        """The ray centres of ``grid`` = (first, dx, dy) shifted by (ox, oy) pixels (``shifted_first``); grid=None:
+        the grid of the last ``set_ray_grid``.  Typically (ox, oy) = ``history_phase(...)`` of the frame."""
+        grid = grid if grid is not None else getattr(self, "base_grid", None)
+        if grid is None:
+            raise ValueError("no base grid: pass grid=(first, dx, dy) or call set_ray_grid first")
+        first, dx, dy = grid[:3]
+        self._check(self.lib.hrt_set_ray_grid(self.handle, _lib.f3(shifted_first(first, dx, dy, ox, oy)), _lib.f3(dx),
+                                              _lib.f3(dy)), "hrt_set_ray_grid")
+
+    def resolve_info(self, offset=(0.0, 0.0), max_history: Optional[int] = None, moments: bool = False,
+                     fill: Optional[bool] = None) -> _lib.ResolveInfo:
+        """hrt_resolve_defaults with the given fields replaced (None: the default)."""
+        info = _lib.ResolveInfo()
+        self.lib.hrt_resolve_defaults(ctypes.byref(info))
+        info.offset_x, info.offset_y = float(np.float32(offset[0])), float(np.float32(offset[1]))
+        if max_history is not None:
+            info.max_history = int(max_history)
+        if fill is not None:
+            info.flags = (info.flags & ~_lib.RESOLVE_FILL) | (_lib.RESOLVE_FILL if fill else 0)
+        if moments:
+            info.flags |= _lib.RESOLVE_MOMENTS
+        return info
+
+    def accumulate_history_from(self, source: "HrtContext", offset=(0.0, 0.0), max_history: Optional[int] = None,
+                                moments: bool = False, fill: Optional[bool] = None, source_hits_ptr: Optional[int] = None,
+                                hits_ptr: Optional[int] = None, info: Optional[_lib.ResolveInfo] = None):
+        """hrt_accumulate_history_from: ``source``'s trace image, sampled on a grid shifted by ``offset`` pixels of
+        its own, folded into this context's history -- each texel into the pixel its sample landed in.  The two
+        hit pointers (device memory, both or neither) restrict it to pixels whose first hits share a surface.
+        Non-blocking."""
+        info = info if info is not None else self.resolve_info(offset, max_history, moments, fill)
+        self._check(self.lib.hrt_accumulate_history_from(self.handle, source.handle, ctypes.byref(info),
+                                                         ctypes.c_void_p(source_hits_ptr or 0),
+                                                         ctypes.c_void_p(hits_ptr or 0)),
+                    "hrt_accumulate_history_from")
 
     # ---- temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history) ----
 
@@ -974,9 +1049,15 @@ class RayTracePipeline:
         self.sample_jitter = float(np.float32(settings.sample_jitter if settings.sample_jitter is not None else jitter))
         self.rays, self.tris, self.meshes, self.spheres = rays[:num_rays], tris, meshes[:n_meshes], spheres
         ctx.set_scene(rays[:num_rays], spheres, tris, meshes[:n_meshes])
+        self.grid = ray_grid(self.image_size, settings.camera_focal_length, settings.viewport_height, settings.up)[:3]
 
     def image(self) -> Image:
         return Image(self.ctx, _lib.IMG_TRACE)
+
+    def shift_rays(self, ox: float, oy: float) -> None:
+        """The pipeline's ray grid shifted by (ox, oy) pixels for the frames that follow (hrt_set_ray_grid; stream
+        ordered, no host wait): (0, 0) restores the rays the pipeline was made with, bit for bit."""
+        self.ctx.shift_ray_grid(ox, oy, self.grid)
 
     def push_constants(self, camera: Camera, rng_offset: int, init: bool) -> _lib.PushConstants:
         """The 124-byte block of dispatch(), src/raytrace_pipeline.rs:243-257."""
@@ -1091,6 +1172,16 @@ class DiffusePipeline:
             self.ctx.accumulate_history_moments(max_history)
         else:
             self.ctx.accumulate_history(max_history)
+
+    def next_frame_history_from(self, next_image: Image, offset=(0.0, 0.0), max_history: Optional[int] = None,
+                                moments: bool = False, fill: Optional[bool] = None, source_hits_ptr: Optional[int] = None,
+                                hits_ptr: Optional[int] = None) -> None:
+        """``next_frame_history`` with the trace image of another context, usually a smaller one whose ray grid was
+        shifted by ``offset`` (``HrtContext.shift_ray_grid`` with ``history_phase``) before the trace
+        (hrt_accumulate_history_from): over nx * ny frames every pixel of this image takes a sample of its own."""
+        if next_image.image_id != _lib.IMG_TRACE:
+            raise ValueError("next_image must be a trace image")
+        self.ctx.accumulate_history_from(next_image.ctx, offset, max_history, moments, fill, source_hits_ptr, hits_ptr)
 
     def refine_until(self, pipeline: "RayTracePipeline", camera: "Camera", first_frame: int, max_passes: int,
                      max_history: int = 1 << 24, guide_ptr: Optional[int] = None, method: int = _lib.REFINE_AUTO,

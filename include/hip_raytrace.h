@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): guided upsampling -- HRT_UPSAMPLE_FOOTPRINT, hrt_upsample_info,
+/* 6, additive (no bump: nothing existing changed): temporal upsampling -- HRT_RESOLVE_FILL, HRT_RESOLVE_MOMENTS,
+ * hrt_resolve_info, hrt_resolve_defaults, hrt_set_ray_grid, hrt_history_phase, hrt_accumulate_history_from.
+ * 6, additive (no bump: nothing existing changed): guided upsampling -- HRT_UPSAMPLE_FOOTPRINT, hrt_upsample_info,
  * hrt_upsample_defaults, hrt_upsample, hrt_upsample_present, hrt_order_after.
  * 6, additive (no bump: nothing existing changed): tile-masked refinement -- HRT_REFINE_TILES_MAX_FRAMES,
  * hrt_refine_tiles_stats, hrt_refine_tiles, hrt_refine_tiles_until.
@@ -388,6 +390,17 @@ typedef struct hrt_upsample_info { /* 32 bytes */
   uint32_t reserved;  /* ignored */
 } hrt_upsample_info;
 
+/* ---- temporal upsampling (hrt_accumulate_history_from) ---- */
+#define HRT_RESOLVE_FILL 1u    /* a pixel without history that took no sample shows the nearest source texel */
+#define HRT_RESOLVE_MOMENTS 2u /* fold the moments image M too */
+typedef struct hrt_resolve_info { /* 32 bytes */
+  float offset_x;       /* finite, each in [-0.5, 0.5]: source sample i sits at source coordinate i + offset */
+  float offset_y;
+  uint32_t max_history; /* 1..HRT_HISTORY_MAX, as hrt_accumulate_history */
+  uint32_t flags;       /* HRT_RESOLVE_* bits */
+  uint32_t reserved[4]; /* ignored */
+} hrt_resolve_info;
+
 /* ---- the first-hit pass (hrt_first_hits) ---- */
 typedef enum hrt_first_hits_method {
   HRT_FIRST_HITS_AUTO = 0,  /* TILES: it measured faster on island and on cave */
@@ -522,6 +535,10 @@ HRT_STATIC_ASSERT(sizeof(hrt_upsample_info) == 32 && offsetof(hrt_upsample_info,
                       offsetof(hrt_upsample_info, footprint) == 12 && offsetof(hrt_upsample_info, flags) == 16 &&
                       offsetof(hrt_upsample_info, sigma_normal) == 20 && offsetof(hrt_upsample_info, reserved) == 28,
                   "hrt_upsample_info");
+HRT_STATIC_ASSERT(sizeof(hrt_resolve_info) == 32 && offsetof(hrt_resolve_info, offset_y) == 4 &&
+                      offsetof(hrt_resolve_info, max_history) == 8 && offsetof(hrt_resolve_info, flags) == 12 &&
+                      offsetof(hrt_resolve_info, reserved) == 16,
+                  "hrt_resolve_info");
 HRT_STATIC_ASSERT(sizeof(hrt_variance_info) == 32 && offsetof(hrt_variance_info, method) == 4 &&
                       offsetof(hrt_variance_info, min_history) == 12 && offsetof(hrt_variance_info, sigma_variance) == 16 &&
                       offsetof(hrt_variance_info, variance_floor) == 20 && offsetof(hrt_variance_info, sigma_depth) == 28,
@@ -1327,6 +1344,54 @@ hrt_status hrt_upsample_present(hrt_context* ctx, const hrt_upsample_info* info,
  * two are the same context; two contexts on different devices are rejected.  (A context that upsamples takes its
  * high-resolution first hits from a second context: this orders the two without hrt_synchronize.) */
 hrt_status hrt_order_after(hrt_context* ctx, hrt_context* producer);
+/* ---- temporal upsampling ----
+ * A context that traces below display size samples a new sub-pixel position of the display grid each frame
+ * (hrt_set_ray_grid with hrt_history_phase's offset), and hrt_accumulate_history_from folds each of its trace texels
+ * into the display-size history pixel the sample landed in: after nx * ny frames every display pixel has had a
+ * sample of its own, and the history converges to what a display-size trace would have produced.
+ *
+ * hrt_set_ray_grid makes the context's ray centres (first + dx * x) + dy * y, as hrt_host_ray_grid and
+ * hrt_generate_rays define them, each operation rounded as written.  NON-blocking, and unlike hrt_generate_rays it
+ * never waits on the host: the write runs on the context's stream after every trace in flight on any trace lane and
+ * before every trace, first-hit pass, refinement or query issued afterwards (events and stream waits only).  The ray
+ * buffer is allocated when the context has none (that one call may synchronise the device); every lane's tile lists
+ * are marked stale.  A later hrt_set_scene with rays = NULL keeps the rays.  A grid shifted by (ox, oy) pixels is
+ * first' = (first + ox * dx) + oy * dy, computed in float by the caller.  Rejected with HRT_ERR_INVALID_ARGUMENT
+ * before anything is enqueued: a NULL argument, a component that is not finite, a context of a row-tile partition or
+ * joined to a communicator.
+ *
+ * hrt_history_phase is host only and pure: the offset of frame k of a ws x hs grid feeding a w x h history.
+ * nx = max(1, ceil(w / ws)) in integers, ny likewise from h and hs; a = k mod nx, b = (k div nx) mod ny;
+ * *ox = (float(a) + 0.5f) / float(nx) - 0.5f, *oy likewise from b and ny.  Equal sizes and downscaling have one
+ * phase, offset 0.  Over any nx * ny consecutive k every target pixel is accepted at least once.  A size of 0
+ * counts as one phase; a NULL output is skipped.
+ *
+ * hrt_accumulate_history_from(ctx, source, info, source_hits, hits): ctx (W x H) owns A, N and M; source (Ws x Hs)
+ * owns the most recent trace image T; source == ctx is allowed.  For target pixel p = (x, y), S20:
+ *   u = S19's upsample_coord(x, Ws, W) - offset_x, i = floorf(u + 0.5f), dx = fabsf(u - i); v, j, dy likewise;
+ *   accepted iff i and j lie inside T (tested in float), dx * float(W) <= 0.5f * float(Ws) and likewise for y (the
+ *   source sample lies in p's own pixel) and, with guides, the surface keys of source_hits[j * Ws + i] and
+ *   hits[y * W + x] are equal (S14).  Both guides are NULL or both are given.
+ *   accepted: exactly one hrt_accumulate_history[_moments] step of p with T(i, j) (M only with HRT_RESOLVE_MOMENTS);
+ *   not accepted, HRT_RESOLVE_FILL, N(p) == 0: A(p) = T(ic, jc) with alpha 255 / 1.0f, i and j clamped to the image;
+ *   N and M unchanged (a count of 0 still says that A is not history: the next accepted sample overwrites it);
+ *   every other pixel keeps A, N and M byte for byte.
+ * source == ctx, offsets 0, no guides, flags 0 gives hrt_accumulate_history's bytes; with MOMENTS,
+ * hrt_accumulate_history_moments'.
+ * NON-blocking.  The kernel runs on ctx's stream, after source's latest trace and its deferred combines and after
+ * the work issued so far on ctx; source's next trace into that lane or ring slot waits on the device until the
+ * kernel has read T, whatever is called on source in between (an event of the lane's that only this call records).  No host wait.  It changes nothing of source, and of ctx only A, N and, with MOMENTS, M.
+ * Rejected with HRT_ERR_INVALID_ARGUMENT before anything is enqueued: a NULL ctx, source or info; contexts on
+ * different devices or in different modes; an offset that is not finite or outside [-0.5, 0.5]; max_history outside
+ * 1..2^24; unknown flag bits; exactly one guide, or a guide that is not memory of the device or not 16-byte
+ * aligned; either context of a row-tile partition or joined to a communicator.  A source other than ctx that has
+ * no scene is rejected with HRT_ERR_NO_SCENE (source == ctx is hrt_accumulate_history on that edge too: no such
+ * check).  The message of a rejection is ctx's (hrt_last_error). */
+void hrt_resolve_defaults(hrt_resolve_info* info); /* offsets 0, max_history 32, HRT_RESOLVE_FILL */
+hrt_status hrt_set_ray_grid(hrt_context* ctx, const float first[3], const float dx[3], const float dy[3]);
+void hrt_history_phase(uint32_t ws, uint32_t w, uint32_t hs, uint32_t h, uint32_t k, float* ox, float* oy);
+hrt_status hrt_accumulate_history_from(hrt_context* ctx, hrt_context* source, const hrt_resolve_info* info,
+                                       const hrt_hit* source_hits, const hrt_hit* hits);
 /* Test support for the above: device memory exported as an fd (HIP VMM) and the exporter's own
  * mapping of it (*ptr, *size rounded to the allocation granularity); hrt_debug_unmap_memory frees it. */
 hrt_status hrt_debug_export_memory(int device, uint64_t bytes, int* fd, void** ptr, uint64_t* size);

@@ -197,6 +197,35 @@ inline hrt_view view_of(const Camera& camera, std::array<uint32_t, 2> image_size
   return v;
 }
 
+// Temporal upsampling (hrt_history_phase): the sub-pixel offset {ox, oy} of frame k of a source_size grid that feeds a
+// target_size history through Context::accumulate_history_from.
+inline std::array<float, 2> history_phase(std::array<uint32_t, 2> source_size, std::array<uint32_t, 2> target_size,
+                                          uint32_t k) {
+  std::array<float, 2> o{};
+  hrt_history_phase(source_size[0], target_size[0], source_size[1], target_size[1], k, &o[0], &o[1]);
+  return o;
+}
+// The first ray centre of a grid shifted by (ox, oy) pixels: (first + ox * dx) + oy * dy, each operation rounded to
+// float on its own (the volatile keeps a compiler from contracting them).
+inline std::array<float, 3> shifted_first(const float first[3], const float dx[3], const float dy[3], float ox, float oy) {
+  std::array<float, 3> out{};
+  for (int c = 0; c < 3; ++c) {
+    volatile float a = ox * dx[c];
+    volatile float b = first[c] + a;
+    volatile float d = oy * dy[c];
+    out[c] = b + d;
+  }
+  return out;
+}
+// view_of for a grid shifted by offset pixels, as Context::set_ray_grid sets it.
+inline hrt_view view_of(const Camera& camera, std::array<uint32_t, 2> image_size, const RayTracerSettings& settings,
+                        std::array<float, 2> offset) {
+  hrt_view v = view_of(camera, image_size, settings);
+  const std::array<float, 3> f = shifted_first(v.grid_first, v.grid_dx, v.grid_dy, offset[0], offset[1]);
+  for (int c = 0; c < 3; ++c) v.grid_first[c] = f[c];
+  return v;
+}
+
 // ---- the device context: the trace image and the accumulated image of one hrt_context -----------
 class Context {
  public:
@@ -301,6 +330,27 @@ class Context {
   // work issued on this context from now on follows everything issued so far on producer's stream (hrt_order_after:
   // an event and a stream wait, no host wait) -- e.g. the first_hits_enqueue that writes high_hits
   void order_after(Context& producer) { check(hrt_order_after(get(), producer.get()), "hrt_order_after", get()); }
+  // temporal upsampling (hrt_set_ray_grid, hrt_accumulate_history_from; not a reference feature).  set_ray_grid: the
+  // ray centres become (first + dx * x) + dy * y, written on the device in stream order, no host wait; with an
+  // offset the grid is shifted by that many pixels (shifted_first; typically history_phase of the frame).
+  // accumulate_history_from: source's trace image, sampled on a grid shifted by info's offsets, folded into this
+  // context's history, each texel into the pixel its sample landed in; the two hit arrays (device memory, both or
+  // neither) restrict it to pixels whose first hits share a surface.  Both only enqueue.
+  void set_ray_grid(const float first[3], const float dx[3], const float dy[3], std::array<float, 2> offset = {0.0f, 0.0f}) {
+    const std::array<float, 3> f = shifted_first(first, dx, dy, offset[0], offset[1]);
+    check(hrt_set_ray_grid(get(), f.data(), dx, dy), "hrt_set_ray_grid", get());
+  }
+  static hrt_resolve_info resolve_defaults(std::array<float, 2> offset = {0.0f, 0.0f}) {
+    hrt_resolve_info info;
+    hrt_resolve_defaults(&info);
+    info.offset_x = offset[0];
+    info.offset_y = offset[1];
+    return info;
+  }
+  void accumulate_history_from(Context& source, const hrt_resolve_info& info, const hrt_hit* source_hits = nullptr,
+                               const hrt_hit* hits = nullptr) {
+    check(hrt_accumulate_history_from(get(), source.get(), &info, source_hits, hits), "hrt_accumulate_history_from", get());
+  }
   // temporal history (hrt_reproject, hrt_accumulate_history, hrt_fill_history, hrt_read_history; not a reference
   // feature).  The hit arrays are width x height hrt_hit records in memory of the context's device, 16-byte
   // aligned (RayTracePipeline::first_hits_into under each view); reproject, accumulate_history and fill_history

@@ -39,6 +39,12 @@ and writes profiles/present_loop_variance.jsonl with i / h and i - h.
      scene into two alternating buffers, hrt_order_after between the two, and hrt_upsample_present (the variance-guided
      filter first, default footprint) in place of the present
 and writes profiles/present_loop_upsample.jsonl with j / i, j - i and whether the two ranges are apart.
+--resolve runs three variants of the moving loop, taking turns in one sitting: i, j, and
+  k  i with the trace alone on a context of half the size, its ray grid moved each frame by hrt_history_phase's
+     offset (hrt_set_ray_grid, jitter_size the full-size grid's default) and the history kept at full size: on the
+     full-size context hrt_first_hits, hrt_reproject_moments, hrt_accumulate_history_from (the half-size trace image
+     folded into the pixels its samples landed in, with moments) and hrt_denoise_variance_present -- all enqueued
+and writes profiles/present_loop_resolve.jsonl with k / i, k / j, k - j and whether k lies between j and i.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -58,6 +64,7 @@ DENOISE_VARIANTS = ("c", "e")
 MOVING_VARIANTS = ("e", "f", "g", "h")
 VARIANCE_VARIANTS = ("h", "i")
 UPSAMPLE_VARIANTS = ("i", "j")
+RESOLVE_VARIANTS = ("i", "j", "k")
 MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
@@ -96,7 +103,7 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
-    moving = variant in ("f", "g", "h", "i", "j")
+    moving = variant in ("f", "g", "h", "i", "j", "k")
     if moving:
         import numpy as np
 
@@ -104,7 +111,7 @@ def child(variant: str, parts: int = 1) -> dict:
         # the last LAG frames still read is never overwritten
         # (h: two -- its passes are ordered on the stream behind the readers of the buffer they overwrite)
         guides = [torch.empty((size[0] * size[1], 8), dtype=torch.float32, device="cuda:0")
-                  for _ in range(2 if variant in ("h", "i", "j") else LAG + 2)]
+                  for _ in range(2 if variant in ("h", "i", "j", "k") else LAG + 2)]
         guide_ctx, guide_rt = ctx, raytraces[0]
         if variant == "g":
             guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
@@ -114,6 +121,13 @@ def child(variant: str, parts: int = 1) -> dict:
             high_rt = E.RayTracePipeline(high_ctx, SIZE, settings)
             high_guides = [torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for _ in range(2)]
             vinfo = ctx.variance_info()
+        if variant == "k":  # the trace alone at half size, sampling the full-size grid's pixels phase by phase
+            low_size = (W // 2, H // 2)
+            low_settings = E.preset(SCENE)[1]
+            low_settings.num_samples, low_settings.max_bounces = SPP, BOUNCES
+            low_settings.sample_jitter = raytraces[0].sample_jitter  # the full-size grid's default jitter
+            low_ctx = E.HrtContext(low_size, device=0, mode=_lib.MODE_RGBA8)
+            low_rt = E.RayTracePipeline(low_ctx, low_size, low_settings)
         d0 = np.asarray(camera.direction, np.float64) / np.linalg.norm(camera.direction)
         side = np.cross(d0, np.asarray(camera.up, np.float64))
         side /= np.linalg.norm(side)
@@ -138,6 +152,19 @@ def child(variant: str, parts: int = 1) -> dict:
             high_hits = high_guides[frame % 2]
             high_ctx.order_after(ctx)
             high_rt.first_hits_async(cam, high_hits.data_ptr())
+        if variant == "k":
+            off = E.history_phase(low_size, SIZE, frame)
+            low_rt.shift_rays(*off)
+            low_rt.compute(cam, frame)
+            guide_rt.first_hits_async(cam, cur_hits.data_ptr())
+            ctx.reproject_moments(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
+            ctx.accumulate_history_from(low_ctx, off, MAX_HISTORY, moments=True)
+            tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+            if len(tickets) > LAG:
+                ctx.present_wait(tickets[-1 - LAG])
+            prev_view = view
+            frame += 1
+            return
         if variant in ("h", "i", "j"):
             guide_rt.first_hits_async(cam, cur_hits.data_ptr())
         else:
@@ -192,18 +219,26 @@ def child(variant: str, parts: int = 1) -> dict:
         step()
     if variant == "j":
         high_ctx.synchronize()
+    if variant == "k":
+        low_ctx.synchronize()
     for c in reversed(ctxs):  # (the root last: its tickets follow every part's copy)
         c.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / FRAMES
     st = ctx.stats()
+    if variant == "k":  # (the traces ran on the half-size context)
+        size, last_kernel = low_size, low_ctx.stats().last_kernel
+    else:
+        last_kernel = st.last_kernel
     assert all(c.stats().accumulates == st.accumulates for c in ctxs)
     out = {"variant": variant, "parts": parts, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
-           "width": W, "height": H, "render_width": size[0], "render_height": size[1], "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[st.last_kernel],
+           "width": W, "height": H, "render_width": size[0], "render_height": size[1], "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[last_kernel],
            "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
     if variant == "g":
         guide_ctx.close()
     if variant == "j":
         high_ctx.close()
+    if variant == "k":
+        low_ctx.close()
     for c in ctxs:
         c.close()
     return out
@@ -211,7 +246,7 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i", "j"), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i", "j", "k"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
@@ -224,6 +259,9 @@ def main() -> int:
                     help="variants h and i (h with the moments calls and the variance-guided filter) only, taking turns")
     ap.add_argument("--upsample", action="store_true",
                     help="variants i and j (i rendered at half size and shown through hrt_upsample_present) only, taking turns")
+    ap.add_argument("--resolve", action="store_true",
+                    help="variants i, j and k (the trace at half size on a shifted grid, the history at full size through "
+                         "hrt_accumulate_history_from) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -235,13 +273,13 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    if (a.denoise or a.moving or a.variance or a.upsample) and a.parts > 1:
+    if (a.denoise or a.moving or a.variance or a.upsample or a.resolve) and a.parts > 1:
         ap.error("--denoise, --moving and --variance run on a single context (a partitioned context cannot denoise or keep "
                  "history)")
     if a.out is None:
-        name = "present_loop_upsample.jsonl" if a.upsample else "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        name = "present_loop_resolve.jsonl" if a.resolve else "present_loop_upsample.jsonl" if a.upsample else "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
         a.out = os.path.join(ROOT, "profiles", name)
-    variants = UPSAMPLE_VARIANTS if a.upsample else VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
+    variants = RESOLVE_VARIANTS if a.resolve else UPSAMPLE_VARIANTS if a.upsample else VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
     order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
@@ -266,7 +304,14 @@ def main() -> int:
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
                                "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
-    if a.upsample:
+    if a.resolve:
+        lo_ms, hi_ms = sorted((med["j"], med["i"]))
+        summary.update(k_over_i=round(med["k"] / med["i"], 4), k_over_j=round(med["k"] / med["j"], 4),
+                       k_minus_j_ms=round(med["k"] - med["j"], 4), k_minus_i_ms=round(med["k"] - med["i"], 4),
+                       k_between_j_and_i=lo_ms <= med["k"] <= hi_ms,
+                       k_i_ranges_apart=max(runs["k"]) < min(runs["i"]) or max(runs["i"]) < min(runs["k"]),
+                       k_j_ranges_apart=max(runs["k"]) < min(runs["j"]) or max(runs["j"]) < min(runs["k"]))
+    elif a.upsample:
         summary.update(j_over_i=round(med["j"] / med["i"], 4), j_minus_i_ms=round(med["j"] - med["i"], 4),
                        ranges_apart=max(runs["j"]) < min(runs["i"]) or max(runs["i"]) < min(runs["j"]))
     elif a.variance:
