@@ -5,9 +5,11 @@ accumulator (assets/image_combiner.glsl), plus the present pass into caller memo
 (include/hip_raytrace.h).  See DESIGN.md.
 """
 from . import _lib
+from ._lib import Motion
 from .app import RayTracingApp, compute_n_then_render, compute_then_render, compute_until_then_render
 from .pipeline import (DiffusePipeline, HrtContext, Image, PresentTarget, RayTracePipeline, RayTracerSettings,
-                       RenderPassOverFrame, View, create_rays, history_phase, ray_grid, shifted_first, sphere_records,
+                       RenderPassOverFrame, View, create_rays, history_phase, motion_between, ray_grid, shifted_first,
+                       sphere_records,
                        transform_meshes, view_matrix)
 from .scene import (Camera, CustomMaterial, InvisLightMaterial, LambertianMaterial, LightMaterial, Mesh,
                     MetalMaterial, RayTracingMesh, Sphere, get_null_mesh, get_null_sphere, load_asset, load_obj, subdivide)
@@ -21,5 +23,5 @@ __all__ = [
     "RayTracingMesh", "Sphere", "get_null_mesh", "get_null_sphere", "load_asset", "load_obj", "PRESETS",
     "load_box_scene", "load_cave_scene", "load_cube_scene", "load_island_scene", "load_spheres_scene", "make_app",
     "preset", "scaled_preset", "subdivide", "PresentTarget", "RenderPassOverFrame", "View", "history_phase", "ray_grid",
-    "shifted_first",
+    "shifted_first", "motion_between", "Motion",
 ]

@@ -186,6 +186,25 @@ REPROJECT_DEFAULTS = (0.02, 0.9)  # HRT_REPROJECT_DEPTH_TOLERANCE / _MIN_NORMAL_
 HISTORY_MAX = 1 << 24  # HRT_HISTORY_MAX: the largest max_history of hrt_accumulate_history
 
 
+class Motion(ctypes.Structure):
+    """hrt_motion: one object's rigid motion between two frames (64 bytes) -- m is the column-major 3x4 [L | b] with
+    previous world point = L * current world point + b."""
+
+    _fields_ = [("m", c_float * 12), ("flags", c_uint32), ("reserved", c_uint32 * 3)]
+
+
+class MotionTables(ctypes.Structure):
+    """hrt_motion_tables: the host tables of one hrt_reproject_motion call (32 bytes)."""
+
+    _fields_ = [("spheres", ctypes.c_void_p), ("n_spheres", c_uint32), ("meshes", ctypes.c_void_p), ("n_meshes", c_uint32)]
+
+
+assert ctypes.sizeof(Motion) == 64 and ctypes.sizeof(MotionTables) == 32
+MOTION_MOVING = 1  # HRT_MOTION_MOVING
+MOTION_MAX_OBJECTS = 65536  # HRT_MOTION_MAX_OBJECTS
+MOTION_RING = 4  # HRT_MOTION_RING: calls in flight before hrt_reproject_motion waits for the oldest pass
+
+
 class VarianceInfo(ctypes.Structure):
     """hrt_variance_info: one variance-guided denoise pass (32 bytes)."""
 
@@ -350,6 +369,7 @@ EXPORTED_SYMBOLS = (
     "hrt_reproject_defaults", "hrt_reproject", "hrt_accumulate_history", "hrt_fill_history", "hrt_read_history",
     "hrt_variance_defaults", "hrt_accumulate_history_moments", "hrt_reproject_moments", "hrt_fill_moments",
     "hrt_read_moments", "hrt_denoise_variance", "hrt_denoise_variance_present",
+    "hrt_reproject_motion", "hrt_reproject_motion_moments", "hrt_host_motion_between",
     "hrt_refine_defaults", "hrt_refine_select", "hrt_refine", "hrt_refine_until",
     "hrt_refine_tiles", "hrt_refine_tiles_until",
     "hrt_upsample_defaults", "hrt_upsample", "hrt_upsample_present", "hrt_order_after",
@@ -452,6 +472,11 @@ def load(debug: bool = False) -> ctypes.CDLL:
         "hrt_variance_defaults": (None, [POINTER(VarianceInfo)]),
         "hrt_accumulate_history_moments": (c_int32, [P, c_uint32]),
         "hrt_reproject_moments": (c_int32, [P, POINTER(ReprojectInfo), POINTER(View), P, POINTER(View), P]),
+        "hrt_reproject_motion": (c_int32, [P, POINTER(ReprojectInfo), POINTER(MotionTables), POINTER(View), P,
+                                           POINTER(View), P]),
+        "hrt_reproject_motion_moments": (c_int32, [P, POINTER(ReprojectInfo), POINTER(MotionTables), POINTER(View), P,
+                                                   POINTER(View), P]),
+        "hrt_host_motion_between": (None, [POINTER(c_float), POINTER(c_float), POINTER(Motion)]),
         "hrt_fill_moments": (c_int32, [P, c_float, c_float]),
         "hrt_read_moments": (c_int32, [P, P, c_size_t]),
         "hrt_denoise_variance": (c_int32, [P, POINTER(VarianceInfo), P, c_uint32, P, c_size_t, P, c_size_t]),

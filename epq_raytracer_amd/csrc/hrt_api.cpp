@@ -505,6 +505,11 @@ extern "C" void hrt_destroy(hrt_context* ctx) {
   free_dev(ctx, ctx->hist_mom);
   free_dev(ctx, ctx->hist_mom_next);
   free_dev(ctx, ctx->var_stage);
+  for (auto& s : ctx->motion_ring) {  // (the streams were drained above: no copy or pass is in flight)
+    free_dev(ctx, s.dev);
+    if (s.host) (void)hipHostFree(s.host);
+    if (s.done) (void)hipEventDestroy(s.done);
+  }
   free_dev(ctx, ctx->up_stage);
   free_dev(ctx, ctx->rf_mask);
   free_dev(ctx, ctx->rf_queries);
@@ -2085,10 +2090,79 @@ extern "C" void hrt_reproject_defaults(hrt_reproject_info* info) {
 
 namespace {
 
+// The new rejections of hrt_reproject_motion[_moments] (host only): the reason, or null.  *moving: whether any entry
+// has HRT_MOTION_MOVING.
+const char* check_motion(const hrt_motion_tables* m, bool* moving) {
+  if (m->n_spheres > HRT_MOTION_MAX_OBJECTS || m->n_meshes > HRT_MOTION_MAX_OBJECTS)
+    return "a motion table holds more than HRT_MOTION_MAX_OBJECTS entries";
+  if ((m->n_spheres && !m->spheres) || (m->n_meshes && !m->meshes)) return "a motion table with a count has a null pointer";
+  const hrt_motion* tab[2] = {m->spheres, m->meshes};
+  const uint32_t n[2] = {m->n_spheres, m->n_meshes};
+  for (int t = 0; t < 2; ++t)
+    for (uint32_t i = 0; i < n[t]; ++i) {
+      const hrt_motion& e = tab[t][i];
+      if (e.flags & ~HRT_MOTION_MOVING) return "a motion entry has an unknown flag bit";
+      if (!(e.flags & HRT_MOTION_MOVING)) continue;
+      *moving = true;
+      for (float v : e.m)
+        if (!std::isfinite(v)) return "a moving motion entry has a component that is not finite";
+    }
+  return nullptr;
+}
+
+// Copies the caller's tables into the next slot of the context's ring and enqueues the slot's upload on ctx->stream;
+// *tabs = the device tables the pass reads.  Blocks only for the slot's previous pass (the ring is exhausted) --
+// the caller records slot->done once more after its pass.
+hrt_status stage_motion(hrt_context* ctx, const hrt_motion_tables* m, hrt_context::MotionSlot** out, hrt::MotionTables* tabs,
+                        const char* who) {
+  hrt_context::MotionSlot& s = ctx->motion_ring[ctx->motion_next];
+  const size_t sb = (size_t)m->n_spheres * sizeof(hrt_motion), mb = (size_t)m->n_meshes * sizeof(hrt_motion);
+  const size_t need = sb + mb;  // (not 0: an entry moves)
+  if (!s.done) HRT_HIP(ctx, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  if (s.used) HRT_HIP(ctx, hipEventSynchronize(s.done));
+  s.used = false;
+  if (s.bytes < need) {  // (the slot's last pass has run: nothing reads the old buffers)
+    if (s.host) (void)hipHostFree(s.host);
+    free_dev(ctx, s.dev);
+    s.host = nullptr;
+    s.bytes = 0;
+    if (hipHostMalloc(&s.host, need, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      s.host = nullptr;
+      return fail(ctx, HRT_ERR_OUT_OF_MEMORY, std::string(who) + ": pinned staging allocation failed");
+    }
+    hrt_status st = ensure_staging(ctx, &s.dev, need, who);
+    if (st != HRT_OK) {
+      (void)hipHostFree(s.host);
+      s.host = nullptr;
+      return st;
+    }
+    s.bytes = need;
+  }
+  if (sb) std::memcpy(s.host, m->spheres, sb);
+  if (mb) std::memcpy(static_cast<char*>(s.host) + sb, m->meshes, mb);
+  HRT_HIP(ctx, hipMemcpyAsync(s.dev, s.host, need, hipMemcpyHostToDevice, ctx->stream));
+  // from here on the slot's buffers are in use: should the pass after this not be enqueued, the slot's next user
+  // still waits for the upload (the caller records the event once more behind its pass)
+  s.used = true;
+  HRT_HIP(ctx, hipEventRecord(s.done, ctx->stream));
+  tabs->spheres = m->n_spheres ? static_cast<const hrt_motion*>(s.dev) : nullptr;
+  tabs->meshes = m->n_meshes ? reinterpret_cast<const hrt_motion*>(static_cast<const char*>(s.dev) + sb) : nullptr;
+  tabs->n_spheres = m->n_spheres;
+  tabs->n_meshes = m->n_meshes;
+  ctx->motion_next = (ctx->motion_next + 1u) % HRT_MOTION_RING;
+  *out = &s;
+  return HRT_OK;
+}
+
 // hrt_reproject (moments false) and hrt_reproject_moments: the same checks, order and swaps; with moments the pass
 // also writes M' into hist_mom_next, swapped with hist_mom like the other two.
+// with_motion: hrt_reproject_motion[_moments] -- the tables are checked with the other arguments, staged through the
+// context's ring (stage_motion) after everything that can still refuse, and the motion form of the pass runs; a
+// call none of whose entries moves runs the plain pass, whose bytes S21 makes its own.
 hrt_status reproject_call(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev, const hrt_hit* prev_hits,
-                          const hrt_view* cur, const hrt_hit* cur_hits, bool moments, const char* who) {
+                          const hrt_view* cur, const hrt_hit* cur_hits, bool moments, const char* who,
+                          bool with_motion = false, const hrt_motion_tables* motion = nullptr) {
   if (!ctx) return HRT_ERR_INVALID_ARGUMENT;
   auto bad = [&](const char* what) { return fail(ctx, HRT_ERR_INVALID_ARGUMENT, std::string(who) + ": " + what); };
   if (!info) return bad("null info");
@@ -2099,6 +2173,11 @@ hrt_status reproject_call(hrt_context* ctx, const hrt_reproject_info* info, cons
   if (!(std::isfinite(info->depth_tolerance) && info->depth_tolerance >= 0.0f))
     return bad("depth_tolerance must be finite and not negative");
   if (!std::isfinite(info->min_normal_dot)) return bad("min_normal_dot must be finite");
+  bool moving = false;
+  if (with_motion) {
+    if (!motion) return bad("null motion tables");
+    if (const char* why = check_motion(motion, &moving)) return bad(why);
+  }
   if (ctx->comm || ctx->part_count > 1) return begin_history(ctx, who);  // (the rejection)
   hrt_status st = bind(ctx);
   if (st != HRT_OK) return st;
@@ -2121,10 +2200,18 @@ hrt_status reproject_call(hrt_context* ctx, const hrt_reproject_info* info, cons
   const hrt::ReprojectPass pass{ctx->accum, ctx->hist_cnt, ctx->hist_accum_next, ctx->hist_cnt_next, prev_hits, cur_hits,
                                 *prev, *cur, ctx->f32(), info->filter, ctx->width, ctx->local_rows,
                                 info->depth_tolerance, info->min_normal_dot};
-  if (moments)
+  if (moving) {
+    hrt_context::MotionSlot* slot = nullptr;
+    hrt::MotionTables tabs{};
+    if ((st = stage_motion(ctx, motion, &slot, &tabs, who)) != HRT_OK) return st;
+    HRT_HIP(ctx, hrt::launch_reproject_motion(pass, tabs, moments ? ctx->hist_mom : nullptr,
+                                              moments ? ctx->hist_mom_next : nullptr, ctx->stream));
+    HRT_HIP(ctx, hipEventRecord(slot->done, ctx->stream));  // the slot's next user waits for the pass
+  } else if (moments) {
     HRT_HIP(ctx, hrt::launch_reproject_moments(pass, ctx->hist_mom, ctx->hist_mom_next, ctx->stream));
-  else
+  } else {
     HRT_HIP(ctx, hrt::launch_reproject(pass, ctx->stream));
+  }
   // A' and N' become the context's accumulator and count image; the old ones are the next pass's targets
   std::swap(ctx->accum, ctx->hist_accum_next);
   std::swap(ctx->hist_cnt, ctx->hist_cnt_next);
@@ -2197,6 +2284,19 @@ extern "C" hrt_status hrt_accumulate_history_moments(hrt_context* ctx, uint32_t 
 extern "C" hrt_status hrt_reproject_moments(hrt_context* ctx, const hrt_reproject_info* info, const hrt_view* prev,
                                             const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
   return reproject_call(ctx, info, prev, prev_hits, cur, cur_hits, true, "hrt_reproject_moments");
+}
+
+// ---- object motion in the temporal history (the motion forms in hrt_history.hip) -------
+extern "C" hrt_status hrt_reproject_motion(hrt_context* ctx, const hrt_reproject_info* info, const hrt_motion_tables* motion,
+                                           const hrt_view* prev, const hrt_hit* prev_hits, const hrt_view* cur,
+                                           const hrt_hit* cur_hits) {
+  return reproject_call(ctx, info, prev, prev_hits, cur, cur_hits, false, "hrt_reproject_motion", true, motion);
+}
+
+extern "C" hrt_status hrt_reproject_motion_moments(hrt_context* ctx, const hrt_reproject_info* info,
+                                                   const hrt_motion_tables* motion, const hrt_view* prev,
+                                                   const hrt_hit* prev_hits, const hrt_view* cur, const hrt_hit* cur_hits) {
+  return reproject_call(ctx, info, prev, prev_hits, cur, cur_hits, true, "hrt_reproject_motion_moments", true, motion);
 }
 
 extern "C" hrt_status hrt_fill_moments(hrt_context* ctx, float m1, float m2) {

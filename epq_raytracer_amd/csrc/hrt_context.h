@@ -257,6 +257,20 @@ struct hrt_context {
   float* hist_mom = nullptr;
   float* hist_mom_next = nullptr;
   float* var_stage = nullptr;
+  // Object motion (hrt_reproject_motion[_moments]): the staging ring of the callers' tables.  A call copies its
+  // tables into slot motion_next's pinned buffer, enqueues the copy to the slot's device buffer and the pass on
+  // `stream`, and records the slot's event after the pass: the slot's next user waits for that event on the host
+  // before it writes the pinned buffer, so neither buffer is reused while a copy or a pass that reads it is in
+  // flight.  Buffers and events are made by the first call that needs them and grown for a larger table
+  struct MotionSlot {
+    void* host = nullptr;
+    void* dev = nullptr;
+    size_t bytes = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;
+  };
+  MotionSlot motion_ring[HRT_MOTION_RING];
+  uint32_t motion_next = 0;
   // Guided upsampling (hrt_upsample, hrt_upsample_present, hrt_order_after): the staging image of a result that
   // goes to host memory (up_stage_bytes of it, grown when a larger result comes), and the event hrt_order_after
   // records on this context's stream when it is the producer.  Each is made by the first call that needs it

@@ -35,4 +35,16 @@ struct ReprojectPass {
 };
 hipError_t launch_reproject(const ReprojectPass& p, hipStream_t stream);
 
+// The reprojection under object motion (hrt_reproject_motion[_moments]): S15 with the
+// pixel's object taken through its entry of the tables.  The tables are hrt_motion records in device memory,
+// 16-byte aligned, that stay unchanged until the pass has run; a count of 0 needs no pointer.  mom_in / mom_out:
+// both null (hrt_reproject_motion) or the moments images as launch_reproject_moments takes them.
+struct MotionTables {
+  const hrt_motion* spheres;
+  const hrt_motion* meshes;
+  uint32_t n_spheres, n_meshes;
+};
+hipError_t launch_reproject_motion(const ReprojectPass& p, const MotionTables& motion, const float* mom_in, float* mom_out,
+                                   hipStream_t stream);
+
 }  // namespace hrt

@@ -14,6 +14,7 @@
 #include "hip_raytrace.h"
 #include "hrt_history.h"
 #include "hrt_history_fold.h"
+#include "hrt_motion_map.h"
 #include "hrt_variance.h"
 #include "hrt_math.h"
 
@@ -169,13 +170,31 @@ __device__ __forceinline__ bool tap_accepted(const ReprojCentre& c, const uint32
 // Moments (S16): the moments image is carried beside them -- mom_out[i] <- the same taps of mom_in with the same
 // weights, in the same order, over the same wsum; (0, 0) for a rejected pixel.  Without it the two pointers are
 // not touched.
-template <typename T, uint32_t Filter, bool Moments>
+//
+// Motion (S21): the pixel's object may carry a rigid motion G between the two frames -- a kind-1 hit's entry is
+// spheres[hit.index], a kind-2 hit's meshes[hit.mesh], 64-byte hrt_motion records read as four 128-bit words.  An
+// index at or past its count, an entry whose flags are 0 and a miss are static and take S15's statements; a moving
+// pixel puts its point through G before step 4's subtraction and its normal through G's linear part before step 8.
+// Neighbouring pixels mostly share an object, so a wave's loads of the entry mostly hit one or two cache lines.
+// The plain forms (Motion false) take an empty last argument: their code is what it was before the motion forms
+// existed (profiles/motion_resources.txt).
+struct MotionTabK {
+  const float4* spheres;
+  const float4* meshes;
+  uint32_t n_spheres, n_meshes;
+};
+struct NoMotionK {};
+template <bool Motion>
+using MotionArgK = std::conditional_t<Motion, MotionTabK, NoMotionK>;
+
+template <typename T, uint32_t Filter, bool Moments, bool Motion>
 __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, const uint32_t* __restrict__ cnt_in,
                                                  T* __restrict__ acc_out, uint32_t* __restrict__ cnt_out,
                                                  const float4* __restrict__ prev_hits,
                                                  const float4* __restrict__ cur_hits, ViewK vp, ViewK vc, uint32_t w,
                                                  uint32_t h, float tol, float min_dot,
-                                                 const float2* __restrict__ mom_in, float2* __restrict__ mom_out) {
+                                                 const float2* __restrict__ mom_in, float2* __restrict__ mom_out,
+                                                 MotionArgK<Motion> tab) {
   const uint32_t x = blockIdx.x * kTileW + (threadIdx.x & (kTileW - 1u));
   const uint32_t y = blockIdx.y * kTileH + threadIdx.x / kTileW;
   if (x >= w || y >= h) return;
@@ -198,7 +217,26 @@ __global__ __launch_bounds__(256) void reproject(const T* __restrict__ acc_in, c
   c.te = 0.0f;
   c.tol_te = 0.0f;
   if (c.kc != 0u) {
-    const f3 p = {vc.o.x + dn.x * ha.x, vc.o.y + dn.y * ha.x, vc.o.z + dn.z * ha.x};
+    f3 p = {vc.o.x + dn.x * ha.x, vc.o.y + dn.y * ha.x, vc.o.z + dn.z * ha.x};
+    if constexpr (Motion) {
+      const uint32_t kind = __float_as_uint(ha.y);
+      const uint32_t idx = kind == 1u ? __float_as_uint(ha.z) : __float_as_uint(ha.w);
+      const float4* e = kind == 1u ? tab.spheres : tab.meshes;
+      const uint32_t cnt = kind == 1u ? tab.n_spheres : tab.n_meshes;
+      if (idx < cnt) {
+        e += (size_t)idx * 4u;
+        if (__float_as_uint(e[3].x) != 0u) {
+          const float4 g0 = e[0], g1 = e[1], g2 = e[2];
+          const float g[12] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w, g2.x, g2.y, g2.z, g2.w};
+          const float pin[3] = {p.x, p.y, p.z}, nin[3] = {c.nc.x, c.nc.y, c.nc.z};
+          float pout[3], nout[3];
+          motion_point(g, pin, pout);
+          motion_normal(g, nin, nout);
+          p = {pout[0], pout[1], pout[2]};
+          c.nc = {nout[0], nout[1], nout[2]};
+        }
+      }
+    }
     v = {p.x - vp.o.x, p.y - vp.o.y, p.z - vp.o.z};
     c.te = __builtin_sqrtf(hdot(v, v));
     c.tol_te = tol * c.te;
@@ -307,7 +345,8 @@ static ViewK view_k(const hrt_view& v) {
 }
 
 template <typename T, bool Moments>
-static void reproject_launch(const ReprojectPass& p, const float* mom_in, float* mom_out, dim3 grid, hipStream_t stream) {
+static void reproject_launch(const ReprojectPass& p, const float* mom_in, float* mom_out, dim3 grid, hipStream_t stream,
+                             const MotionTables* motion) {
   const T* ain = static_cast<const T*>(p.acc_in);
   T* aout = static_cast<T*>(p.acc_out);
   const float4* ph = reinterpret_cast<const float4*>(p.prev_hits);
@@ -315,15 +354,31 @@ static void reproject_launch(const ReprojectPass& p, const float* mom_in, float*
   const ViewK vp = view_k(p.prev), vc = view_k(p.cur);
   const float2* mi = reinterpret_cast<const float2*>(mom_in);
   float2* mo = reinterpret_cast<float2*>(mom_out);
+  if (motion) {
+    const MotionTabK tab{reinterpret_cast<const float4*>(motion->spheres), reinterpret_cast<const float4*>(motion->meshes),
+                         motion->n_spheres, motion->n_meshes};
+    if (p.filter == HRT_REPROJECT_NEAREST)
+      reproject<T, HRT_REPROJECT_NEAREST, Moments, true><<<grid, 256, 0, stream>>>(
+          ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h, p.depth_tolerance, p.min_normal_dot, mi, mo, tab);
+    else
+      reproject<T, HRT_REPROJECT_BILINEAR, Moments, true><<<grid, 256, 0, stream>>>(
+          ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h, p.depth_tolerance, p.min_normal_dot, mi, mo, tab);
+    return;
+  }
   if (p.filter == HRT_REPROJECT_NEAREST)
-    reproject<T, HRT_REPROJECT_NEAREST, Moments><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w,
-                                                                           p.h, p.depth_tolerance, p.min_normal_dot, mi, mo);
+    reproject<T, HRT_REPROJECT_NEAREST, Moments, false><<<grid, 256, 0, stream>>>(
+        ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h, p.depth_tolerance, p.min_normal_dot, mi, mo, NoMotionK{});
   else
-    reproject<T, HRT_REPROJECT_BILINEAR, Moments><<<grid, 256, 0, stream>>>(ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w,
-                                                                            p.h, p.depth_tolerance, p.min_normal_dot, mi, mo);
+    reproject<T, HRT_REPROJECT_BILINEAR, Moments, false><<<grid, 256, 0, stream>>>(
+        ain, p.cnt_in, aout, p.cnt_out, ph, ch, vp, vc, p.w, p.h, p.depth_tolerance, p.min_normal_dot, mi, mo, NoMotionK{});
 }
 
-static hipError_t reproject_dispatch(const ReprojectPass& p, const float* mom_in, float* mom_out, hipStream_t stream) {
+static hipError_t reproject_dispatch(const ReprojectPass& p, const float* mom_in, float* mom_out, hipStream_t stream,
+                                     const MotionTables* motion = nullptr) {
+  if (motion && (p.w != 0 && p.h != 0)) {
+    if ((motion->n_spheres && !motion->spheres) || (motion->n_meshes && !motion->meshes)) return hipErrorInvalidValue;
+    if ((((uintptr_t)motion->spheres | (uintptr_t)motion->meshes) & 15u) != 0) return hipErrorInvalidValue;
+  }
   if (p.w == 0 || p.h == 0) return hipSuccess;
   if (!p.acc_in || !p.cnt_in || !p.acc_out || !p.cnt_out || !p.prev_hits || !p.cur_hits) return hipErrorInvalidValue;
   if (p.acc_in == p.acc_out || p.cnt_in == p.cnt_out) return hipErrorInvalidValue;
@@ -334,13 +389,13 @@ static hipError_t reproject_dispatch(const ReprojectPass& p, const float* mom_in
   if (grid.y > 65535u || p.w > (1u << 24)) return hipErrorInvalidValue;
   if (mom_in) {
     if (p.f32)
-      reproject_launch<float4, true>(p, mom_in, mom_out, grid, stream);
+      reproject_launch<float4, true>(p, mom_in, mom_out, grid, stream, motion);
     else
-      reproject_launch<uint32_t, true>(p, mom_in, mom_out, grid, stream);
+      reproject_launch<uint32_t, true>(p, mom_in, mom_out, grid, stream, motion);
   } else if (p.f32) {
-    reproject_launch<float4, false>(p, nullptr, nullptr, grid, stream);
+    reproject_launch<float4, false>(p, nullptr, nullptr, grid, stream, motion);
   } else {
-    reproject_launch<uint32_t, false>(p, nullptr, nullptr, grid, stream);
+    reproject_launch<uint32_t, false>(p, nullptr, nullptr, grid, stream, motion);
   }
   return hipGetLastError();
 }
@@ -354,6 +409,14 @@ hipError_t launch_reproject_moments(const ReprojectPass& p, const float* mom_in,
   if (!mom_in || !mom_out || mom_in == mom_out || (((uintptr_t)mom_in | (uintptr_t)mom_out) & 7u) != 0)
     return hipErrorInvalidValue;
   return reproject_dispatch(p, mom_in, mom_out, stream);
+}
+
+hipError_t launch_reproject_motion(const ReprojectPass& p, const MotionTables& motion, const float* mom_in, float* mom_out,
+                                   hipStream_t stream) {
+  if (p.w == 0 || p.h == 0) return hipSuccess;
+  if ((mom_in == nullptr) != (mom_out == nullptr)) return hipErrorInvalidValue;
+  if (mom_in && (mom_in == mom_out || (((uintptr_t)mom_in | (uintptr_t)mom_out) & 7u) != 0)) return hipErrorInvalidValue;
+  return reproject_dispatch(p, mom_in, mom_out, stream, &motion);
 }
 
 hipError_t launch_fold_history_moments(void* cur, const void* nw, uint32_t* cnt, float* mom, bool f32, size_t npix,

@@ -3,6 +3,7 @@
 // the reference host is Rust, which never contracts, so every expression below is evaluated as
 // written (DESIGN.md numerics spec S8).
 #include "hrt_host.h"
+#include "hrt_motion_map.h"
 
 #include <cerrno>
 #include <cstdio>
@@ -77,6 +78,16 @@ extern "C" uint32_t hrt_host_create_rays(uint32_t width, uint32_t height, float 
     }
   }
   return n;
+}
+
+// (the arithmetic lives in hrt_motion_map.h, which the reprojection kernel and tests/cpp/motion_map_test.cpp share)
+extern "C" void hrt_host_motion_between(const float prev_pose[12], const float cur_pose[12], hrt_motion* out) {
+  if (!prev_pose || !cur_pose || !out) return;
+  float g[12];
+  const bool moved = hrt::motion_between(prev_pose, cur_pose, g);
+  std::memcpy(out->m, g, sizeof g);
+  out->flags = moved ? HRT_MOTION_MOVING : 0u;
+  out->reserved[0] = out->reserved[1] = out->reserved[2] = 0u;
 }
 
 extern "C" void hrt_host_view_matrix(const float direction[3], const float up[3], float out[16]) {

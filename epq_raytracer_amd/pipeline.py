@@ -95,6 +95,17 @@ def ray_grid(image_size, camera_focal_length, viewport_height, up):
     return (np.array(first[:], np.float32), np.array(dx[:], np.float32), np.array(dy[:], np.float32), jit.value)
 
 
+def motion_between(prev_pose, cur_pose) -> _lib.Motion:
+    """hrt_host_motion_between: the ``_lib.Motion`` record of an object whose object-to-world pose -- 12 floats, a
+    column-major 3x4 [R | t] with R a rotation -- was ``prev_pose`` in the previous frame and is ``cur_pose`` now."""
+    a = np.ascontiguousarray(prev_pose, dtype=np.float32).reshape(12)
+    b = np.ascontiguousarray(cur_pose, dtype=np.float32).reshape(12)
+    out = _lib.Motion()
+    fp = ctypes.POINTER(ctypes.c_float)
+    _lib.load().hrt_host_motion_between(a.ctypes.data_as(fp), b.ctypes.data_as(fp), ctypes.byref(out))
+    return out
+
+
 def shifted_first(first, dx, dy, ox, oy) -> np.ndarray:
     """The first ray centre of a grid shifted by (ox, oy) pixels: (first + ox * dx) + oy * dy, every operation in
     binary32 -- what hrt_set_ray_grid takes as ``first`` for frame k's ``history_phase`` offset."""
@@ -666,6 +677,36 @@ class HrtContext:
                                                    ctypes.c_void_p(prev_hits_ptr), ctypes.byref(cur.record),
                                                    ctypes.c_void_p(cur_hits_ptr)), "hrt_reproject_moments")
 
+    # ---- object motion in the temporal history (hrt_reproject_motion[_moments]) ----
+
+    @staticmethod
+    def motion_tables(spheres=None, meshes=None):
+        """(hrt_motion_tables, the arrays it points to) of two sequences of ``_lib.Motion`` records (None or empty:
+        a NULL table with count 0).  Keep the second value alive until the call that takes the first has returned."""
+        def arr(seq):
+            seq = list(seq) if seq is not None else []
+            return (_lib.Motion * len(seq))(*seq) if seq else None
+        sa, ma = arr(spheres), arr(meshes)
+        t = _lib.MotionTables(ctypes.addressof(sa) if sa is not None else None, len(sa) if sa is not None else 0,
+                              ctypes.addressof(ma) if ma is not None else None, len(ma) if ma is not None else 0)
+        return t, (sa, ma)
+
+    def reproject_motion(self, prev: "View", prev_hits_ptr: int, cur: "View", cur_hits_ptr: int, spheres=None, meshes=None,
+                         moments: bool = False, info: Optional[_lib.ReprojectInfo] = None, tables=None, **fields) -> None:
+        """hrt_reproject_motion (moments: hrt_reproject_motion_moments): ``reproject`` / ``reproject_moments`` with a
+        rigid motion per object -- ``spheres[i]`` for a hit of sphere i, ``meshes[m]`` for a hit of
+        mesh m, ``_lib.Motion`` records as ``motion_between`` makes them; a missing entry is static.  ``tables``: an
+        ``_lib.MotionTables`` instead.  The tables are copied before the call returns."""
+        info = info if info is not None else self.reproject_info(**fields)
+        keep = None
+        if tables is None:
+            tables, keep = self.motion_tables(spheres, meshes)
+        name = "hrt_reproject_motion_moments" if moments else "hrt_reproject_motion"
+        self._check(getattr(self.lib, name)(self.handle, ctypes.byref(info), ctypes.byref(tables), ctypes.byref(prev.record),
+                                            ctypes.c_void_p(prev_hits_ptr), ctypes.byref(cur.record),
+                                            ctypes.c_void_p(cur_hits_ptr)), name)
+        del keep
+
     def fill_moments(self, m1: float, m2: float) -> None:
         """hrt_fill_moments: every pixel's moments = (m1, m2)."""
         self._check(self.lib.hrt_fill_moments(self.handle, float(m1), float(m2)), "hrt_fill_moments")
@@ -1172,6 +1213,18 @@ class DiffusePipeline:
             self.ctx.accumulate_history_moments(max_history)
         else:
             self.ctx.accumulate_history(max_history)
+
+    def reproject_history(self, prev: "View", prev_hits_ptr: int, cur: "View", cur_hits_ptr: int, motion=None,
+                          moments: bool = False, **fields) -> None:
+        """The reprojection that precedes ``next_frame_history`` after a move: ``HrtContext.reproject[_moments]``, or,
+        with motion = (spheres, meshes) -- two sequences of ``motion_between`` records, either may be None -- the
+        form that follows moving objects (``HrtContext.reproject_motion``)."""
+        if motion is not None:
+            self.ctx.reproject_motion(prev, prev_hits_ptr, cur, cur_hits_ptr, motion[0], motion[1], moments, **fields)
+        elif moments:
+            self.ctx.reproject_moments(prev, prev_hits_ptr, cur, cur_hits_ptr, **fields)
+        else:
+            self.ctx.reproject(prev, prev_hits_ptr, cur, cur_hits_ptr, **fields)
 
     def next_frame_history_from(self, next_image: Image, offset=(0.0, 0.0), max_history: Optional[int] = None,
                                 moments: bool = False, fill: Optional[bool] = None, source_hits_ptr: Optional[int] = None,

@@ -41,7 +41,10 @@
 extern "C" {
 #endif
 
-/* 6, additive (no bump: nothing existing changed): temporal upsampling -- HRT_RESOLVE_FILL, HRT_RESOLVE_MOMENTS,
+/* 6, additive (no bump: nothing existing changed): object motion in the temporal history -- HRT_MOTION_MOVING,
+ * HRT_MOTION_MAX_OBJECTS, HRT_MOTION_RING, hrt_motion, hrt_motion_tables, hrt_reproject_motion,
+ * hrt_reproject_motion_moments (and hrt_host_motion_between in hrt_host.h).
+ * 6, additive (no bump: nothing existing changed): temporal upsampling -- HRT_RESOLVE_FILL, HRT_RESOLVE_MOMENTS,
  * hrt_resolve_info, hrt_resolve_defaults, hrt_set_ray_grid, hrt_history_phase, hrt_accumulate_history_from.
  * 6, additive (no bump: nothing existing changed): guided upsampling -- HRT_UPSAMPLE_FOOTPRINT, hrt_upsample_info,
  * hrt_upsample_defaults, hrt_upsample, hrt_upsample_present, hrt_order_after.
@@ -355,6 +358,23 @@ typedef struct hrt_reproject_info { /* 32 bytes */
   uint32_t reserved[4];  /* ignored */
 } hrt_reproject_info;
 
+/* ---- object motion in the temporal history (hrt_reproject_motion) ---- */
+#define HRT_MOTION_MOVING 1u          /* hrt_motion.flags bit 0: the object moved between the two frames */
+#define HRT_MOTION_MAX_OBJECTS 65536u /* the largest count of either table */
+#define HRT_MOTION_RING 4u            /* calls in flight before hrt_reproject_motion waits for the oldest one's pass */
+typedef struct hrt_motion { /* 64 bytes */
+  float m[12];          /* column-major 3x4 G = [L | b]: previous world point = L * current world point + b;
+                           L assumed a rotation (as hrt_view's mat3 is) */
+  uint32_t flags;       /* 0: the object did not move (S15's path, untouched); HRT_MOTION_MOVING */
+  uint32_t reserved[3]; /* ignored */
+} hrt_motion;
+typedef struct hrt_motion_tables { /* host arrays, copied before the call returns */
+  const hrt_motion* spheres; /* indexed by hrt_hit.index of a kind-1 hit */
+  uint32_t n_spheres;
+  const hrt_motion* meshes;  /* indexed by hrt_hit.mesh of a kind-2 hit */
+  uint32_t n_meshes;
+} hrt_motion_tables;
+
 /* ---- the variance-guided denoise (hrt_denoise_variance, the moments calls) ---- */
 /* hrt_variance_defaults' parameters: design parameters chosen on the CPU oracle's frames */
 #define HRT_VARIANCE_SIGMA 4.0f
@@ -562,6 +582,11 @@ HRT_STATIC_ASSERT(sizeof(hrt_refine_tiles_stats) == 40 && offsetof(hrt_refine_ti
                       offsetof(hrt_refine_tiles_stats, items) == 16 && offsetof(hrt_refine_tiles_stats, reserved) == 20 &&
                       offsetof(hrt_refine_tiles_stats, selected) == 24 && offsetof(hrt_refine_tiles_stats, pixels_traced) == 32,
                   "hrt_refine_tiles_stats");
+HRT_STATIC_ASSERT(sizeof(hrt_motion) == 64 && offsetof(hrt_motion, flags) == 48 && offsetof(hrt_motion, reserved) == 52,
+                  "hrt_motion");
+HRT_STATIC_ASSERT(sizeof(hrt_motion_tables) == 32 && offsetof(hrt_motion_tables, n_spheres) == 8 &&
+                      offsetof(hrt_motion_tables, meshes) == 16 && offsetof(hrt_motion_tables, n_meshes) == 24,
+                  "hrt_motion_tables");
 HRT_STATIC_ASSERT(sizeof(hrt_first_hits_stats) == 48 && offsetof(hrt_first_hits_stats, reserved) == 4 &&
                       offsetof(hrt_first_hits_stats, tiles) == 8 && offsetof(hrt_first_hits_stats, tiles_listed) == 12 &&
                       offsetof(hrt_first_hits_stats, tiles_empty) == 16 &&
@@ -1134,6 +1159,37 @@ hrt_status hrt_fill_history(hrt_context* ctx, uint32_t count);
 /* BLOCKING: the count image, height x width uint32 in trace-image row order, to host or device memory at dst
  * (bytes >= height * width * 4). */
 hrt_status hrt_read_history(hrt_context* ctx, uint32_t* dst, size_t bytes);
+
+/* ---- object motion in the temporal history (DESIGN.md §2 S21 pins the arithmetic, §36 the kernels) ---------
+ * hrt_reproject and hrt_reproject_moments assume that only the camera moved: the current pixel's surface point is
+ * looked up at the same world position in the previous view.  hrt_reproject_motion and
+ * hrt_reproject_motion_moments are those two calls with a rigid motion per object: a pixel whose current hit is
+ * sphere i (kind 1, hrt_hit.index == i) takes motion->spheres[i], one whose hit is a triangle of mesh m (kind 2,
+ * hrt_hit.mesh == m) takes motion->meshes[m]; when that entry has HRT_MOTION_MOVING the surface point goes through
+ * G to where it was in the previous frame before it is looked up there, and the current normal goes through G's
+ * linear part before the normal test.  An index at or past its table's count, an entry with flags == 0 and a
+ * miss are static: they take S15's statements, not a multiplication by an identity, so a call whose tables are
+ * empty or all static writes hrt_reproject[_moments]' bytes.  Every byte is defined by S21: both libraries and the
+ * numpy restatement in tests/motion_ref.py agree bit for bit.
+ *
+ * The tables are HOST arrays.  They are copied before the call returns: the caller may overwrite or free them at
+ * once.  The calls do not wait for the device: the copy goes through a ring of HRT_MOTION_RING pinned staging
+ * slots of the context's own (each with its device copy, written by a stream-ordered copy), and a call blocks
+ * only when all of them belong to passes that have not run yet -- then for the oldest one (and once more when a
+ * slot has to grow for a larger table).  A NULL table with count 0 is allowed.
+ *
+ * Everything else is hrt_reproject[_moments]': the ordering on the context's stream, the swap of the accumulator,
+ * N and M, the statistics, counters, tickets, fold records and trace images that stay untouched, and every
+ * rejection (row-tile partitions and communicator-joined contexts included).  Rejected besides, with
+ * HRT_ERR_INVALID_ARGUMENT before anything is enqueued (the message names the reason): motion NULL; a count above
+ * HRT_MOTION_MAX_OBJECTS; a count that is not 0 with a NULL pointer; an entry with a flag bit other than
+ * HRT_MOTION_MOVING; a moving entry with a component of m that is not finite. */
+hrt_status hrt_reproject_motion(hrt_context* ctx, const hrt_reproject_info* info, const hrt_motion_tables* motion,
+                                const hrt_view* prev, const hrt_hit* prev_hits, const hrt_view* cur,
+                                const hrt_hit* cur_hits);
+hrt_status hrt_reproject_motion_moments(hrt_context* ctx, const hrt_reproject_info* info,
+                                        const hrt_motion_tables* motion, const hrt_view* prev, const hrt_hit* prev_hits,
+                                        const hrt_view* cur, const hrt_hit* cur_hits);
 
 /* ---- the variance-guided denoise (DESIGN.md §2 S16 pins the arithmetic, §31 the kernels) ------------------
  * Beside the accumulator and the count image N the context owns a moments image M: two floats per pixel, the

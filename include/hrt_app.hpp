@@ -197,6 +197,14 @@ inline hrt_view view_of(const Camera& camera, std::array<uint32_t, 2> image_size
   return v;
 }
 
+// Object motion (hrt_host_motion_between): the motion table entry of an object whose object-to-world pose -- a
+// column-major 3x4 [R | t], R a rotation -- was prev_pose in the previous frame and is cur_pose now.
+inline hrt_motion motion_between(const std::array<float, 12>& prev_pose, const std::array<float, 12>& cur_pose) {
+  hrt_motion m{};
+  hrt_host_motion_between(prev_pose.data(), cur_pose.data(), &m);
+  return m;
+}
+
 // Temporal upsampling (hrt_history_phase): the sub-pixel offset {ox, oy} of frame k of a source_size grid that feeds a
 // target_size history through Context::accumulate_history_from.
 inline std::array<float, 2> history_phase(std::array<uint32_t, 2> source_size, std::array<uint32_t, 2> target_size,
@@ -396,6 +404,29 @@ class Context {
                          const hrt_reproject_info* info = nullptr) {
     const hrt_reproject_info ri = info ? *info : reproject_defaults();
     check(hrt_reproject_moments(get(), &ri, &prev, prev_hits, &cur, cur_hits), "hrt_reproject_moments", get());
+  }
+  // object motion in the temporal history (hrt_reproject_motion[_moments]; not a reference feature): reproject /
+  // reproject_moments with a rigid motion per object -- spheres[i] for a hit of sphere i, meshes[m] for a hit of
+  // mesh m, records as epq::motion_between makes them; a missing entry is static.  The vectors are copied before
+  // the call returns; the call only enqueues.
+  void reproject_motion(const std::vector<hrt_motion>& spheres, const std::vector<hrt_motion>& meshes, const hrt_view& prev,
+                        const hrt_hit* prev_hits, const hrt_view& cur, const hrt_hit* cur_hits,
+                        const hrt_reproject_info* info = nullptr) {
+    const hrt_reproject_info ri = info ? *info : reproject_defaults();
+    const hrt_motion_tables t = motion_tables(spheres, meshes);
+    check(hrt_reproject_motion(get(), &ri, &t, &prev, prev_hits, &cur, cur_hits), "hrt_reproject_motion", get());
+  }
+  void reproject_motion_moments(const std::vector<hrt_motion>& spheres, const std::vector<hrt_motion>& meshes,
+                                const hrt_view& prev, const hrt_hit* prev_hits, const hrt_view& cur,
+                                const hrt_hit* cur_hits, const hrt_reproject_info* info = nullptr) {
+    const hrt_reproject_info ri = info ? *info : reproject_defaults();
+    const hrt_motion_tables t = motion_tables(spheres, meshes);
+    check(hrt_reproject_motion_moments(get(), &ri, &t, &prev, prev_hits, &cur, cur_hits), "hrt_reproject_motion_moments",
+          get());
+  }
+  static hrt_motion_tables motion_tables(const std::vector<hrt_motion>& spheres, const std::vector<hrt_motion>& meshes) {
+    return hrt_motion_tables{spheres.empty() ? nullptr : spheres.data(), (uint32_t)spheres.size(),
+                             meshes.empty() ? nullptr : meshes.data(), (uint32_t)meshes.size()};
   }
   void fill_moments(float m1, float m2) { check(hrt_fill_moments(get(), m1, m2), "hrt_fill_moments", get()); }
   std::vector<float> read_moments() {

@@ -11,6 +11,8 @@
  *   hrt_host_view_matrix       get_view_matrix        src/raytrace_pipeline.rs:269-285
  *   hrt_host_transform_meshes  transform_meshes       src/raytrace_pipeline.rs:377-428
  *                              (+ create_mesh_subbuffer :363-374 first_index bookkeeping)
+ *   hrt_host_motion_between    (no counterpart: the reference's scenes do not move) the per-object rigid
+ *                              motion hrt_reproject_motion takes
  *   hrt_obj_*                  graphics::load_obj (rust_vulkan_graphics@b3c6a9c4, external):
  *                              one mesh per `o` record, file order, face winding preserved
  *                              (called at src/main.rs:131,237,283)
@@ -61,6 +63,13 @@ int64_t hrt_debug_bvh_wq_nodes_bfs(const hrt_triangle* tris, uint32_t n_tris, co
 /* Column-major mat4 for push_constants.cam_alignment_mat: columns = normalised direction,
  * new_y, new_z (so mat3(M) * (1,0,0) = direction / |direction|), 4th column (0,0,0,1). */
 void hrt_host_view_matrix(const float direction[3], const float up[3], float out[16]);
+
+/* The motion table entry (hrt_reproject_motion) of an object whose object-to-world pose was prev_pose in the
+ * previous frame and is cur_pose now -- column-major 3x4 [R | t], R a rotation: out = prev o cur^-1, that is
+ * L = Rp * Rc^T (L[r][c] = (Rp[r][0] * Rc[c][0] + Rp[r][1] * Rc[c][1]) + Rp[r][2] * Rc[c][2]) and b = tp - L * tc
+ * ((L * tc).r = (L[r][0] * tc.x + L[r][1] * tc.y) + L[r][2] * tc.z), each operation rounded as written.  flags is
+ * HRT_MOTION_MOVING unless the two poses are bytewise equal; reserved is zeroed. */
+void hrt_host_motion_between(const float prev_pose[12], const float cur_pose[12], hrt_motion* out);
 
 /* Flatten meshes into triangle and mesh records.  For mesh m: positions_m (n_verts_m * 3 floats),
  * indices_m (n_idx_m, a multiple of 3, 0-based into positions_m), material_m.

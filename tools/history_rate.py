@@ -17,6 +17,17 @@ accumulator in and out, trace texel and count in, count out (20 / 56 B; hrt_accu
 traffic over the time as a fraction of the HBM peak (8 TB/s); fold_history / accumulate as a ratio, and the
 share of pixels each move keeps.  One JSON line per mode, appended to --out (default
 profiles/history_rate.jsonl).
+
+--motion: what the motion forms cost beside the plain ones (hrt_reproject_motion[_moments]): island
+and cave at 1920x1080, both modes, the small move, BILINEAR.  Variants, taking turns in the same way (two warm-up
+rounds, five timed calls each, timed to hrt_synchronize, the host copy of the tables included):
+
+  plain, plain_moments               hrt_reproject, hrt_reproject_moments
+  one_mesh, one_mesh_moments         the motion forms with mesh 0 moving by about two pixels, the others static
+  all, all_moments                   ... with every mesh moving
+
+The scene itself stays where it is: the pass reads the same hit records either way, and its cost does not depend on
+whether the tables tell the truth.  One JSON line per scene and mode ("tool": "history_rate --motion").
 """
 import argparse
 import json
@@ -46,14 +57,82 @@ def turned(E, cam, dpos, turn):
     return E.Camera([float(a + b) for a, b in zip(cam.position, dpos)], [float(v) for v in nd], cam.up)
 
 
+def motion_rates(E, _lib, torch):
+    """--motion: one record per scene and mode."""
+    W, H = SIZE
+    px = 2.0 / H
+    lines = []
+    for scene in ("island", "cave"):
+        for mode_name, mode in (("rgba8", _lib.MODE_RGBA8), ("rgba32f", _lib.MODE_RGBA32F)):
+            camera, settings = E.preset(scene)
+            settings.num_samples, settings.max_bounces = 1, 8
+            ctx = E.HrtContext(SIZE, device=0, mode=mode)
+            raytrace, diffuse = E.RayTracePipeline(ctx, SIZE, settings), E.DiffusePipeline(ctx, SIZE)
+            for frame in range(4):
+                raytrace.compute(camera, frame)
+                diffuse.next_frame_history(raytrace.image(), moments=True)
+            cams = {"base": camera, "small": turned(E, camera, (0.02, 0.0, 0.01), (2 * px, -px))}
+            views = {k: E.View(c, SIZE, settings) for k, c in cams.items()}
+            hits = {k: torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0") for k in cams}
+            for k, c in cams.items():
+                raytrace.first_hits_into(c, hits[k].data_ptr())
+            info = ctx.reproject_info(filter=_lib.REPROJECT_BILINEAR)
+            n = len(settings.mesh_data)
+            depth = float(np.linalg.norm(np.asarray(camera.position, np.float64)))  # the scenes sit around the origin
+            ident = [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0]
+            moved = E.motion_between(ident, ident[:9] + [2 * px * depth, 0.0, px * depth])
+            still = E.motion_between(ident, ident)
+            tables = {"one_mesh": ctx.motion_tables(None, [moved] + [still] * (n - 1)),
+                      "all": ctx.motion_tables(None, [moved] * n)}
+            args = (views["base"], hits["base"].data_ptr(), views["small"], hits["small"].data_ptr())
+
+            def plain(moments):
+                (ctx.reproject_moments if moments else ctx.reproject)(*args, info)
+
+            def motion(which, moments):
+                ctx.reproject_motion(*args, moments=moments, info=info, tables=tables[which][0])
+
+            variants = {"plain": lambda: plain(False), "plain_moments": lambda: plain(True)}
+            for which in tables:
+                variants[which] = lambda which=which: motion(which, False)
+                variants[which + "_moments"] = lambda which=which: motion(which, True)
+            runs = {v: [] for v in variants}
+            for rnd in range(WARMUP + CALLS):
+                for v, call in variants.items():
+                    ctx.fill_history(8)
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    ctx.synchronize()
+                    if rnd >= WARMUP:
+                        runs[v].append((time.perf_counter() - t0) * 1e3)
+            rec = {"tool": "history_rate --motion", "scene": scene, "width": W, "height": H, "mode": mode_name,
+                   "calls": CALLS, "warmup": WARMUP, "meshes": n, "build_id": _lib.build_id(), "variants": {}}
+            for v in variants:
+                rec["variants"][v] = {"median_ms": round(statistics.median(runs[v]), 4), "min_ms": round(min(runs[v]), 4),
+                                      "max_ms": round(max(runs[v]), 4)}
+            ctx.close()
+            lines.append(json.dumps(rec))
+            print(lines[-1], flush=True)
+    return lines
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "history_rate.jsonl"))
+    ap.add_argument("--motion", action="store_true", help="the motion forms beside the plain ones (see above)")
     a = ap.parse_args()
     import torch
 
     import epq_raytracer_amd as E
     from epq_raytracer_amd import _lib
+
+    if a.motion:
+        lines = motion_rates(E, _lib, torch)
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+        return 0
 
     W, H = SIZE
     px = 2.0 / H

@@ -45,6 +45,12 @@ and writes profiles/present_loop_upsample.jsonl with j / i, j - i and whether th
      full-size context hrt_first_hits, hrt_reproject_moments, hrt_accumulate_history_from (the half-size trace image
      folded into the pixels its samples landed in, with moments) and hrt_denoise_variance_present -- all enqueued
 and writes profiles/present_loop_resolve.jsonl with k / i, k / j, k - j and whether k lies between j and i.
+--objects runs two variants of the moving loop only, taking turns in one sitting: i, and
+  m  i with one object moving as well: every frame hrt_set_scene with mesh 0 shifted (one of eight precomputed states,
+     about two pixels apart), hrt_first_hits, and hrt_reproject_motion_moments with hrt_host_motion_between of the
+     two states in place of hrt_reproject_moments.  hrt_set_scene rebuilds the scene and waits for the device: the
+     host time spent inside it is reported separately (set_scene_ms_per_frame)
+and writes profiles/present_loop_motion.jsonl with m / i, m - i and hrt_set_scene's share of m.
 Every child runs under its own time limit and the first failing one ends the run.  One JSON line per
 child, then a summary line (median and spread per variant, c / b and d / c).
 """
@@ -65,6 +71,7 @@ MOVING_VARIANTS = ("e", "f", "g", "h")
 VARIANCE_VARIANTS = ("h", "i")
 UPSAMPLE_VARIANTS = ("i", "j")
 RESOLVE_VARIANTS = ("i", "j", "k")
+OBJECTS_VARIANTS = ("i", "m")
 MAX_HISTORY = 32
 SCENE, SIZE, SPP, BOUNCES, WARMUP, FRAMES, LAG = "island", (1920, 1080), 64, 8, 5, 32, 3
 
@@ -103,7 +110,7 @@ def child(variant: str, parts: int = 1) -> dict:
         guide = torch.empty((H * W, 8), dtype=torch.float32, device="cuda:0")  # hrt_hit records
         raytraces[0].first_hits_into(camera, guide.data_ptr())
 
-    moving = variant in ("f", "g", "h", "i", "j", "k")
+    moving = variant in ("f", "g", "h", "i", "j", "k", "m")
     if moving:
         import numpy as np
 
@@ -111,7 +118,7 @@ def child(variant: str, parts: int = 1) -> dict:
         # the last LAG frames still read is never overwritten
         # (h: two -- its passes are ordered on the stream behind the readers of the buffer they overwrite)
         guides = [torch.empty((size[0] * size[1], 8), dtype=torch.float32, device="cuda:0")
-                  for _ in range(2 if variant in ("h", "i", "j", "k") else LAG + 2)]
+                  for _ in range(2 if variant in ("h", "i", "j", "k", "m") else LAG + 2)]
         guide_ctx, guide_rt = ctx, raytraces[0]
         if variant == "g":
             guide_ctx = E.HrtContext(SIZE, device=0, mode=_lib.MODE_RGBA8)
@@ -128,6 +135,19 @@ def child(variant: str, parts: int = 1) -> dict:
             low_settings.sample_jitter = raytraces[0].sample_jitter  # the full-size grid's default jitter
             low_ctx = E.HrtContext(low_size, device=0, mode=_lib.MODE_RGBA8)
             low_rt = E.RayTracePipeline(low_ctx, low_size, low_settings)
+        if variant == "m":  # eight states of the scene: mesh 0 swaying along x, records made ahead of the loop
+            import copy
+            states, set_scene_s = [], [0.0]
+            for k in range(8):
+                shift = np.array([0.15 * np.sin(2 * np.pi * k / 8), 0.0, 0.0], np.float32)
+                st_settings = E.preset(SCENE)[1]
+                m0 = copy.deepcopy(st_settings.mesh_data[0])
+                m0.mesh.positions = (np.asarray(m0.mesh.positions, np.float32) + shift).astype(np.float32)
+                st_settings.mesh_data[0] = m0
+                tris, meshes = E.transform_meshes(st_settings.mesh_data)
+                states.append((tris, meshes, [1, 0, 0, 0, 1, 0, 0, 0, 1] + [float(v) for v in shift]))
+            still = E.motion_between(states[0][2], states[0][2])
+            # (frames count from 1 and states[0] has no shift: the first frame's previous state is the preset's scene)
         d0 = np.asarray(camera.direction, np.float64) / np.linalg.norm(camera.direction)
         side = np.cross(d0, np.asarray(camera.up, np.float64))
         side /= np.linalg.norm(side)
@@ -159,6 +179,23 @@ def child(variant: str, parts: int = 1) -> dict:
             guide_rt.first_hits_async(cam, cur_hits.data_ptr())
             ctx.reproject_moments(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr())
             ctx.accumulate_history_from(low_ctx, off, MAX_HISTORY, moments=True)
+            tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
+            if len(tickets) > LAG:
+                ctx.present_wait(tickets[-1 - LAG])
+            prev_view = view
+            frame += 1
+            return
+        if variant == "m":
+            rt = raytraces[0]
+            prev_state, state = states[(frame - 1) % 8], states[frame % 8]
+            t_set = time.perf_counter()
+            ctx.set_scene(rt.rays, rt.spheres, state[0], state[1])
+            set_scene_s[0] += time.perf_counter() - t_set
+            guide_rt.first_hits_async(cam, cur_hits.data_ptr())
+            rt.compute(cam, frame)
+            table = [E.motion_between(prev_state[2], state[2])] + [still] * (len(state[1]) - 1)
+            ctx.reproject_motion(prev_view, prev_hits.data_ptr(), view, cur_hits.data_ptr(), meshes=table, moments=True)
+            diffuses[0].next_frame_history(rt.image(), MAX_HISTORY, moments=True)
             tickets.append(ctx.denoise_variance_present(dst, nbytes, W, H, guide_ptr=cur_hits.data_ptr()))
             if len(tickets) > LAG:
                 ctx.present_wait(tickets[-1 - LAG])
@@ -214,6 +251,8 @@ def child(variant: str, parts: int = 1) -> dict:
         step()
     for c in ctxs:
         c.synchronize()
+    if variant == "m":
+        set_scene_s[0] = 0.0
     t0 = time.perf_counter()
     for _ in range(FRAMES):
         step()
@@ -233,6 +272,8 @@ def child(variant: str, parts: int = 1) -> dict:
     out = {"variant": variant, "parts": parts, "ms_per_frame": round(ms, 4), "frames": FRAMES, "warmup": WARMUP, "scene": SCENE,
            "width": W, "height": H, "render_width": size[0], "render_height": size[1], "spp": SPP, "bounces": BOUNCES, "kernel": _lib.KERNEL_NAMES[last_kernel],
            "accumulates": st.accumulates, "tickets": len(tickets), "build_id": _lib.build_id()}
+    if variant == "m":
+        out["set_scene_ms_per_frame"] = round(set_scene_s[0] * 1e3 / FRAMES, 4)
     if variant == "g":
         guide_ctx.close()
     if variant == "j":
@@ -246,7 +287,7 @@ def child(variant: str, parts: int = 1) -> dict:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i", "j", "k"), help="run one variant in this process (what the driver starts)")
+    ap.add_argument("--variant", choices=VARIANTS + ("e", "f", "g", "h", "i", "j", "k", "m"), help="run one variant in this process (what the driver starts)")
     ap.add_argument("--parts", type=int, default=1, help="contexts of 8-row tiles on device 0, joined as one group")
     ap.add_argument("--out", default=None, help="default profiles/present_loop.jsonl (present_loop_group.jsonl "
                                                 "with --parts above 1, appended to)")
@@ -262,6 +303,9 @@ def main() -> int:
     ap.add_argument("--resolve", action="store_true",
                     help="variants i, j and k (the trace at half size on a shifted grid, the history at full size through "
                          "hrt_accumulate_history_from) only, taking turns")
+    ap.add_argument("--objects", action="store_true",
+                    help="variants i and m (i with one object moved every frame: hrt_set_scene and "
+                         "hrt_reproject_motion_moments) only, taking turns")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--baseline-lib", default=None,
                     help="another build of libhip_raytrace.so (same ABI): each repeat also runs variant b on it "
@@ -273,13 +317,13 @@ def main() -> int:
     if a.variant:
         print(json.dumps(child(a.variant, a.parts)), flush=True)
         return 0
-    if (a.denoise or a.moving or a.variance or a.upsample or a.resolve) and a.parts > 1:
+    if (a.denoise or a.moving or a.variance or a.upsample or a.resolve or a.objects) and a.parts > 1:
         ap.error("--denoise, --moving and --variance run on a single context (a partitioned context cannot denoise or keep "
                  "history)")
     if a.out is None:
-        name = "present_loop_resolve.jsonl" if a.resolve else "present_loop_upsample.jsonl" if a.upsample else "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
+        name = "present_loop_motion.jsonl" if a.objects else "present_loop_resolve.jsonl" if a.resolve else "present_loop_upsample.jsonl" if a.upsample else "present_loop_variance.jsonl" if a.variance else "present_loop_history.jsonl" if a.moving else "present_loop_denoise.jsonl" if a.denoise else "present_loop_group.jsonl" if a.parts > 1 else "present_loop.jsonl"
         a.out = os.path.join(ROOT, "profiles", name)
-    variants = RESOLVE_VARIANTS if a.resolve else UPSAMPLE_VARIANTS if a.upsample else VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
+    variants = OBJECTS_VARIANTS if a.objects else RESOLVE_VARIANTS if a.resolve else UPSAMPLE_VARIANTS if a.upsample else VARIANCE_VARIANTS if a.variance else MOVING_VARIANTS if a.moving else DENOISE_VARIANTS if a.denoise else VARIANTS
     order = ([("b_baseline", "b", a.baseline_lib)] if a.baseline_lib else []) + [(v, v, None) for v in variants]
     runs = {name: [] for name, _, _ in order}
     lines = []
@@ -304,7 +348,13 @@ def main() -> int:
     summary = {"parts": a.parts,
                "summary": {v: {"median_ms": round(med[v], 4), "min_ms": min(runs[v]), "max_ms": max(runs[v]),
                                "spread_ms": round(max(runs[v]) - min(runs[v]), 4)} for v in runs}}
-    if a.resolve:
+    if a.objects:
+        sets = [json.loads(ln)["set_scene_ms_per_frame"] for ln in lines if json.loads(ln).get("run") == "m"]
+        summary.update(m_over_i=round(med["m"] / med["i"], 4), m_minus_i_ms=round(med["m"] - med["i"], 4),
+                       set_scene_median_ms=round(statistics.median(sets), 4),
+                       set_scene_share_of_m=round(statistics.median(sets) / med["m"], 4),
+                       ranges_apart=max(runs["m"]) < min(runs["i"]) or max(runs["i"]) < min(runs["m"]))
+    elif a.resolve:
         lo_ms, hi_ms = sorted((med["j"], med["i"]))
         summary.update(k_over_i=round(med["k"] / med["i"], 4), k_over_j=round(med["k"] / med["j"], 4),
                        k_minus_j_ms=round(med["k"] - med["j"], 4), k_minus_i_ms=round(med["k"] - med["i"], 4),
