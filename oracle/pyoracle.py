@@ -1,8 +1,11 @@
 """ctypes front-end of the CPU oracle (oracle/rt_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
-leg -- never by the product.  Parity status: "parity unpinned" against the GLSL reference (which
-cannot run here); pinned by the RNG known-answer vectors and analytic KATs.
+leg -- never by the product.  Parity status: the oracle is pinned to the text of the
+reference's shaders -- load_glsl_ref() is that text compiled as C++ (oracle/glsl_ref/, built where a
+reference checkout exists) and tests/test_glsl_ref.py compares the two bit for bit -- and by the RNG
+known-answer vectors and analytic KATs.  A Vulkan driver's own numerics, the SPIR-V compiler's
+evaluation order and the Rust host prep remain unpinned (the GLSL path cannot run here).
 """
 from __future__ import annotations
 
@@ -267,6 +270,96 @@ def accumulate_rgba32f(frame: int, current: np.ndarray, new_image: np.ndarray) -
 
 def num_threads() -> int:
     return load().orc_num_threads()
+
+
+# ---- the reference's own shader text, compiled as C++ (oracle/glsl_ref/) --------------------------------------------
+
+REF_BUILD = os.path.join(HERE, "_ref")
+_glsl = None
+
+
+def reference_dir() -> str:
+    return os.environ.get("HRT_REFERENCE_DIR", "/root/reference")
+
+
+def have_reference() -> bool:
+    return os.path.exists(os.path.join(reference_dir(), "assets", "raytracing.glsl"))
+
+
+def load_glsl_ref():
+    """oracle/_ref/libglslref.so: the reference's two shaders, translated mechanically and compiled against
+    glsl_ref/glsl_shim.hpp (`make -C oracle glsl_ref`).  Built here when a reference checkout exists; a machine
+    without one loads what an earlier build left.  None only when there is neither."""
+    global _glsl
+    if _glsl is not None:
+        return _glsl
+    path = os.path.join(REF_BUILD, "libglslref.so")
+    if have_reference() and not os.path.exists(path):
+        build()
+    if not os.path.exists(path):
+        return None
+    lib = ctypes.CDLL(path)
+    lib.glr_selfcheck.restype = c_int
+    _glsl = lib
+    return lib
+
+
+def batch(lib, name: str, *args) -> None:
+    """Call one of the batched exports (orc_b_* of rt_oracle.c, glr_* of glsl_ref/rt_harness.inc; both take the same
+    lists): ints go as uint32, arrays and None as pointers, ctypes structures by reference.  Arrays are used in
+    place (outputs and RNG states are written back), so they must be C-contiguous and of the export's dtype."""
+    conv = []
+    for a in args:
+        if a is None:
+            conv.append(c_void_p(0))
+        elif isinstance(a, (int, np.integer)):
+            conv.append(c_uint32(int(a)))
+        elif isinstance(a, np.ndarray):
+            assert a.flags["C_CONTIGUOUS"]
+            conv.append(c_void_p(a.ctypes.data if a.size else 0))
+        else:
+            conv.append(ctypes.byref(a))
+    fn = getattr(lib, name)
+    fn.restype = None
+    fn(*conv)
+
+
+def glsl_trace(pc, rays, spheres, tris, meshes, rows=None, nthreads: int = 0):
+    """The shader's frame (or its rows [y0, y1)): (rgba8 (H, W, 4), the float vec4s it stored (H, W, 4), reads of the
+    triangle buffer).  Same record arrays as trace()."""
+    lib = load_glsl_ref()
+    W, H = pc.width, pc.height
+    y0, y1 = (0, H) if rows is None else rows
+    img8, img32 = np.zeros((H, W, 4), np.uint8), np.zeros((H, W, 4), np.float32)
+    tt = c_uint64()
+    keep = [np.ascontiguousarray(rays).view(np.uint8), _bytes(spheres), _bytes(tris), _bytes(meshes)]
+    lib.glr_trace_rows.restype = None
+    lib.glr_trace_rows(ctypes.byref(pc), *[_p(a) for a in keep], c_uint32(y0), c_uint32(y1), _p(img8), _p(img32),
+                       ctypes.byref(tt), c_int(int(nthreads)))
+    return img8, img32, tt.value
+
+
+def glsl_trace_pixels(pc, rays, spheres, tris, meshes, xs, ys):
+    """The shader's main() at the listed pixels: (stored vec4s (n, 4) float32, texels (n, 4) uint8, per-pixel
+    triangle-buffer reads (n,) uint64)."""
+    lib = load_glsl_ref()
+    xy = np.ascontiguousarray(np.stack([np.asarray(xs, np.uint32), np.asarray(ys, np.uint32)], -1).reshape(-1))
+    n = len(xy) // 2
+    f32, u8, tests = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.uint8), np.zeros(n, np.uint64)
+    keep = [np.ascontiguousarray(rays).view(np.uint8), _bytes(spheres), _bytes(tris), _bytes(meshes)]
+    lib.glr_trace_pixels.restype = None
+    lib.glr_trace_pixels(ctypes.byref(pc), *[_p(a) for a in keep], _p(xy), c_uint32(n), _p(f32), _p(u8), _p(tests))
+    return f32, u8, tests
+
+
+def glsl_combine_rgba8(frame: int, current: np.ndarray, new_image: np.ndarray) -> None:
+    """image_combiner.glsl's fold of new_image into current ((H, W, 4) uint8, in place) as frame `frame`."""
+    assert current.dtype == np.uint8 and new_image.dtype == np.uint8 and current.shape == new_image.shape
+    assert current.ndim == 3 and current.shape[2] == 4 and current.flags["C_CONTIGUOUS"]
+    lib = load_glsl_ref()
+    nw = np.ascontiguousarray(new_image)
+    lib.glr_combine_rgba8.restype = None
+    lib.glr_combine_rgba8(c_uint32(frame), _p(current), _p(nw), c_uint32(current.shape[1]), c_uint32(current.shape[0]))
 
 
 def _bytes(a):

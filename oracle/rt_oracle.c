@@ -5,11 +5,16 @@
  * cpu_baseline leg may load this library, and only as the checker / the timed CPU
  * baseline.  The product (epq_raytracer_amd/, libhip_raytrace.so) never links it.
  *
- * PARITY STATUS: "parity unpinned" against the GLSL path itself.  The reference is
- * Rust + Vulkan (vulkano 0.33) and cannot be built or run in this container (no
+ * PARITY STATUS: pinned to the TEXT of the reference's two shaders.  The
+ * reference is Rust + Vulkan (vulkano 0.33) and cannot be built or run here (no
  * cargo/rustc, no glslang, no Vulkan ICD; git deps rust_maths@992a952d and
- * rust_vulkan_graphics@b3c6a9c4 are not vendored -- SURVEY.md 8(c)).  The reference
- * ships no tests, golden images or fixtures.  What IS pinned:
+ * rust_vulkan_graphics@b3c6a9c4 are not vendored -- SURVEY.md 8(c)) and ships no tests,
+ * golden images or fixtures; but oracle/glsl_ref/ compiles assets/raytracing.glsl and
+ * assets/image_combiner.glsl themselves as C++ against a shim of the builtins written from
+ * S1-S7 below, and tests/test_glsl_ref.py holds every function and whole frames of this
+ * file to that library bit for bit (the orc_b_* exports at the end exist for it).  Still
+ * unpinned: a Vulkan driver's own numerics and evaluation order, and the Rust host prep.
+ * Also pinned:
  *   - the integer RNG (assets/raytracing.glsl:13-25) against the known-answer
  *     vectors derived in SURVEY.md 8(c) (tests/test_oracle.py);
  *   - analytic known-answer cases for every intersection routine;
@@ -629,6 +634,79 @@ void orc_transform_mesh(const float* positions, const uint32_t* indices, uint32_
     t->normal[0] = n.x; t->normal[1] = n.y; t->normal[2] = n.z; t->normal[3] = 1.0f;
   }
   mn[0] = mnx; mn[1] = mny; mn[2] = mnz; mx[0] = mxx; mx[1] = mxy; mx[2] = mxz;
+}
+
+/* ---------------------------------------------------------------------------------
+ * Batched exports, one per function of assets/raytracing.glsl, for tests/test_glsl_ref.py: the
+ * same argument lists as the glr_* entries of oracle/glsl_ref/rt_harness.inc, n independent
+ * cases each; `states` arrays are read and written back.  A hit is 19 floats: normal, position,
+ * distance, material (empty_mat() when nothing was hit).
+ * ------------------------------------------------------------------------------- */
+static inline void st3(float* p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+static void st_hit(float* p, const orc_hit* h) {
+  static const orc_material empty = {{0, 0, 0, 1}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  st3(p, h->hit_normal); st3(p + 3, h->hit_pos); p[6] = h->hit_dist;
+  memcpy(p + 7, h->hit_mat ? h->hit_mat : &empty, sizeof empty);
+}
+void orc_b_hash(uint32_t n, uint32_t* states, uint32_t* out) {
+  for (uint32_t k = 0; k < n; k++) out[k] = orc_hash(&states[k]);
+}
+void orc_b_scale01(uint32_t n, const uint32_t* in, float* out) {
+  for (uint32_t k = 0; k < n; k++) out[k] = orc_u01(in[k]);
+}
+void orc_b_normal_dist(uint32_t n, uint32_t* states, float* out) {
+  for (uint32_t k = 0; k < n; k++) out[k] = orc_normal(&states[k]);
+}
+void orc_b_point_on_sphere(uint32_t n, uint32_t* states, float* out) {
+  for (uint32_t k = 0; k < n; k++) st3(out + 3 * k, orc_unit_sphere(&states[k]));
+}
+void orc_b_get_ray_dir(uint32_t n, const orc_push* pc, const float* centres, uint32_t* states, float* out) {
+  for (uint32_t k = 0; k < n; k++) st3(out + 3 * k, get_ray_dir(pc, ld3(centres + 3 * k), &states[k]));
+}
+void orc_b_intersecting_sphere(uint32_t n, const orc_sphere* spheres, const float* o, const float* d, float* out) {
+  for (uint32_t k = 0; k < n; k++) {
+    orc_hit h = intersecting_sphere(&spheres[k], ld3(o + 3 * k), ld3(d + 3 * k));
+    st_hit(out + 19 * k, &h);
+  }
+}
+void orc_b_intersecting_aabb(uint32_t n, const float* mn, const float* mx, const float* o, const float* d, int32_t* out) {
+  for (uint32_t k = 0; k < n; k++) out[k] = orc_intersecting_aabb(mn + 3 * k, mx + 3 * k, o + 3 * k, d + 3 * k);
+}
+void orc_b_intersecting_tri(uint32_t n, const orc_triangle* tris, const float* o, const float* d, float* out) {
+  for (uint32_t k = 0; k < n; k++) intersecting_tri(&tris[k], ld3(o + 3 * k), ld3(d + 3 * k), out + 4 * k);
+}
+void orc_b_intersecting_mesh(uint32_t n, const orc_triangle* tris, const orc_mesh* mesh, const float* o, const float* d,
+                             float* out, uint64_t* tri_tests) {
+  orc_world w = {NULL, 0, tris, mesh, 1, 0, 0};
+  for (uint32_t k = 0; k < n; k++) {
+    orc_hit h = intersecting_mesh(&w, mesh, ld3(o + 3 * k), ld3(d + 3 * k));
+    st_hit(out + 19 * k, &h);
+  }
+  if (tri_tests) *tri_tests = w.tri_tests;
+}
+void orc_b_world_hit(uint32_t n, const orc_push* pc, const orc_sphere* spheres, const orc_triangle* tris,
+                     const orc_mesh* meshes, const float* o, const float* d, float* out, uint64_t* tri_tests) {
+  orc_world w = {spheres, pc->num_spheres, tris, meshes, pc->num_meshes, 0, 0};
+  for (uint32_t k = 0; k < n; k++) {
+    orc_hit h = world_hit(&w, ld3(o + 3 * k), ld3(d + 3 * k));
+    st_hit(out + 19 * k, &h);
+  }
+  if (tri_tests) *tri_tests = w.tri_tests;
+}
+void orc_b_environment_light(uint32_t n, const orc_push* pc, const float* d, float* out) {
+  for (uint32_t k = 0; k < n; k++) st3(out + 3 * k, environment_light(pc, ld3(d + 3 * k)));
+}
+void orc_b_adjust_dir(uint32_t n, const float* d, const float* normals, const orc_material* mats, const int32_t* specular,
+                      uint32_t* states, float* out) {
+  for (uint32_t k = 0; k < n; k++)
+    st3(out + 3 * k, adjust_dir(ld3(d + 3 * k), ld3(normals + 3 * k), &mats[k], specular[k] != 0, &states[k]));
+}
+void orc_b_trace_ray(uint32_t n, const orc_push* pc, const orc_sphere* spheres, const orc_triangle* tris,
+                     const orc_mesh* meshes, const float* o, const float* d, uint32_t* states, float* out,
+                     uint64_t* tri_tests) {
+  orc_world w = {spheres, pc->num_spheres, tris, meshes, pc->num_meshes, 0, 0};
+  for (uint32_t k = 0; k < n; k++) st3(out + 3 * k, trace_ray(&w, pc, ld3(o + 3 * k), ld3(d + 3 * k), &states[k]));
+  if (tri_tests) *tri_tests = w.tri_tests;
 }
 
 int orc_num_threads(void) {
